@@ -15,11 +15,14 @@ rendezvous_1s_dt0_01s.txt (tests/golden/ copy).  The default frame is 98 (camera
 frame 0 (1787 m, 99.9 % of the tiles provably empty and culled) is reported in `extras` as what it is: a culling rate.
 
 Tree: by default rays walk the CERTIFIED SECOND TREE (include/dsrt.h, dsrt_ctx_set_certified_tree): a SAH tree whose every answer the kernel certifies against the
-reference's own median-split tree, re-walking that tree when it cannot -- the reference's bytes with a third fewer node visits.  The line proves it on the run itself:
-`reference_kernel_fixture` compares the image of the last timed step with the image the reference's own kernel rendered of this frame (tests/golden/), `parity_rows`
+reference's own median-split tree, re-walking that tree when it cannot -- the reference's bytes with a third fewer node visits.  With --full the line proves it on the run
+itself: `reference_kernel_fixture` compares the image of the last timed step with the image the reference's own kernel rendered of this frame (tests/golden/), `parity_rows`
 with the CPU oracle's rows; `extras.reference_walk_only` times the same frame with every ray on the reference tree (`--tree reference` makes that the headline).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and, at N = 1, `cpu_baseline`.
+Prints ONE JSON line on rank 0: metric, value, unit, steps, ms_per_step, ... of the timed steps.  A plain run does nothing else: it sets up, warms up, times --steps
+steps, writes --dump-outputs DIR/image.npy if asked and prints the line.  --full adds every other measurement and check: `roofline`, `lane_slots` and the counting
+launch's figures, `extras` (single GPU), and at N = 1 `cpu_baseline`, `parity_rows` and the reference-kernel comparisons; at N > 1 the batch-launch, rng_mode 1 and
+scaling legs.
 
 roofline.  The path is branchy fp32 vector arithmetic over a scene that lives in L2 / Infinity Cache; the counters say it is bound
 by vector-ALU ISSUE (and, second, by the L1's request rate), not by HBM.  The object therefore carries
@@ -440,6 +443,23 @@ def fixture_check(rgb, fixture_name, args, obj, W, H, spp, depth):
     return rec
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rgb8):
+    """--dump-outputs: the H x W x 3 rgb8 image of the last timed step as out_dir/image.npy, float32 (the byte values 0..255, exact).  An image
+    above 64 MB in float32 is cut to a fixed sample of whole rows (seed 0, ascending), whose indices go to out_dir/image_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = rgb8.shape[:2]
+    img = rgb8.astype(np.float32)
+    if img.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - (1 << 20)) // (W * 3 * 4 + 8))
+        rows = np.sort(np.random.default_rng(0).choice(H, size=keep, replace=False))
+        img = img[rows]
+        np.save(os.path.join(out_dir, "image_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "image.npy"), img)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -452,9 +472,15 @@ def main():
     ap.add_argument("--frame", type=int, default=98)
     ap.add_argument("--tris", type=int, default=1000000)
     ap.add_argument("--obj", type=str, default="")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra single-GPU measurements (far frame 0; rng_mode 1; SAH tree; drop-in entry point)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 child passes (roofline fields that need counters become null)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: the counting launch (Mrays/s, coverage, lane slots), roofline calibration and "
+                         "PMC passes, single-GPU extras, CPU baselines and the oracle / reference-kernel comparisons, and on N > 1 GPUs the batch-launch, rng_mode 1 "
+                         "and scaling legs.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write the image of the last timed step as DIR/image.npy (float32 H x W x 3, the rgb8 values)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra single-GPU measurements (far frame 0; rng_mode 1; SAH tree; drop-in entry point)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines and the comparisons of the headline image with the oracle and the reference kernel")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 child passes (roofline fields that need counters become null)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--stack-entries", type=int, default=0)
     ap.add_argument("--sequence", action="store_true", help="config 5: render every pose of the file once (default 250 spp) and report frames/s")
@@ -473,10 +499,14 @@ def main():
     ap.add_argument("--tune3", type=int, default=0, help="--sequence: DsrtRenderDesc.tune[3], the DSRT_TUNE_* switches of include/dsrt.h (development switches: env DSRT_EXPERIMENT)")
     ap.add_argument("--tree", choices=["certified", "reference"], default="certified",
                     help="certified (default): rays walk the certified second tree (dsrt_ctx_set_certified_tree: a SAH tree whose every answer the kernel certifies against the "
-                         "reference's median-split tree, re-walking that tree when it cannot) -- the reference's bytes, checked against the reference kernel's own image in this "
-                         "line; reference: every ray walks the reference tree (the plain walk; also timed as extras.reference_walk_only)")
+                         "reference's median-split tree, re-walking that tree when it cannot) -- the reference's bytes, checked against the reference kernel's own image in the "
+                         "--full line; reference: every ray walks the reference tree (the plain walk; also timed as extras.reference_walk_only)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.sequence:
+        ap.error("--dump-outputs covers the single-frame benchmark, not --sequence")
 
     if args.tree == "certified" and args.bvh == "median":
         os.environ.setdefault("DSRT_CERTIFIED_TREE", "1")          # contexts the library creates itself (dsrt_multi_*, the drop-in gpu_render_scene) follow the same choice
@@ -583,9 +613,11 @@ def main():
         t0 = time.perf_counter()
         per_rank = []
         for _ in range(args.steps):
-            _, ms, _ = multi.render_frame(desc, cam, tuple(fr.sun_dir_model))
+            img, ms, _ = multi.render_frame(desc, cam, tuple(fr.sun_dir_model))
             per_rank.append(ms)
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img)
         print(json.dumps({"metric": "Msamples/s (ISS-mesh frame, 1920x1080 @1000spp path-traced samples per second, whole job)", "value": W * H * spp * args.steps / dt / 1e6,
                           "unit": "Msamples/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
                           "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -682,8 +714,10 @@ def main():
     dt = timed(args.steps, args.warmup)
     my_kernel_ms = sum(kernel_ms) / max(1, len(kernel_ms))
     headline_stats = list(last_stats)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image[:W * H * 3].cpu().numpy().reshape(H, W, 3))
     # the image of the last timed step, kept on the host for the parity check against the oracle's rows (after the timed region, before anything overwrites it)
-    headline_image = image[:W * H * 3].cpu().numpy().reshape(H, W, 3) if rank == 0 and not args.no_cpu else None
+    headline_image = image[:W * H * 3].cpu().numpy().reshape(H, W, 3) if rank == 0 and args.full and not args.no_cpu else None
     headline_fixture = fixture_check(headline_image, "ref_gpu_detmath_images.json", args, obj, W, H, spp, depth) if headline_image is not None else None
     rehearsal_report = None
     if rehearsal and rank == 0:                                     # (before the rng_mode 1 steps below overwrite `image`)
@@ -694,7 +728,7 @@ def main():
     # one frame's serial chains run under the others), one gather and one de-interleave for the lot.  Reported beside the headline, which
     # stays one launch per step, each waited for.
     batched = None
-    if shard:
+    if shard and args.full:
         nb = max(2, args.steps)
         pbytes = lay["rgb8_bytes_padded"]
         bbuf = bimg = None
@@ -732,7 +766,7 @@ def main():
     # N > 1: the same sharded step with rng_mode 1 (a Philox sub-sequence per sample: the mode whose work units are samples, not
     # 1000-sample pixel chains, and therefore the one that can scale).  Reported beside the headline, never instead of it.
     mode1 = None
-    if shard:
+    if shard and args.full:
         step_desc[0] = d.make_desc(W, H, spp, depth, shard_rank=rank, shard_count=shard, stack_entries=args.stack_entries, rng_mode=1)
         # (rng_mode 1 makes the library allocate its integer-sum buffer: agree that every rank got it before the first gather of this leg)
         if all_ranks_can(lambda: ctx.render(step_desc[0], part.data_ptr(), stream=stream, want_stats=True), "first render in rng_mode 1"):
@@ -748,7 +782,7 @@ def main():
     # step in the reference's stream; the same with a Philox stream per sample; K frames per launch), each against ITS OWN one-GPU time, measured
     # in this run: rank 0 renders the whole frame alone while the other ranks wait at the barrier.  Only measured figures go in here.
     scaling_detail = None
-    if shard:
+    if shard and args.full:
         one_gpu = {}
         if rank == 0:
             whole = torch.zeros(W * H * 3, dtype=torch.uint8, device=dev)
@@ -787,22 +821,23 @@ def main():
     tiles_total, tiles_culled = (last_stats[0].tiles_total, last_stats[0].tiles_culled) if last_stats else (0, 0)
 
     # ---- work counters of exactly this launch shape (untimed counting build), for Mrays/s and the algorithmic bytes ----
-    cdesc = d.make_desc(W, H, spp, depth, shard_rank=desc.shard_rank, shard_count=desc.shard_count, collect_counters=1,
-                        stack_entries=args.stack_entries)
-    st = ctx.render(cdesc, part.data_ptr(), stream=stream, want_stats=True)
-    pixels_mine = lay["tiles_this_shard"] * 64 if shard else W * H
-    my_bytes = algorithmic_bytes(st, pixels_mine)
-    tot = torch.tensor([float(st.rays), float(st.primary_hits), float(st.samples), float(my_bytes)], dtype=torch.float64, device=dev)
-    if world > 1:
-        all_reduce(tot)
-    rays, primary_hits, samples_counted, _ = [float(v) for v in tot.tolist()]
-    lane_slots = {"node_loop_active": st.internal_entered / max(1, st.node_slots), "leaf_loop_active": st.tri_tests / max(1, st.tri_slots),
-                  "advance_active": st.adv_active / max(1, st.adv_slots), "node_loop_parked_at_leaf": st.idle_at_leaf / max(1, st.node_slots),
-                  "node_loop_waiting_for_advance": st.idle_waiting / max(1, st.node_slots), "node_loop_out_of_work": st.idle_done / max(1, st.node_slots)}
+    if args.full:
+        cdesc = d.make_desc(W, H, spp, depth, shard_rank=desc.shard_rank, shard_count=desc.shard_count, collect_counters=1,
+                            stack_entries=args.stack_entries)
+        st = ctx.render(cdesc, part.data_ptr(), stream=stream, want_stats=True)
+        pixels_mine = lay["tiles_this_shard"] * 64 if shard else W * H
+        my_bytes = algorithmic_bytes(st, pixels_mine)
+        tot = torch.tensor([float(st.rays), float(st.primary_hits), float(st.samples), float(my_bytes)], dtype=torch.float64, device=dev)
+        if world > 1:
+            all_reduce(tot)
+        rays, primary_hits, samples_counted, _ = [float(v) for v in tot.tolist()]
+        lane_slots = {"node_loop_active": st.internal_entered / max(1, st.node_slots), "leaf_loop_active": st.tri_tests / max(1, st.tri_slots),
+                      "advance_active": st.adv_active / max(1, st.adv_slots), "node_loop_parked_at_leaf": st.idle_at_leaf / max(1, st.node_slots),
+                      "node_loop_waiting_for_advance": st.idle_waiting / max(1, st.node_slots), "node_loop_out_of_work": st.idle_done / max(1, st.node_slots)}
 
     # ---- extras (single GPU only).  Reported, never the headline. ----
     extras = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         def measure(frame_idx, rng_mode):
             frx, camx, _ = frame_scene(frame_idx)
             ctx.set_camera_sun(camx, tuple(frx.sun_dir_model))
@@ -962,7 +997,7 @@ def main():
 
     # ---- roofline: calibration kernels live, PMC counters of this workload from child passes ----
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         secs = my_kernel_ms * 1e-3
         roof = {"bound": "valu_issue", "achieved": None, "peak": None, "unit": "G wave-instructions/s", "frac": None, "traffic": None,
                 "kernel": "dsrt_render_kernel", "kernel_ms": my_kernel_ms,
@@ -1044,22 +1079,18 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "mrays_per_s": rays * args.steps / dt / 1e6,
             "config": {
                 "workload": f"{mesh_name}: {n_tris} triangles, pose frame {args.frame} of rendezvous_1s_dt0_01s.txt (camera {fr.sep_m:.1f} m), "
                             f"{W}x{H} @ {spp} spp, max_depth {depth}, seed 1337, rng_mode 0 (reference LCG stream)",
                 "mesh_triangles": n_tris, "frame": args.frame, "width": W, "height": H, "spp": spp, "max_depth": depth,
-                "coverage": primary_hits / max(1.0, samples_counted), "rays_per_sample": rays / max(1.0, samples_counted),
                 "tiles_total_rank0": int(tiles_total), "tiles_culled_rank0": int(tiles_culled),
                 "parallelism": f"screen tiles 8x8 interleaved over {n_gpus} GPU(s)" + (", one RCCL gather + de-interleave per step" if shard else ""),
-                "bvh": args.bvh, "bvh_stack_need": hs.stack_need, "lds_stack_entries": st.lds_stack_entries,
+                "bvh": args.bvh, "bvh_stack_need": hs.stack_need,
                 "tree": ("certified second tree: rays walk a binned-SAH tree over the reachable triangles; the kernel certifies every answer against the reference's median-split tree "
                          "(no exact tie, inside the reference-leaf box's slab interval, no zero direction component) and re-walks the reference tree otherwise. The image is the "
-                         "reference's, byte for byte: reference_kernel_fixture below compares THIS run's image with the reference kernel's own") if certified else
+                         "reference's, byte for byte" + (": reference_kernel_fixture below compares THIS run's image with the reference kernel's own" if args.full else "")) if certified else
                         "reference tree only (every ray walks the reference's median-split tree)",
                 "certified_tree_used_rank0": int(last_stats[0].certified_tree_used) if last_stats else None,
-                "certificate_fallbacks_in_the_counting_launch": int(st.certificate_fallbacks), "nodes_entered_per_ray": st.nodes_entered / max(1, st.rays),
-                "tri_tests_per_ray": st.tri_tests / max(1, st.rays),
                 "math_mode": 0,
                 "math_mode_note": "the headline runs in math_mode 0: cosf / sinf / powf from include/dsrt_detmath.h, the one image every machine (the CPU oracle included) reproduces; it "
                                   "equals the reference's kernel built with those three functions (reference_kernel_fixture below). The mode that equals the reference's kernel built "
@@ -1069,9 +1100,14 @@ def main():
                                        "(DESIGN.md section 5 has the per-rank times for 1/2/4/8 ranks and the rng_mode 1 column that does scale)",
             },
             "setup": setup,
-            "lane_slots": lane_slots,
-            "roofline": roof,
         }
+        if args.full:                                               # the counting launch and the roofline
+            out["mrays_per_s"] = rays * args.steps / dt / 1e6
+            out["config"].update({"coverage": primary_hits / max(1.0, samples_counted), "rays_per_sample": rays / max(1.0, samples_counted),
+                                  "lds_stack_entries": st.lds_stack_entries, "certificate_fallbacks_in_the_counting_launch": int(st.certificate_fallbacks),
+                                  "nodes_entered_per_ray": st.nodes_entered / max(1, st.rays), "tri_tests_per_ray": st.tri_tests / max(1, st.rays)})
+            out["lane_slots"] = lane_slots
+            out["roofline"] = roof
         if extras:
             out["extras"] = extras
         if mode1:
@@ -1082,7 +1118,7 @@ def main():
             out["scaling_detail"] = scaling_detail
         if rehearsal_report:
             out["rehearsal"] = rehearsal_report
-        if n_gpus == 1 and not args.no_cpu:
+        if args.full and n_gpus == 1 and not args.no_cpu:
             out["cpu_baseline"], out["parity_rows"] = cpu_baseline(d, scene, W, H, spp, args.cpu_budget, gpu_rgb8=headline_image)
             out["reference_kernel_fixture"] = headline_fixture
             if not args.no_extras:

@@ -515,7 +515,7 @@ def test_bench_two_rank_flow_rehearsed_on_one_gpu(tmp_path):
     # `python bench.py --gpus 2` from a plain interpreter -- the way the driver calls it for N = 1 -- must start the two-rank job itself
     # (one process per rank through torch.distributed.run) and hand back its exit code and its JSON line, never run one GPU silently
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--tris", "20000", "--width", "322", "--height", "190",
-           "--spp", "16", "--no-cpu"]
+           "--spp", "16", "--no-cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -538,13 +538,45 @@ def test_bench_line_ties_the_headline_frame_to_the_oracle(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--tris", "20000", "--width", "322", "--height", "190", "--spp", "16",
-           "--no-extras", "--no-pmc", "--cpu-budget", "2"]
+           "--full", "--no-extras", "--no-pmc", "--cpu-budget", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     pr = out["parity_rows"]
     assert pr["rows"] >= 8 and pr["pixels"] == pr["rows"] * 322 and pr["mismatched"] == 0 and pr["lit_pixels"] > 100, pr
     assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_the_last_image(tmp_path, dsrt):
+    """`python bench.py` without --full: the line of the timed steps and nothing else, and --dump-outputs writes the image of the last timed step
+    (float32 rgb8 values) -- the image a render of the same frame gives."""
+    import json
+    import subprocess
+    import sys
+    from dsrt_amd import meshgen
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    W, H, spp, steps = 322, 190, 16, 2
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", "1", "--tris", "20000", "--width", str(W), "--height", str(H),
+           "--spp", str(spp), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["unit"] == "Msamples/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == steps
+    assert out["value"] > 0 and abs(out["value"] - W * H * spp / out["ms_per_step"] / 1e3) < 1e-6 * out["value"]
+    assert not {"roofline", "extras", "cpu_baseline", "parity_rows", "lane_slots", "mrays_per_s"} & set(out), sorted(out)
+    img = np.load(tmp_path / "out" / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (H, W, 3)
+    # the same frame rendered here: bench's mesh, pose and tree
+    obj = f"/tmp/dsrt_bench_station_v{meshgen.VERSION}_20000.obj"
+    hs = dsrt.HostScene().add_obj(obj)
+    hs.build_bvh()
+    fr = dsrt.pose_to_frame(dsrt.read_pose_file(os.path.join(GOLDEN, "rendezvous_1s_dt0_01s.txt"))[98])
+    ctx = dsrt.Context(0).set_certified_tree(True)
+    ctx.upload(hs.view(dsrt.frame_camera(fr, 40.0, W, H, spp, 50), tuple(fr.sun_dir_model)))
+    want, _, _ = ctx.render_to_host(dsrt.make_desc(W, H, spp, 50))
+    ctx.close()
+    assert (want.max(axis=2) > 0).sum() > 100
+    assert np.array_equal(img, want.astype(np.float32))
 
 
 def test_headline_mesh_rows_match_the_oracle(dsrt, gpu_ctx, oracle):

@@ -19,7 +19,7 @@ def test_python_tools_and_entry_points_parse():
 def test_bench_command_line_builds():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--sequence", "--batch", "--split", "--deal", "--single-process"):
+    for flag in ("--gpus", "--steps", "--warmup", "--sequence", "--batch", "--split", "--deal", "--single-process", "--full", "--dump-outputs"):
         assert flag in out.stdout, flag
 
 
