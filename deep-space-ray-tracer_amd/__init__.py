@@ -17,7 +17,7 @@ except ImportError:  # pragma: no cover
     _torch = None
 
 from . import capi
-from .capi import (DsrtFrame, DsrtPose, DsrtRenderDesc, DsrtStats, GPUCamera, GPUScene)
+from .capi import (DsrtFrame, DsrtGBuffer, DsrtPose, DsrtRenderDesc, DsrtStats, GPUCamera, GPUScene)
 
 lib = capi.load()
 
@@ -184,6 +184,13 @@ def write_png(path, rgb, width, height):
     _check(lib.dsrt_write_png(str(path).encode(), rgb.ctypes.data, int(width), int(height)), "dsrt_write_png")
 
 
+def write_pfm(path, data):
+    """Portable float map of an (H, W) or (H, W, 3) float array in image order (top row first); dsrt_write_pfm stores it bottom-up."""
+    a = np.ascontiguousarray(data, dtype=np.float32)
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    _check(lib.dsrt_write_pfm(str(path).encode(), a.ctypes.data, int(a.shape[1]), int(a.shape[0]), int(ch)), "dsrt_write_pfm")
+
+
 def make_desc(width, height, spp, max_depth=50, gamma=2.0, seed=1337, tile_size=0, shard_rank=0, shard_count=0,
               collect_counters=0, checked=0, stack_entries=0, tune=(0, 0, 0, 0), rng_mode=0, math_mode=0):
     d = DsrtRenderDesc()
@@ -331,6 +338,29 @@ class Context:
         _check(rc, "dsrt_render_to_host")
         shape = (desc.height, desc.width, 3)
         return rgb.reshape(shape), (f32.reshape(shape) if want_f32 else None), st
+
+    def render_gbuffer(self, desc, ptrs, stream=None, want_stats=False):
+        """dsrt_render_gbuffer: the G-buffer of the current camera into DEVICE buffers.  `ptrs` maps channel names (capi.GBUFFER_CHANNELS) to device
+        pointers, e.g. torch tensors' data_ptr(); channels not named are not written.  Asynchronous on `stream` unless want_stats."""
+        unknown = set(ptrs) - set(capi.GBUFFER_CHANNELS)
+        if unknown:
+            raise ValueError(f"unknown G-buffer channel(s) {sorted(unknown)}; known: {list(capi.GBUFFER_CHANNELS)}")
+        gb = DsrtGBuffer(**{k: C.c_void_p(int(v)) for k, v in ptrs.items() if v})
+        st = DsrtStats() if want_stats else None
+        _check(lib.dsrt_render_gbuffer(self._h, C.byref(desc), C.byref(gb), C.c_void_p(stream) if stream else None, C.byref(st) if st is not None else None),
+               "dsrt_render_gbuffer")
+        return st
+
+    def gbuffer_to_host(self, desc, channels=None):
+        """dsrt_render_gbuffer_to_host: {channel: numpy array of shape (H, W) or (H, W, C)} for `channels` (default: all of capi.GBUFFER_CHANNELS)."""
+        names = list(capi.GBUFFER_CHANNELS) if channels is None else list(channels)
+        out = {}
+        for n in names:
+            dt, comps = capi.GBUFFER_CHANNELS[n]
+            out[n] = np.zeros((desc.height, desc.width) + ((comps,) if comps > 1 else ()), dt)
+        gb = DsrtGBuffer(**{n: C.c_void_p(a.ctypes.data) for n, a in out.items()})
+        _check(lib.dsrt_render_gbuffer_to_host(self._h, C.byref(desc), C.byref(gb), None), "dsrt_render_gbuffer_to_host")
+        return out
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

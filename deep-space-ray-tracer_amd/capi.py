@@ -92,6 +92,16 @@ class DsrtStats(C.Structure):
                [(n, C.c_float) for n in ("heavy_queue_empty_ms", "light_queue_empty_ms", "last_wave_exit_ms")] + [("certified_tree_used", C.c_int)]
 
 
+class DsrtGBuffer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("t", "range", "depth", "position", "normal", "uv", "albedo", "prim_id", "material_id", "sun_cos", "flags")]
+
+
+# The G-buffer channels (include/dsrt.h, dsrt_render_gbuffer): name -> (numpy dtype, components per pixel), in DsrtGBuffer's order.
+GBUFFER_CHANNELS = {"t": ("<f4", 1), "range": ("<f4", 1), "depth": ("<f4", 1), "position": ("<f4", 3), "normal": ("<f4", 3), "uv": ("<f4", 2),
+                    "albedo": ("<f4", 3), "prim_id": ("<i4", 1), "material_id": ("<i4", 1), "sun_cos": ("<f4", 1), "flags": ("u1", 1)}
+GB_HIT, GB_FRONT_FACE, GB_SPHERE, GB_SUN_VISIBLE = 1, 2, 4, 8          # DSRT_GB_* of include/dsrt.h
+
+
 # numpy record layouts of the reference arrays (for dumping / comparing with goldens)
 F3 = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
 TRI_DTYPE = np.dtype([("v", "<f4", (3, 3)), ("n", "<f4", (3, 3)), ("uv", "<f4", (3, 3)), ("material_id", "<i4"), ("albedo_tex", "<i4")])
@@ -103,16 +113,16 @@ assert TRI_DTYPE.itemsize == 116 and NODE_DTYPE.itemsize == 40 and MAT_DTYPE.ite
 
 # The ABI version THESE hand-written structs were laid out for (include/dsrt.h, DSRT_ABI_VERSION).  load() requires library == header == this, and compares the sizes
 # of the structs above with the library's own (dsrt_sizeof): a header and library bumped without this file are refused, not mis-laid.
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 EXPORTS = [
     "dsrt_last_error", "dsrt_abi_version", "dsrt_sizeof", "dsrt_microbench_copy", "dsrt_dev_set_experiment", "dsrt_selftest_poke_node_word", "dsrt_ctx_set_certified_tree", "dsrt_ctx_has_certified_tree", "dsrt_dropin_has_certified_tree", "dsrt_host_scene_second_tree_probe",
     "dsrt_host_scene_create", "dsrt_host_scene_destroy", "dsrt_host_scene_add_obj", "dsrt_host_scene_add_world_file",
     "dsrt_host_scene_add_arrays", "dsrt_host_scene_add_texture_file", "dsrt_host_scene_build_bvh", "dsrt_host_scene_build_bvh_sah", "dsrt_host_scene_build_bvh_gpu", "dsrt_host_scene_view", "dsrt_host_scene_bvh_stack_need", "dsrt_host_scene_texture_failures",
-    "dsrt_scene_set_frame", "dsrt_read_pose_file", "dsrt_pose_to_frame", "dsrt_camera_look_at", "dsrt_decode_image_file", "dsrt_write_ppm", "dsrt_write_png",
+    "dsrt_scene_set_frame", "dsrt_read_pose_file", "dsrt_pose_to_frame", "dsrt_camera_look_at", "dsrt_decode_image_file", "dsrt_write_ppm", "dsrt_write_png", "dsrt_write_pfm",
     "dsrt_device_count", "dsrt_ctx_create", "dsrt_ctx_destroy", "dsrt_ctx_clone", "dsrt_ctx_device",
     "dsrt_multi_create", "dsrt_multi_destroy", "dsrt_multi_count", "dsrt_multi_uses_rccl", "dsrt_selftest_rccl_gather", "dsrt_multi_scene_upload", "dsrt_multi_render_frame", "dsrt_multi_render_sequence", "dsrt_scene_upload", "dsrt_scene_upload_device",
-    "dsrt_scene_set_camera_sun", "dsrt_shard_layout", "dsrt_ctx_scene_bounds", "dsrt_render", "dsrt_render_batch", "dsrt_render_batch_to_host", "dsrt_deinterleave_tiles", "dsrt_deinterleave_batch", "dsrt_render_to_host",
+    "dsrt_scene_set_camera_sun", "dsrt_shard_layout", "dsrt_ctx_scene_bounds", "dsrt_render", "dsrt_render_batch", "dsrt_render_batch_to_host", "dsrt_deinterleave_tiles", "dsrt_deinterleave_batch", "dsrt_render_to_host", "dsrt_render_gbuffer", "dsrt_render_gbuffer_to_host",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -169,6 +179,7 @@ def load():
     sig("dsrt_decode_image_file", C.c_int, [C.c_char_p, C.c_int, P(C.c_int), P(C.c_int), vp, C.c_size_t])
     sig("dsrt_write_ppm", C.c_int, [C.c_char_p, vp, C.c_int, C.c_int])
     sig("dsrt_write_png", C.c_int, [C.c_char_p, vp, C.c_int, C.c_int])
+    sig("dsrt_write_pfm", C.c_int, [C.c_char_p, vp, C.c_int, C.c_int, C.c_int])
     sig("dsrt_device_count", C.c_int, [])
     sig("dsrt_ctx_create", C.c_int, [C.c_int, P(vp)])
     sig("dsrt_ctx_destroy", None, [vp])
@@ -197,6 +208,8 @@ def load():
     sig("dsrt_deinterleave_tiles", C.c_int, [vp, P(DsrtRenderDesc), vp, vp, vp])
     sig("dsrt_deinterleave_batch", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, vp, vp, vp])
     sig("dsrt_render_to_host", C.c_int, [vp, P(DsrtRenderDesc), vp, vp, P(DsrtStats)])
+    sig("dsrt_render_gbuffer", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtGBuffer), vp, P(DsrtStats)])
+    sig("dsrt_render_gbuffer_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtGBuffer), P(DsrtStats)])
     sig("dsrt_selftest_math", C.c_int, [vp, C.c_int, vp, C.c_float, vp, C.c_int])
     sig("dsrt_selftest_devkat", C.c_int, [vp, C.c_int, vp, vp, C.c_int])
     sig("dsrt_selftest_philox", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp])
@@ -211,7 +224,7 @@ def load():
     if not (have == want == ABI_VERSION):
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
-    for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame)):      # DSRT_SIZEOF_* of include/dsrt.h, in order
+    for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer)):      # DSRT_SIZEOF_* of include/dsrt.h, in order
         if lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

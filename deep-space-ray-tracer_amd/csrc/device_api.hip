@@ -40,6 +40,7 @@ hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_
                              uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch = nullptr, uint32_t frames = 1, uint32_t stride = 0);
 hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream);
 hipError_t launch_content_hash(const uint32_t* words, size_t n_words, uint64_t salt, uint64_t* d_hash2, hipStream_t stream);
+hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream);          // gbuffer_kernel.hip
 // DsrtRenderDesc.math_mode 1: the same kernels compiled against the device math library's sinf / cosf / powf (render_kernel.hip, second compilation)
 namespace devlibm {
 hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream);
@@ -353,6 +354,7 @@ struct DsrtContext {
     DevBuf<BatchFrame> batch_table;  // dsrt_render_batch: one entry per frame
     std::vector<BatchFrame> batch_host;
     DevBuf<unsigned long long> accum_fixed;
+    DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t done = nullptr;      // recorded behind every render: the next render on ANY stream waits for it (queue words, spill strip,
     bool done_valid = false;        // pre-pass arrays and partial sums are per context, so a context has one render in flight)
@@ -943,6 +945,89 @@ int dsrt_render_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* h
     if (rc) return rc;
     HIP_TRY(hipMemcpy(h_rgb8, d8.p, px * 3, hipMemcpyDeviceToHost));
     if (h_f32) HIP_TRY(hipMemcpy(h_f32, d32.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return DSRT_OK;
+    });
+}
+
+// The G-buffer pass (gbuffer_kernel.hip): the context's camera and sun, the reference tree, one launch.  It reads the resident scene and writes the
+// caller's buffers and one status word of its own; the context's working buffers, camera and sun are not touched.
+int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, void* stream_v, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_gbuffer", [&]() -> int {
+    if (!ctx || !desc || !gb) { set_error("dsrt_render_gbuffer: null argument"); return DSRT_ERR_INVALID; }
+    if (desc->width < 2 || desc->height < 2) { set_error("dsrt_render_gbuffer: width and height must be at least 2 (the camera divides by W-1 and H-1)"); return DSRT_ERR_INVALID; }
+    if (desc->shard_count > 1) { set_error("dsrt_render_gbuffer renders whole images only (shard_count <= 1)"); return DSRT_ERR_INVALID; }
+    if ((unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) { set_error("dsrt_render_gbuffer: image too large (2^31 pixels)"); return DSRT_ERR_INVALID; }
+    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render_gbuffer: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const PackedScene& sc = *ctx->scene;
+    GBufferArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.scene = sc.view;
+    const GPUCamera& c = ctx->camera;
+    const float cam12[12] = {c.origin.x, c.origin.y, c.origin.z, c.lower_left_corner.x, c.lower_left_corner.y, c.lower_left_corner.z,
+                             c.horizontal.x, c.horizontal.y, c.horizontal.z, c.vertical.x, c.vertical.y, c.vertical.z};
+    static_assert(sizeof cam12 == sizeof a.cam, "camera block");
+    std::memcpy(a.cam, cam12, sizeof cam12);
+    a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
+    a.sun_dir[0] = ctx->sun_dir.x; a.sun_dir[1] = ctx->sun_dir.y; a.sun_dir[2] = ctx->sun_dir.z;
+    a.sun_enabled = ctx->sun_enabled;
+    a.width = desc->width; a.height = desc->height;
+    a.tiles_x = (desc->width + 7) / 8;
+    const int tiles = a.tiles_x * ((desc->height + 7) / 8);
+    a.stack_entries = std::max(1, std::min(64, sc.view.stack_need));       // upload refuses trees that need more than 64
+    a.t = gb->t; a.range = gb->range; a.depth = gb->depth; a.position = gb->position; a.normal = gb->normal; a.uv = gb->uv; a.albedo = gb->albedo;
+    a.prim_id = gb->prim_id; a.material_id = gb->material_id; a.sun_cos = gb->sun_cos; a.flags = gb->flags;
+    if (ctx->gb_status.n < 1) { int rc = ctx->gb_status.alloc(1); if (rc) return rc; }
+    a.status = ctx->gb_status.p;
+    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // one launch at a time per context, as for a render
+    HIP_TRY(hipMemsetAsync(ctx->gb_status.p, 0, sizeof(uint32_t), stream));
+    if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    HIP_TRY(launch_gbuffer(a, tiles, stream));
+    HIP_TRY(hipEventRecord(ctx->done, stream));
+    ctx->done_valid = true;
+    if (stats) {
+        HIP_TRY(hipEventRecord(ctx->ev1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        std::memset(stats, 0, sizeof *stats);
+        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, ctx->ev0, ctx->ev1));
+        HIP_TRY(hipMemcpy(&stats->device_flags, ctx->gb_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        stats->waves_launched = tiles;
+        if (stats->device_flags) {
+            char buf[96];
+            std::snprintf(buf, sizeof buf, "G-buffer kernel raised status flags 0x%x", stats->device_flags);
+            set_error(buf);
+            return DSRT_ERR_DEVICE_FLAG;
+        }
+    }
+    return DSRT_OK;
+    });
+}
+
+int dsrt_render_gbuffer_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_gbuffer_to_host", [&]() -> int {
+    if (!ctx || !desc || !gb) { set_error("dsrt_render_gbuffer_to_host: null argument"); return DSRT_ERR_INVALID; }
+    if (desc->width < 2 || desc->height < 2 || desc->shard_count > 1 || (unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) {
+        set_error("dsrt_render_gbuffer_to_host: bad size or shard"); return DSRT_ERR_INVALID;
+    }
+    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render_gbuffer_to_host: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * desc->height;
+    // one device buffer per channel asked for: {host pointer, bytes per pixel}, in DsrtGBuffer's order
+    void* const host[11] = {gb->t, gb->range, gb->depth, gb->position, gb->normal, gb->uv, gb->albedo, gb->prim_id, gb->material_id, gb->sun_cos, gb->flags};
+    const size_t bpp[11] = {4, 4, 4, 12, 12, 8, 12, 4, 4, 4, 1};
+    DevBuf<uint8_t> dev[11];
+    void* d[11] = {nullptr};
+    for (int i = 0; i < 11; ++i)
+        if (host[i]) { int rc = dev[i].alloc(px * bpp[i]); if (rc) return rc; d[i] = dev[i].p; }
+    DsrtGBuffer dg;
+    dg.t = (float*)d[0]; dg.range = (float*)d[1]; dg.depth = (float*)d[2]; dg.position = (float*)d[3]; dg.normal = (float*)d[4]; dg.uv = (float*)d[5];
+    dg.albedo = (float*)d[6]; dg.prim_id = (int32_t*)d[7]; dg.material_id = (int32_t*)d[8]; dg.sun_cos = (float*)d[9]; dg.flags = (uint8_t*)d[10];
+    DsrtStats local;
+    int rc = dsrt_render_gbuffer(ctx, desc, &dg, nullptr, stats ? stats : &local);
+    if (rc) return rc;
+    for (int i = 0; i < 11; ++i)
+        if (host[i]) HIP_TRY(hipMemcpy(host[i], d[i], px * bpp[i], hipMemcpyDeviceToHost));
     return DSRT_OK;
     });
 }

@@ -153,6 +153,20 @@ struct RenderArgs {
     int       audit;           // counting build: 1 = every answer of the second tree is also walked on the reference tree and compared (path_machine.h, CERTIFICATE AUDIT)
 };
 
+// The argument block of the G-buffer pass (gbuffer_kernel.hip, include/dsrt.h: dsrt_render_gbuffer).
+struct GBufferArgs {
+    DeviceScene scene;
+    float cam[12];             // as FrameParams::cam
+    float neg_w[3];            // -camera.w: the optical axis, for `depth`
+    float sun_dir[3];
+    int   sun_enabled;
+    int   width, height, tiles_x;
+    int   stack_entries;       // LDS stack entries per lane the launch provides (>= the tree's stack_need)
+    float* t; float* range; float* depth; float* position; float* normal; float* uv; float* albedo;   // the channels of DsrtGBuffer, NULL = not written
+    int* prim_id; int* material_id; float* sun_cos; uint8_t* flags;
+    uint32_t* status;          // kFlag* bits below: a reference, slot or material out of range (never raised by a library-built scene)
+};
+
 // order matches the DsrtStats tail in include/dsrt.h
 enum Counter { C_SAMPLES, C_RAYS, C_PRIMARY_HITS, C_BOX_FETCHES, C_NODES_ENTERED, C_INTERNAL_ENTERED, C_TRI_TESTS, C_HIT_UPDATES,
                C_SPHERE_TESTS, C_SHADED_HITS, C_TEX_FETCHES, C_STACK_SPILLS, C_MAX_STACK,

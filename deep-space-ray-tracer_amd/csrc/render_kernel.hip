@@ -30,6 +30,7 @@
 #include <rocrand/rocrand_kernel.h>
 
 #include "path_machine.h"
+#include "walk_common.h"
 
 namespace dsrt {
 #ifdef DSRT_DEVICE_LIBM
@@ -44,29 +45,7 @@ constexpr int kWavesPerBlock = 4;
 #define DSRT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 #endif
 
-// Moller-Trumbore :336-353 on one pair record (two triangles, packed fp32), evaluated in full; the reference's early returns become one
-// predicate per triangle.  Each `if (x) return false` is kept as `!(x)` so that NaNs fall the same way.  The test against `closest`
-// (:353) is NOT part of this: it is applied, in order, by apply_pair.
-__device__ __forceinline__ void moller_trumbore_pair(const float4* __restrict__ tp, F3 ro, F3 rd, v2f& t, v2f& u, v2f& v, bool& ok_a, bool& ok_b) {
-    const float4 f0 = tp[0], f1 = tp[1], f2 = tp[2], f3 = tp[3];
-    const float2 f4 = *reinterpret_cast<const float2*>(tp + 4);
-    const v2f v0x = {f0.x, f0.y}, v0y = {f0.z, f0.w}, v0z = {f1.x, f1.y};
-    const v2f e1x = {f1.z, f1.w}, e1y = {f2.x, f2.y}, e1z = {f2.z, f2.w};
-    const v2f e2x = {f3.x, f3.y}, e2y = {f3.z, f3.w}, e2z = {f4.x, f4.y};
-    const v2f pvx = rd.y * e2z - rd.z * e2y, pvy = rd.z * e2x - rd.x * e2z, pvz = rd.x * e2y - rd.y * e2x;   // cross(rd, e2)
-    const v2f det = (e1x * pvx + e1y * pvy) + e1z * pvz;
-    const v2f inv_det = {1.0f / det.x, 1.0f / det.y};
-    const v2f tvx = ro.x - v0x, tvy = ro.y - v0y, tvz = ro.z - v0z;
-    u = ((tvx * pvx + tvy * pvy) + tvz * pvz) * inv_det;
-    const v2f qvx = tvy * e1z - tvz * e1y, qvy = tvz * e1x - tvx * e1z, qvz = tvx * e1y - tvy * e1x;          // cross(tvec, e1)
-    v = ((rd.x * qvx + rd.y * qvy) + rd.z * qvz) * inv_det;
-    t = ((e2x * qvx + e2y * qvy) + e2z * qvz) * inv_det;
-    const v2f uv = u + v;
-    ok_a = !(fabsf(det.x) < 1e-8f) && !(u.x < 0.0f) && !(u.x > 1.0f) && !(v.x < 0.0f) && !(uv.x > 1.0f) && !(t.x < kTMin);
-    ok_b = !(fabsf(det.y) < 1e-8f) && !(u.y < 0.0f) && !(u.y > 1.0f) && !(v.y < 0.0f) && !(uv.y > 1.0f) && !(t.y < kTMin);
-}
-
-// The accepts of one pair record in the reference's order (:353, :371-379): A, then B against the `closest` A may have just lowered.
+// The accepts of one pair record (moller_trumbore_pair, walk_common.h, evaluates both triangles in full) in the reference's order (:353, :371-379): A, then B against the `closest` A may have just lowered.
 // `slot_a` = slot of triangle A.  Returns true when the walk is over (an any-hit shadow ray found its blocker).
 template <bool COUNT, bool ANYHIT>
 __device__ __forceinline__ bool apply_pair(Lane& ln, uint32_t* c, int slot_a, v2f t, v2f u, v2f v, bool ok_a, bool ok_b, bool has_b) {

@@ -1,4 +1,4 @@
-// image_io.cpp -- texture decode (PNM, PNG here; JPEG in jpeg_decode.cpp; BMP and TGA in bmp_tga_decode.cpp) to 8-bit RGB, and the P6 / PNG writers.
+// image_io.cpp -- texture decode (PNM, PNG here; JPEG in jpeg_decode.cpp; BMP and TGA in bmp_tga_decode.cpp) to 8-bit RGB, and the P6 / PNG / PFM writers.
 //
 // The reference decodes textures with its vendored stb_image forced to 3 channels
 // (src/gpu_scene_builder.cpp:215) and writes frames as binary PPM (src/gpu_render.cu:1099-1107).
@@ -244,6 +244,31 @@ extern "C" int dsrt_write_ppm(const char* path, const uint8_t* rgb, int width, i
     std::fclose(f);
     if (done != n) { dsrt::set_error(std::string("short write to ") + path); return DSRT_ERR_IO; }
     return DSRT_OK;
+}
+
+// PFM writer (the G-buffer's float channels): "Pf" for one channel, "PF" for three, scale -1 = little-endian, rows bottom-up as the format
+// stores them (the input is in image order, top row first).  The bytes are formed explicitly, so the file does not depend on the host's byte order.
+extern "C" int dsrt_write_pfm(const char* path, const float* data, int width, int height, int channels) {
+    return dsrt::guarded("dsrt_write_pfm", [&]() -> int {
+    if (!path || !data || width <= 0 || height <= 0 || (channels != 1 && channels != 3)) { dsrt::set_error("dsrt_write_pfm: bad argument"); return DSRT_ERR_INVALID; }
+    const size_t row = (size_t)width * (size_t)channels;
+    std::vector<uint8_t> bytes(row * 4);
+    FILE* f = std::fopen(path, "wb");
+    if (!f) { dsrt::set_error(std::string("cannot open ") + path + " for writing"); return DSRT_ERR_IO; }
+    bool ok = std::fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", width, height) > 0;
+    for (int y = height - 1; y >= 0 && ok; --y) {
+        const float* src = data + (size_t)y * row;
+        for (size_t i = 0; i < row; ++i) {
+            uint32_t w;
+            std::memcpy(&w, src + i, 4);
+            bytes[4 * i + 0] = (uint8_t)w; bytes[4 * i + 1] = (uint8_t)(w >> 8); bytes[4 * i + 2] = (uint8_t)(w >> 16); bytes[4 * i + 3] = (uint8_t)(w >> 24);
+        }
+        ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    }
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok) { dsrt::set_error(std::string("short write to ") + path); return DSRT_ERR_IO; }
+    return DSRT_OK;
+    });
 }
 
 // PNG writer (8-bit RGB, filter 0, one zlib stream): the reference shells out to ImageMagick to turn its PPM into a PNG

@@ -151,6 +151,7 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_GPU_CAMERA: return sizeof(GPUCamera);
         case DSRT_SIZEOF_POSE: return sizeof(DsrtPose);
         case DSRT_SIZEOF_FRAME: return sizeof(DsrtFrame);
+        case DSRT_SIZEOF_GBUFFER: return sizeof(DsrtGBuffer);
         default: return 0;
     }
 }

@@ -8,7 +8,9 @@
 //   * the scene is flattened, BVH-built and uploaded ONCE; only camera and sun change per frame (the reference
 //     rebuilds and re-uploads everything per frame, :405);
 //   * the output directory is created if missing but never emptied (the reference deletes its contents, :41-50);
-//   * PPM only: there is no ImageMagick shell-out (:28-36) and no upscaling step (:438-447).
+//   * PPM (or PNG with --png): there is no ImageMagick shell-out (:28-36) and no upscaling step (:438-447);
+//   * --gbuffer also writes each frame's ground truth next to it (include/dsrt.h, dsrt_render_gbuffer): <frame>_range.pfm, <frame>_normal.pfm,
+//     <frame>_mask.pgm (255 where the centre ray hits) and <frame>_sunlit.pgm (255 where that hit sees the Sun).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +20,16 @@
 
 #include "../../include/dsrt.h"
 
+// 8-bit P5 of `bit` of every flags byte: 255 where set
+static bool write_mask_pgm(const std::string& path, const std::vector<uint8_t>& flags, int width, int height, uint8_t bit) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::vector<uint8_t> px(flags.size());
+    for (size_t i = 0; i < flags.size(); ++i) px[i] = (flags[i] & bit) ? 255 : 0;
+    bool ok = std::fprintf(f, "P5\n%d %d\n255\n", width, height) > 0 && std::fwrite(px.data(), 1, px.size(), f) == px.size();
+    return std::fclose(f) == 0 && ok;
+}
+
 static int fail(const char* what) {
     std::fprintf(stderr, "dsrt_render: %s: %s\n", what, dsrt_last_error());
     return 1;
@@ -26,7 +38,7 @@ static int fail(const char* what) {
 int main(int argc, char** argv) {
     std::string pose_file, out_dir = "output", obj;
     int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0;
-    bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false;
+    bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -48,9 +60,10 @@ int main(int argc, char** argv) {
         else if (a == "--reference-math") math_mode = 1;          // sinf / cosf / powf from the device math library: the reference's own kernel's bytes on this GPU (include/dsrt.h)
         else if (a == "--certified-tree") certified = true;        // rays walk the certified second tree: the reference's bytes, a third fewer node visits (include/dsrt.h)
         else if (a == "--strict-textures") strict_textures = true;  // refuse a mesh whose texture maps this library cannot decode (include/dsrt.h)
+        else if (a == "--gbuffer") gbuffer = true;                  // ground-truth channels of every frame next to its image (include/dsrt.h, dsrt_render_gbuffer)
         else if (a == "--png") png = true;                          // frames as PNG instead of PPM (the reference converts with ImageMagick)
         else if (a == "--upscale") std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--strict-textures]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     mkdir(out_dir.c_str(), 0777);
@@ -138,6 +151,27 @@ int main(int argc, char** argv) {
             const uint8_t* img = fb.data() + q * image_bytes;
             if ((png ? dsrt_write_png(path.c_str(), img, width, height) : dsrt_write_ppm(path.c_str(), img, width, height)) != DSRT_OK) return fail("writing the frame");
             std::printf("Saved %s\n", path.c_str());
+            if (gbuffer) {
+                // the frame's ground truth: the context's camera and sun are set to this frame's (the batch launch above took them as arguments)
+                const size_t px = (size_t)width * height;
+                std::vector<float> range(px), normal(px * 3);
+                std::vector<uint8_t> flags(px);
+                DsrtGBuffer g;
+                std::memset(&g, 0, sizeof g);
+                g.range = range.data(); g.normal = normal.data(); g.flags = flags.data();
+                if (dsrt_scene_set_camera_sun(ctx, &cams[k + q], suns.data() + 3 * (k + q)) != DSRT_OK || dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK)
+                    return fail("rendering the G-buffer");
+                char stem[64];
+                std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[k + q]);
+                const std::string base = out_dir + stem;
+                if (dsrt_write_pfm((base + "_range.pfm").c_str(), range.data(), width, height, 1) != DSRT_OK ||
+                    dsrt_write_pfm((base + "_normal.pfm").c_str(), normal.data(), width, height, 3) != DSRT_OK) return fail("writing the G-buffer");
+                if (!write_mask_pgm(base + "_mask.pgm", flags, width, height, DSRT_GB_HIT) || !write_mask_pgm(base + "_sunlit.pgm", flags, width, height, DSRT_GB_SUN_VISIBLE)) {
+                    std::fprintf(stderr, "dsrt_render: cannot write the masks of %s\n", base.c_str());
+                    return 1;
+                }
+                std::printf("Saved %s_{range,normal}.pfm, %s_{mask,sunlit}.pgm\n", base.c_str(), base.c_str());
+            }
         }
     }
     dsrt_ctx_destroy(ctx);

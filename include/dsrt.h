@@ -35,9 +35,9 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
-#define DSRT_ABI_VERSION 7
+#define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
 /* sizeof of the structs that cross this ABI, as the LIBRARY was compiled: a binding that mirrors them by hand (ctypes, cgo, JNA ...) compares its own sizes with
  * these at load time, so that a struct that grew in the header and the library but not in the binding is refused instead of silently mis-laid.  0 = unknown. */
@@ -47,6 +47,7 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_GPU_CAMERA  3
 #define DSRT_SIZEOF_POSE        4
 #define DSRT_SIZEOF_FRAME       5
+#define DSRT_SIZEOF_GBUFFER     6
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -152,6 +153,9 @@ int dsrt_decode_image_file(const char* path, int flip_vertically, int* width, in
 int dsrt_write_ppm(const char* path, const uint8_t* rgb, int width, int height);
 /* 8-bit RGB PNG: what the reference obtains by shelling out to ImageMagick on the PPM (src/main.cpp:28-36). */
 int dsrt_write_png(const char* path, const uint8_t* rgb, int width, int height);
+/* Portable float map: `channels` 1 ("Pf") or 3 ("PF") floats per pixel, `data` in image order (top row first, as every buffer of this
+ * library); the file holds the rows bottom-up, as the format wants, little-endian (scale -1).  For the G-buffer channels (dsrt_render_gbuffer). */
+int dsrt_write_pfm(const char* path, const float* data, int width, int height, int channels);
 
 /* ===================================================================================== */
 /* Device side.                                                                          */
@@ -333,6 +337,58 @@ int dsrt_render_batch(DsrtContext* ctx, const DsrtRenderDesc* desc, int frames, 
  * like the reference's main.cpp. */
 int dsrt_render_batch_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int frames, const GPUCamera* cameras, const float* sun_dirs_xyz,
                               uint8_t* h_rgb8, DsrtStats* stats);
+
+/*
+ * GROUND-TRUTH G-BUFFER.  One primary ray per pixel through the pixel CENTRE -- the reference's camera ray (make_camera_ray_jittered, src/gpu_render.cu:941-968)
+ * with jx = jy = 0.5 -- for the context's current camera and sun (dsrt_scene_set_camera_sun), and per pixel what its first hit is.  The hit is the reference's
+ * own primary query, scene_hit(ray, 0.001f, 1e9f) (:744), on the REFERENCE tree even when the certified second tree is resident: bit for bit the triangle,
+ * t, u, v the oracle's scene_hit returns (ties resolve by the reference's visit order).  Pixels in the rgb8 output's order: top row first, so buffer row r
+ * is camera row H-1-r.  Every channel is optional (NULL = not written); each is a DEVICE buffer of width*height elements of the type and count below.
+ *
+ *   channel      type x comps  on a hit                                                                        on a miss
+ *   t            f32 x 1       ray parameter of the hit                                                        +inf
+ *   range        f32 x 1       t * sqrtf(dot(d, d)), f32 ops in that order: Euclidean distance, model units    +inf
+ *   depth        f32 x 1       t * dot(d, -camera.w): distance along the optical axis                          +inf
+ *   position     f32 x 3       p = o + t d as ray_at forms it (model frame)                                     0
+ *   normal       f32 x 3       the hit record's normal: interpolated, normalised, face-forwarded (set_face_normal) 0
+ *   uv           f32 x 2       barycentric u, v of the hit (0, 0 for spheres)                                  0
+ *   albedo       f32 x 3       material albedo x tex2D texel at the interpolated uv, as ray_color forms it (:763-774) 0
+ *   prim_id      i32           original triangle index (into GPUScene.triangles); sphere s -> -2 - s           -1
+ *   material_id  i32           the hit record's material id                                                     -1
+ *   sun_cos      f32 x 1       fmaxf(0, dot(normal, normalize(-sun_dir))); 0 when the sun is disabled          0
+ *   flags        u8            DSRT_GB_* below                                                                  0
+ *
+ * DSRT_GB_SUN_VISIBLE: sun_cos > 0 and the reference's shadow ray (origin p + normal * 1e-3f, direction normalize(-sun_dir), scene_hit(..., 0.001f, 1e9f); :800-810)
+ * is not blocked -- set for every hit whatever its material: a geometric shadow mask.  The shadow rays are traced only when `flags` is asked for.
+ * No sinf / cosf / powf are involved: DsrtRenderDesc.math_mode does not matter.
+ */
+typedef struct DsrtGBuffer {
+    float*   t;
+    float*   range;
+    float*   depth;
+    float*   position;
+    float*   normal;
+    float*   uv;
+    float*   albedo;
+    int32_t* prim_id;
+    int32_t* material_id;
+    float*   sun_cos;
+    uint8_t* flags;
+} DsrtGBuffer;
+
+#define DSRT_GB_HIT          1    /* the primary ray hit something                  */
+#define DSRT_GB_FRONT_FACE   2    /* ... on the side its (outward) normal faces      */
+#define DSRT_GB_SPHERE       4    /* ... and that something is a sphere              */
+#define DSRT_GB_SUN_VISIBLE  8    /* the hit point sees the Sun (see above)          */
+
+/* The G-buffer of the current camera into the DEVICE buffers of `gb`.  Uses desc->width / height only (the sampling fields are ignored).
+ * DSRT_ERR_INVALID: width or height < 2 (the camera divides by W-1 and H-1), shard_count > 1, a NULL desc or gb; DSRT_ERR_NO_SCENE before an upload.
+ * Asynchronous on `stream` unless `stats` is given; then the call synchronises and fills kernel_ms, waves_launched and device_flags (the rest is 0).
+ * The context's camera, sun, scene and working buffers are left as they were: a render after this call gives the same bytes as one before it.
+ * Like a render, the call waits for the context's previous render, and the next render waits for it. */
+int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, void* stream, DsrtStats* stats);
+/* The same into HOST buffers (each channel of `gb` a host pointer or NULL), synchronously. */
+int dsrt_render_gbuffer_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, DsrtStats* stats);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
