@@ -17,7 +17,7 @@ except ImportError:  # pragma: no cover
     _torch = None
 
 from . import capi
-from .capi import (DsrtFrame, DsrtGBuffer, DsrtPose, DsrtRenderDesc, DsrtStats, GPUCamera, GPUScene)
+from .capi import (DsrtFrame, DsrtGBuffer, DsrtPose, DsrtRayHits, DsrtRays, DsrtRenderDesc, DsrtStats, GPUCamera, GPUScene)
 
 lib = capi.load()
 
@@ -151,6 +151,19 @@ def pose_to_frame(pose):
     f = DsrtFrame()
     _check(lib.dsrt_pose_to_frame(C.byref(pose), C.byref(f)), "dsrt_pose_to_frame")
     return f
+
+
+def pose_to_model(pose, xyz, direction=False):
+    """World-frame points (or, with direction=True, directions) of a pose's epoch into the model frame the scene lives in (dsrt_pose_points_to_model /
+    dsrt_pose_dirs_to_model): `xyz` of shape (3,) or (N, 3), computed in float64 as the pose file holds it; returns float32 of the same shape."""
+    a = np.ascontiguousarray(xyz, dtype=np.float64)
+    if a.ndim not in (1, 2) or a.shape[-1] != 3:
+        raise ValueError(f"pose_to_model: xyz must have shape (3,) or (N, 3), not {a.shape}")
+    flat = a.reshape(-1, 3)
+    out = np.empty(flat.shape, np.float32)
+    fn = lib.dsrt_pose_dirs_to_model if direction else lib.dsrt_pose_points_to_model
+    _check(fn(C.byref(pose), int(flat.shape[0]), flat.ctypes.data, out.ctypes.data), fn.__name__)
+    return out.reshape(a.shape)
 
 
 def camera_look_at(lookfrom, lookat, vfov, width, height, spp, max_depth):
@@ -361,6 +374,86 @@ class Context:
         gb = DsrtGBuffer(**{n: C.c_void_p(a.ctypes.data) for n, a in out.items()})
         _check(lib.dsrt_render_gbuffer_to_host(self._h, C.byref(desc), C.byref(gb), None), "dsrt_render_gbuffer_to_host")
         return out
+
+    def trace_rays(self, origins, dirs, t_min=None, t_max=None, any_hit=False, channels=None, stream=None, want_stats=False):
+        """Ray queries on the resident scene (include/dsrt.h, dsrt_trace_rays): {channel: array} for `channels` (capi.RAY_HIT_CHANNELS; default all of
+        them, or `flags` alone with any_hit=True), of shape (N,) or (N, comps).  origins / dirs are float32 (N, 3), t_min / t_max float32 (N,) or None, all
+        contiguous and all of one kind:
+          * torch tensors on this context's device: the device path; outputs are tensors on that device, ordered on `stream` (a torch.cuda.Stream or a raw
+            hipStream_t; default: torch's current stream), which first waits for torch's current stream;
+          * numpy arrays: dsrt_trace_rays_to_host, numpy outputs.
+        With want_stats, returns (outputs, DsrtStats) and the call synchronises."""
+        names = (["flags"] if any_hit else list(capi.RAY_HIT_CHANNELS)) if channels is None else list(channels)
+        unknown = set(names) - set(capi.RAY_HIT_CHANNELS)
+        if unknown:
+            raise ValueError(f"unknown ray-hit channel(s) {sorted(unknown)}; known: {list(capi.RAY_HIT_CHANNELS)}")
+        inputs = {"origins": origins, "dirs": dirs, "t_min": t_min, "t_max": t_max}
+        is_torch = _torch is not None and isinstance(origins, _torch.Tensor)
+        n = None
+        for key, x in inputs.items():
+            if x is None:
+                if key in ("origins", "dirs"):
+                    raise ValueError(f"trace_rays: {key} is required")
+                continue
+            want_shape = "(N, 3)" if key in ("origins", "dirs") else "(N,)"
+            if is_torch:
+                if not isinstance(x, _torch.Tensor):
+                    raise TypeError(f"trace_rays: {key} must be a torch tensor like origins, not {type(x).__name__}")
+                if x.dtype != _torch.float32:
+                    raise TypeError(f"trace_rays: {key} must be float32, not {x.dtype}")
+                if x.device.type != "cuda" or x.device.index != self.device:
+                    raise ValueError(f"trace_rays: {key} is on {x.device}, the context is on cuda:{self.device}")
+                if not x.is_contiguous():
+                    raise ValueError(f"trace_rays: {key} must be contiguous")
+            else:
+                if not isinstance(x, np.ndarray):
+                    raise TypeError(f"trace_rays: {key} must be a numpy array or a torch tensor, not {type(x).__name__}")
+                if x.dtype != np.float32:
+                    raise TypeError(f"trace_rays: {key} must be float32, not {x.dtype}")
+                if not x.flags["C_CONTIGUOUS"]:
+                    raise ValueError(f"trace_rays: {key} must be C-contiguous")
+            shape = tuple(x.shape)
+            if (key in ("origins", "dirs") and (len(shape) != 2 or shape[1] != 3)) or (key in ("t_min", "t_max") and len(shape) != 1):
+                raise ValueError(f"trace_rays: {key} must have shape {want_shape}, not {shape}")
+            if n is None:
+                n = shape[0]
+            elif shape[0] != n:
+                raise ValueError(f"trace_rays: {key} holds {shape[0]} rays, origins {n}")
+        mode = capi.TRACE_ANY if any_hit else capi.TRACE_CLOSEST
+        st = DsrtStats() if want_stats else None
+        if is_torch:
+            torch_dt = {"<f4": _torch.float32, "<i4": _torch.int32, "u1": _torch.uint8}
+            out = {}
+            for k in names:
+                dt, comps = capi.RAY_HIT_CHANNELS[k]
+                out[k] = _torch.empty((n, comps) if comps > 1 else (n,), dtype=torch_dt[dt], device=origins.device)
+            cur = _torch.cuda.current_stream(origins.device)
+            ts = stream if isinstance(stream, _torch.cuda.Stream) else None
+            raw = ts.cuda_stream if ts is not None else (int(stream) if stream else cur.cuda_stream)
+            if raw != cur.cuda_stream:
+                if ts is not None:
+                    ts.wait_stream(cur)                                     # inputs written and outputs allocated on the current stream come first
+                    for x in list(inputs.values()) + list(out.values()):
+                        if x is not None:
+                            x.record_stream(ts)
+                else:
+                    cur.synchronize()
+            if n:
+                rays = DsrtRays(**{k: C.c_void_p(x.data_ptr()) for k, x in inputs.items() if x is not None})
+                hits = DsrtRayHits(**{k: C.c_void_p(x.data_ptr()) for k, x in out.items()})
+                _check(lib.dsrt_trace_rays(self._h, int(n), C.byref(rays), mode, C.byref(hits), C.c_void_p(raw),
+                                           C.byref(st) if st is not None else None), "dsrt_trace_rays")
+        else:
+            out = {}
+            for k in names:
+                dt, comps = capi.RAY_HIT_CHANNELS[k]
+                out[k] = np.empty((n, comps) if comps > 1 else (n,), dt)
+            if n:
+                rays = DsrtRays(**{k: C.c_void_p(x.ctypes.data) for k, x in inputs.items() if x is not None})
+                hits = DsrtRayHits(**{k: C.c_void_p(x.ctypes.data) for k, x in out.items()})
+                _check(lib.dsrt_trace_rays_to_host(self._h, int(n), C.byref(rays), mode, C.byref(hits), C.byref(st) if st is not None else None),
+                       "dsrt_trace_rays_to_host")
+        return (out, st) if want_stats else out
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

@@ -102,6 +102,19 @@ GBUFFER_CHANNELS = {"t": ("<f4", 1), "range": ("<f4", 1), "depth": ("<f4", 1), "
 GB_HIT, GB_FRONT_FACE, GB_SPHERE, GB_SUN_VISIBLE = 1, 2, 4, 8          # DSRT_GB_* of include/dsrt.h
 
 
+class DsrtRays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("origins", "dirs", "t_min", "t_max")]
+
+
+class DsrtRayHits(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("t", "range", "position", "normal", "uv", "albedo", "prim_id", "material_id", "flags")]
+
+
+# The ray-query channels (include/dsrt.h, dsrt_trace_rays): name -> (numpy dtype, components per ray), in DsrtRayHits' order.
+RAY_HIT_CHANNELS = {n: GBUFFER_CHANNELS[n] for n, _ in DsrtRayHits._fields_}
+TRACE_CLOSEST, TRACE_ANY = 0, 1                                         # DSRT_TRACE_* of include/dsrt.h
+
+
 # numpy record layouts of the reference arrays (for dumping / comparing with goldens)
 F3 = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
 TRI_DTYPE = np.dtype([("v", "<f4", (3, 3)), ("n", "<f4", (3, 3)), ("uv", "<f4", (3, 3)), ("material_id", "<i4"), ("albedo_tex", "<i4")])
@@ -119,10 +132,11 @@ EXPORTS = [
     "dsrt_last_error", "dsrt_abi_version", "dsrt_sizeof", "dsrt_microbench_copy", "dsrt_dev_set_experiment", "dsrt_selftest_poke_node_word", "dsrt_ctx_set_certified_tree", "dsrt_ctx_has_certified_tree", "dsrt_dropin_has_certified_tree", "dsrt_host_scene_second_tree_probe",
     "dsrt_host_scene_create", "dsrt_host_scene_destroy", "dsrt_host_scene_add_obj", "dsrt_host_scene_add_world_file",
     "dsrt_host_scene_add_arrays", "dsrt_host_scene_add_texture_file", "dsrt_host_scene_build_bvh", "dsrt_host_scene_build_bvh_sah", "dsrt_host_scene_build_bvh_gpu", "dsrt_host_scene_view", "dsrt_host_scene_bvh_stack_need", "dsrt_host_scene_texture_failures",
-    "dsrt_scene_set_frame", "dsrt_read_pose_file", "dsrt_pose_to_frame", "dsrt_camera_look_at", "dsrt_decode_image_file", "dsrt_write_ppm", "dsrt_write_png", "dsrt_write_pfm",
+    "dsrt_scene_set_frame", "dsrt_read_pose_file", "dsrt_pose_to_frame", "dsrt_pose_points_to_model", "dsrt_pose_dirs_to_model", "dsrt_camera_look_at", "dsrt_decode_image_file", "dsrt_write_ppm", "dsrt_write_png", "dsrt_write_pfm",
     "dsrt_device_count", "dsrt_ctx_create", "dsrt_ctx_destroy", "dsrt_ctx_clone", "dsrt_ctx_device",
     "dsrt_multi_create", "dsrt_multi_destroy", "dsrt_multi_count", "dsrt_multi_uses_rccl", "dsrt_selftest_rccl_gather", "dsrt_multi_scene_upload", "dsrt_multi_render_frame", "dsrt_multi_render_sequence", "dsrt_scene_upload", "dsrt_scene_upload_device",
     "dsrt_scene_set_camera_sun", "dsrt_shard_layout", "dsrt_ctx_scene_bounds", "dsrt_render", "dsrt_render_batch", "dsrt_render_batch_to_host", "dsrt_deinterleave_tiles", "dsrt_deinterleave_batch", "dsrt_render_to_host", "dsrt_render_gbuffer", "dsrt_render_gbuffer_to_host",
+    "dsrt_trace_rays", "dsrt_trace_rays_to_host",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -175,6 +189,8 @@ def load():
     sig("dsrt_scene_set_frame", None, [P(GPUScene), P(GPUCamera), P(C.c_float)])
     sig("dsrt_read_pose_file", C.c_int, [C.c_char_p, P(DsrtPose), C.c_int, P(C.c_int)])
     sig("dsrt_pose_to_frame", C.c_int, [P(DsrtPose), P(DsrtFrame)])
+    sig("dsrt_pose_points_to_model", C.c_int, [P(DsrtPose), C.c_int, vp, vp])
+    sig("dsrt_pose_dirs_to_model", C.c_int, [P(DsrtPose), C.c_int, vp, vp])
     sig("dsrt_camera_look_at", C.c_int, [P(GPUCamera), P(C.c_float), P(C.c_float), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int])
     sig("dsrt_decode_image_file", C.c_int, [C.c_char_p, C.c_int, P(C.c_int), P(C.c_int), vp, C.c_size_t])
     sig("dsrt_write_ppm", C.c_int, [C.c_char_p, vp, C.c_int, C.c_int])
@@ -210,6 +226,8 @@ def load():
     sig("dsrt_render_to_host", C.c_int, [vp, P(DsrtRenderDesc), vp, vp, P(DsrtStats)])
     sig("dsrt_render_gbuffer", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtGBuffer), vp, P(DsrtStats)])
     sig("dsrt_render_gbuffer_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtGBuffer), P(DsrtStats)])
+    sig("dsrt_trace_rays", C.c_int, [vp, C.c_int, P(DsrtRays), C.c_int, P(DsrtRayHits), vp, P(DsrtStats)])
+    sig("dsrt_trace_rays_to_host", C.c_int, [vp, C.c_int, P(DsrtRays), C.c_int, P(DsrtRayHits), P(DsrtStats)])
     sig("dsrt_selftest_math", C.c_int, [vp, C.c_int, vp, C.c_float, vp, C.c_int])
     sig("dsrt_selftest_devkat", C.c_int, [vp, C.c_int, vp, vp, C.c_int])
     sig("dsrt_selftest_philox", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp])
@@ -224,7 +242,8 @@ def load():
     if not (have == want == ABI_VERSION):
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
-    for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer)):      # DSRT_SIZEOF_* of include/dsrt.h, in order
+    for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
+                                          DsrtRayHits)):      # DSRT_SIZEOF_* of include/dsrt.h, in order
         if lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

@@ -41,6 +41,7 @@ hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_
 hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream);
 hipError_t launch_content_hash(const uint32_t* words, size_t n_words, uint64_t salt, uint64_t* d_hash2, hipStream_t stream);
 hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream);          // gbuffer_kernel.hip
+hipError_t launch_raycast(const RaycastArgs& a, bool any_hit, int blocks, hipStream_t stream);                  // raycast_kernel.hip
 // DsrtRenderDesc.math_mode 1: the same kernels compiled against the device math library's sinf / cosf / powf (render_kernel.hip, second compilation)
 namespace devlibm {
 hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream);
@@ -355,6 +356,7 @@ struct DsrtContext {
     std::vector<BatchFrame> batch_host;
     DevBuf<unsigned long long> accum_fixed;
     DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
+    DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t done = nullptr;      // recorded behind every render: the next render on ANY stream waits for it (queue words, spill strip,
     bool done_valid = false;        // pre-pass arrays and partial sums are per context, so a context has one render in flight)
@@ -432,6 +434,37 @@ void experiment_from_environment() {            // once per process
 }
 
 uint32_t experiment_word() { return g_experiment.load(); }
+
+// Ray queries (raycast_kernel.hip).  Argument checks shared by the device and the host form: every range is known from `count`.
+struct Range { const void* p; size_t bytes; };
+
+bool ranges_overlap(const Range& a, const Range& b) {
+    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+int check_trace_args(const char* fn, const DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits) {
+    auto fail = [&](const char* why) { set_error(std::string(fn) + ": " + why); return DSRT_ERR_INVALID; };
+    if (!ctx || !rays || !hits) return fail("null argument");
+    if (!rays->origins || !rays->dirs) return fail("null origins or dirs");
+    if (count < 0) return fail("count < 0");
+    if (mode != DSRT_TRACE_CLOSEST && mode != DSRT_TRACE_ANY) return fail("unknown mode");
+    const size_t n = (size_t)count;
+    const Range in[4] = {{rays->origins, n * 12}, {rays->dirs, n * 12}, {rays->t_min, n * 4}, {rays->t_max, n * 4}};
+    const Range out[9] = {{hits->t, n * 4}, {hits->range, n * 4}, {hits->position, n * 12}, {hits->normal, n * 12}, {hits->uv, n * 8},
+                          {hits->albedo, n * 12}, {hits->prim_id, n * 4}, {hits->material_id, n * 4}, {hits->flags, n}};
+    bool any_out = false, non_flag_out = false;
+    for (int k = 0; k < 9; ++k) if (out[k].p) { any_out = true; if (k != 8) non_flag_out = true; }
+    if (!any_out) return fail("no output channel");
+    if (mode == DSRT_TRACE_ANY && non_flag_out) return fail("DSRT_TRACE_ANY writes `flags` only");
+    for (const Range& r : in) if ((uintptr_t)r.p & 3u) return fail("pointer not 4-byte aligned");
+    for (const Range& r : out) if ((uintptr_t)r.p & 3u) return fail("pointer not 4-byte aligned");
+    for (const Range& o : out)
+        for (const Range& i : in)
+            if (ranges_overlap(o, i)) return fail("an output range overlaps an input range");
+    return DSRT_OK;
+}
 
 }  // namespace
 
@@ -1028,6 +1061,84 @@ int dsrt_render_gbuffer_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, co
     if (rc) return rc;
     for (int i = 0; i < 11; ++i)
         if (host[i]) HIP_TRY(hipMemcpy(host[i], d[i], px * bpp[i], hipMemcpyDeviceToHost));
+    return DSRT_OK;
+    });
+}
+
+int dsrt_trace_rays(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, void* stream_v, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_trace_rays", [&]() -> int {
+    if (int rc = check_trace_args("dsrt_trace_rays", ctx, count, rays, mode, hits)) return rc;
+    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_trace_rays: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return DSRT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const PackedScene& sc = *ctx->scene;
+    const bool any_hit = mode == DSRT_TRACE_ANY;
+    RaycastArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.scene = sc.view;
+    a.origins = rays->origins; a.dirs = rays->dirs; a.t_min = rays->t_min; a.t_max = rays->t_max;
+    a.count = count;
+    a.stack_entries = std::max(1, std::min(64, sc.view.stack_need));       // upload refuses trees that need more than 64
+    a.t = hits->t; a.range = hits->range; a.position = hits->position; a.normal = hits->normal; a.uv = hits->uv; a.albedo = hits->albedo;
+    a.prim_id = hits->prim_id; a.material_id = hits->material_id; a.flags = hits->flags;
+    if (ctx->rc_status.n < 1) { int rc = ctx->rc_status.alloc(1); if (rc) return rc; }
+    a.status = ctx->rc_status.p;
+    const int blocks = (int)(((size_t)count + 63) / 64);                   // one lane per ray
+    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // one launch at a time per context, as for a render
+    HIP_TRY(hipMemsetAsync(ctx->rc_status.p, 0, sizeof(uint32_t), stream));
+    if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    HIP_TRY(launch_raycast(a, any_hit, blocks, stream));
+    HIP_TRY(hipEventRecord(ctx->done, stream));
+    ctx->done_valid = true;
+    if (stats) {
+        HIP_TRY(hipEventRecord(ctx->ev1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, ctx->ev0, ctx->ev1));
+        HIP_TRY(hipMemcpy(&stats->device_flags, ctx->rc_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        stats->waves_launched = blocks;
+        if (stats->device_flags) {
+            char buf[96];
+            std::snprintf(buf, sizeof buf, "ray query kernel raised status flags 0x%x", stats->device_flags);
+            set_error(buf);
+            return DSRT_ERR_DEVICE_FLAG;
+        }
+    }
+    return DSRT_OK;
+    });
+}
+
+int dsrt_trace_rays_to_host(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_trace_rays_to_host", [&]() -> int {
+    if (int rc = check_trace_args("dsrt_trace_rays_to_host", ctx, count, rays, mode, hits)) return rc;
+    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_trace_rays_to_host: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return DSRT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = (size_t)count;
+    // inputs {host pointer, bytes}, then the channels in DsrtRayHits' order
+    const void* const hin[4] = {rays->origins, rays->dirs, rays->t_min, rays->t_max};
+    const size_t bin[4] = {n * 12, n * 12, n * 4, n * 4};
+    void* const hout[9] = {hits->t, hits->range, hits->position, hits->normal, hits->uv, hits->albedo, hits->prim_id, hits->material_id, hits->flags};
+    const size_t bout[9] = {n * 4, n * 4, n * 12, n * 12, n * 8, n * 12, n * 4, n * 4, n};
+    DevBuf<uint8_t> din[4], dout[9];
+    void* di[4] = {nullptr};
+    void* dd[9] = {nullptr};
+    for (int i = 0; i < 4; ++i)
+        if (hin[i]) { int rc = din[i].alloc(bin[i]); if (rc) return rc; di[i] = din[i].p; HIP_TRY(hipMemcpy(di[i], hin[i], bin[i], hipMemcpyHostToDevice)); }
+    for (int i = 0; i < 9; ++i)
+        if (hout[i]) { int rc = dout[i].alloc(bout[i]); if (rc) return rc; dd[i] = dout[i].p; }
+    DsrtRays dr;
+    dr.origins = (const float*)di[0]; dr.dirs = (const float*)di[1]; dr.t_min = (const float*)di[2]; dr.t_max = (const float*)di[3];
+    DsrtRayHits dh;
+    dh.t = (float*)dd[0]; dh.range = (float*)dd[1]; dh.position = (float*)dd[2]; dh.normal = (float*)dd[3]; dh.uv = (float*)dd[4]; dh.albedo = (float*)dd[5];
+    dh.prim_id = (int32_t*)dd[6]; dh.material_id = (int32_t*)dd[7]; dh.flags = (uint8_t*)dd[8];
+    DsrtStats local;
+    int rc = dsrt_trace_rays(ctx, count, &dr, mode, &dh, nullptr, stats ? stats : &local);
+    if (rc) return rc;
+    for (int i = 0; i < 9; ++i)
+        if (hout[i]) HIP_TRY(hipMemcpy(hout[i], dd[i], bout[i], hipMemcpyDeviceToHost));
     return DSRT_OK;
     });
 }

@@ -167,6 +167,18 @@ struct GBufferArgs {
     uint32_t* status;          // kFlag* bits below: a reference, slot or material out of range (never raised by a library-built scene)
 };
 
+// The argument block of the ray queries (raycast_kernel.hip, include/dsrt.h: dsrt_trace_rays).
+struct RaycastArgs {
+    DeviceScene scene;
+    const float* origins; const float* dirs;    // count x 3 each
+    const float* t_min; const float* t_max;     // count each, NULL = 0.001f / 1e9f
+    int   count;
+    int   stack_entries;       // LDS stack entries per lane the launch provides (>= the tree's stack_need)
+    float* t; float* range; float* position; float* normal; float* uv; float* albedo;   // the channels of DsrtRayHits, NULL = not written
+    int* prim_id; int* material_id; uint8_t* flags;
+    uint32_t* status;          // kFlag* bits below, as for the G-buffer pass
+};
+
 // order matches the DsrtStats tail in include/dsrt.h
 enum Counter { C_SAMPLES, C_RAYS, C_PRIMARY_HITS, C_BOX_FETCHES, C_NODES_ENTERED, C_INTERNAL_ENTERED, C_TRI_TESTS, C_HIT_UPDATES,
                C_SPHERE_TESTS, C_SHADED_HITS, C_TEX_FETCHES, C_STACK_SPILLS, C_MAX_STACK,

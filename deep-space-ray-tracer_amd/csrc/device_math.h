@@ -202,20 +202,22 @@ __device__ __forceinline__ F3 scatter_dielectric(F3 rd, F3 hn, bool front, float
 //   slab plane with a zero direction component) loses both of the reference's comparisons and leaves the bound
 //   unchanged -- which is what fmaxf/fminf do with one NaN operand; the running bounds themselves are never NaN.
 //   +0/-0 differences cannot matter: the bounds are only ever compared.
-__device__ __forceinline__ bool slab(F3 lo, F3 hi, F3 o, F3 inv, float t_max, float& t_entry) {
+__device__ __forceinline__ bool slab(F3 lo, F3 hi, F3 o, F3 inv, float t_min, float t_max, float& t_entry) {
     float ax = (lo.x - o.x) * inv.x, bx = (hi.x - o.x) * inv.x;
     float ay = (lo.y - o.y) * inv.y, by = (hi.y - o.y) * inv.y;
     float az = (lo.z - o.z) * inv.z, bz = (hi.z - o.z) * inv.z;
     float t0x = inv.x < 0.0f ? bx : ax, t1x = inv.x < 0.0f ? ax : bx;
     float t0y = inv.y < 0.0f ? by : ay, t1y = inv.y < 0.0f ? ay : by;
     float t0z = inv.z < 0.0f ? bz : az, t1z = inv.z < 0.0f ? az : bz;
-    float tmin = fmaxf(fmaxf(kTMin, t0x), fmaxf(t0y, t0z));
+    float tmin = fmaxf(fmaxf(t_min, t0x), fmaxf(t0y, t0z));
     float tmax = fminf(fminf(t_max, t1x), fminf(t1y, t1z));
     t_entry = tmin;
     return !(tmax <= tmin);
 }
 
-__device__ __forceinline__ bool hit_sphere(const GPUSphere& sph, F3 o, F3 d, float t_max, float& t_out, F3& n_out) {   // :478-504
+__device__ __forceinline__ bool slab(F3 lo, F3 hi, F3 o, F3 inv, float t_max, float& t_entry) { return slab(lo, hi, o, inv, kTMin, t_max, t_entry); }
+
+__device__ __forceinline__ bool hit_sphere(const GPUSphere& sph, F3 o, F3 d, float t_min, float t_max, float& t_out, F3& n_out) {   // :478-504
     F3 center = mk(sph.center.x, sph.center.y, sph.center.z);
     F3 oc = o - center;
     float a = dot(d, d);
@@ -225,14 +227,18 @@ __device__ __forceinline__ bool hit_sphere(const GPUSphere& sph, F3 o, F3 d, flo
     if (disc < 0.0f) return false;
     float sq = sqrtf(disc);
     float root = (-half_b - sq) / a;
-    if (root < kTMin || root > t_max) {
+    if (root < t_min || root > t_max) {
         root = (-half_b + sq) / a;
-        if (root < kTMin || root > t_max) return false;
+        if (root < t_min || root > t_max) return false;
     }
     t_out = root;
     F3 p = mk(o.x + root * d.x, o.y + root * d.y, o.z + root * d.z);
     n_out = (p - center) * (1.0f / sph.radius);
     return true;
+}
+
+__device__ __forceinline__ bool hit_sphere(const GPUSphere& sph, F3 o, F3 d, float t_max, float& t_out, F3& n_out) {   // t_min = 0.001f (:744, :816)
+    return hit_sphere(sph, o, d, kTMin, t_max, t_out, n_out);
 }
 
 __device__ __forceinline__ F3 tex2d(const DeviceScene& s, int tex_id, float u, float v, uint32_t& n_fetch) {           // :232-259

@@ -6,7 +6,7 @@
 //   * The walk is the reference's, on the REFERENCE tree (DeviceScene.root_ref) even when the certified second tree is resident: near child first
 //     by the render kernel's ordering test, far child pushed, LIFO pop, a leaf's triangles in leaf order, every box tested against the shrinking
 //     `closest`.  Equal t is accepted (:353), so ties resolve as in the reference.  The per-record arithmetic is the render kernel's own
-//     (walk_common.h: visit_pair, moller_trumbore_pair); spheres follow the tree, in order, as in scene_hit :527-548.
+//     (walk_common.h: walk_reference_tree, visit_pair, moller_trumbore_pair); spheres follow the tree, in order, as in scene_hit :527-548.
 //   * The traversal stack lives in LDS, [entry][lane] like the render kernel's, sized per launch by the tree's depth (DeviceScene.stack_need,
 //     at most 64: dsrt_scene_upload refuses deeper trees): no runtime-indexed private array, hence no scratch.
 //   * Second phase of the same launch: the lanes whose hit faces the Sun trace the shadow ray as an any-hit walk.  It stops at the first accepted
@@ -17,64 +17,6 @@
 namespace dsrt {
 
 constexpr uint32_t kGbHit = 1u, kGbFront = 2u, kGbSphere = 4u, kGbSunVisible = 8u;      // DSRT_GB_* of include/dsrt.h
-
-// The walk of bvh_hit_closest :387-473 on the reference tree, one lane, its stack column `stk` (entry e at stk[e * 64]).  Closest-hit: on return
-// (closest, slot, u, v) are the accepted triangle of smallest t (slot -1: none).  ANYHIT: returns at the first accepted triangle.
-template <bool ANYHIT>
-__device__ __forceinline__ void walk_reference_tree(const DeviceScene& S, uint2* stk, int cap, F3 ro, F3 rd, F3 rinv, float& closest, int& slot, float& hu, float& hv,
-                                                    uint32_t& status) {
-    float t_entry;
-    int cur = (S.root_ref != kRefNone && slab(ld3(S.root_lo), ld3(S.root_hi), ro, rinv, closest, t_entry)) ? S.root_ref : kRefNone;     // :394-410
-    int sp = 0;
-    while (cur != kRefNone) {
-        if (cur == kRefPop) {
-            // a postponed child is entered iff its entry distance is still in front of `closest` (bbox_hit of a box known to be hit, :422-424)
-            if (sp == 0) { cur = kRefNone; break; }
-            --sp;
-            const uint2 e = stk[sp * 64];
-            if (closest > __uint_as_float(e.y)) cur = (int)e.x;
-        } else if (cur >= kRefBias) {
-            if (cur - kRefBias >= S.num_pairs) { status |= kFlagBadNodeRef; break; }
-            const float4* rec = reinterpret_cast<const float4*>(S.pairs_biased + ((uint32_t)cur << 6));
-            const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
-            const int ref_l = __float_as_int(q3.x), ref_r = __float_as_int(q3.y);
-            bool hl, hr, left_near;
-            float tl, tr;
-            visit_pair(q0, q1, q2, q3, ro, rd, rinv, closest, hl, hr, tl, tr, left_near);
-            if (hl && hr) {                                                  // far child postponed with its entry distance
-                if (sp >= cap) { status |= kFlagStackOverflow; break; }
-                stk[sp * 64] = make_uint2((uint32_t)(left_near ? ref_r : ref_l), __float_as_uint(left_near ? tr : tl));
-                ++sp;
-            }
-            const bool take_left = hl && !(hr && !left_near);
-            cur = (hl || hr) ? (take_left ? ref_l : ref_r) : kRefPop;
-        } else if (cur < 0) {
-            int first = leaf_payload(cur), count = leaf_code(cur) + 1;
-            if (count == 8) {
-                if (first >= S.num_big_leaves) { status |= kFlagBadBigLeaf; break; }
-                const int2 bl = S.big_leaves[first]; first = bl.x; count = bl.y;
-            }
-            if (first < 0 || count < 0 || first + ((count + 1) >> 1) > S.num_tri_pairs) { status |= kFlagBadTriSlot; break; }
-            for (int i = 0; i < count; i += 2) {                             // leaf order, A then B of each pair record (:413-420)
-                const int pair = first + (i >> 1);
-                v2f t, u, v;
-                bool ok_a, ok_b;
-                moller_trumbore_pair(S.tri_pairs + (size_t)pair * 5, ro, rd, t, u, v, ok_a, ok_b);
-                if (ok_a && !(t.x > closest)) {
-                    closest = t.x; slot = pair * 2; hu = u.x; hv = v.x;
-                    if (ANYHIT) return;
-                }
-                if (ok_b && !(t.y > closest)) {                              // an absent B is all zeros: det == 0, never ok
-                    closest = t.y; slot = pair * 2 + 1; hu = u.y; hv = v.y;
-                    if (ANYHIT) return;
-                }
-            }
-            cur = kRefPop;
-        } else {
-            status |= kFlagBadNodeRef; break;
-        }
-    }
-}
 
 __global__ void __launch_bounds__(64) dsrt_gbuffer_kernel(const GBufferArgs a) {
     extern __shared__ uint2 gb_stack[];                                      // [entry][lane]
@@ -94,7 +36,7 @@ __global__ void __launch_bounds__(64) dsrt_gbuffer_kernel(const GBufferArgs a) {
     const F3 rinv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);
     float closest = kTMax, hu = 0.0f, hv = 0.0f;
     int slot = -1;
-    if (live) walk_reference_tree<false>(S, stk, a.stack_entries, ro, rd, rinv, closest, slot, hu, hv, status);
+    if (live) walk_reference_tree<false>(S, stk, a.stack_entries, ro, rd, rinv, kTMin, closest, slot, hu, hv, status);
 
     // ---- finish scene_hit :516-551: the triangle's record from (slot, t, u, v), then the spheres ----
     bool hit = false, front = false, sphere = false;
@@ -149,7 +91,7 @@ __global__ void __launch_bounds__(64) dsrt_gbuffer_kernel(const GBufferArgs a) {
             const F3 sinv = mk(1.0f / ldir.x, 1.0f / ldir.y, 1.0f / ldir.z);
             float s_closest = kTMax, su = 0.0f, sv = 0.0f;
             int s_slot = -1;
-            walk_reference_tree<true>(S, stk, a.stack_entries, so, ldir, sinv, s_closest, s_slot, su, sv, status);
+            walk_reference_tree<true>(S, stk, a.stack_entries, so, ldir, sinv, kTMin, s_closest, s_slot, su, sv, status);
             bool blocked = s_slot >= 0;
             for (int i = 0; !blocked && i < S.num_spheres; ++i) {
                 float t_hit; F3 n_hit;

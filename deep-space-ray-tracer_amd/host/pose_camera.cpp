@@ -116,6 +116,32 @@ int dsrt_pose_to_frame(const DsrtPose* pose, DsrtFrame* out) {
     return DSRT_OK;
 }
 
+// World-frame pose-file coordinates into the model frame: the camera's transform of dsrt_pose_to_frame, operation for operation.
+int dsrt_pose_points_to_model(const DsrtPose* pose, int n, const double* world_xyz, float* model_xyz) {
+    if (!pose || n < 0 || (n > 0 && (!world_xyz || !model_xyz))) { dsrt::set_error("dsrt_pose_points_to_model: bad argument"); return DSRT_ERR_INVALID; }
+    const double yaw_deg = (double)pose->model_euler_deg[0];
+    for (int i = 0; i < n; ++i) {
+        const double* w = world_xyz + (size_t)i * 3;
+        const D3 rel{w[0] - pose->model_pos_world[0], w[1] - pose->model_pos_world[1], w[2] - pose->model_pos_world[2]};
+        const D3 m = yaw_about_y(rel, -yaw_deg);
+        float* o = model_xyz + (size_t)i * 3;
+        o[0] = (float)m.x; o[1] = (float)m.y; o[2] = (float)m.z;
+    }
+    return DSRT_OK;
+}
+
+int dsrt_pose_dirs_to_model(const DsrtPose* pose, int n, const double* world_xyz, float* model_xyz) {
+    if (!pose || n < 0 || (n > 0 && (!world_xyz || !model_xyz))) { dsrt::set_error("dsrt_pose_dirs_to_model: bad argument"); return DSRT_ERR_INVALID; }
+    const double yaw_deg = (double)pose->model_euler_deg[0];
+    for (int i = 0; i < n; ++i) {
+        const double* w = world_xyz + (size_t)i * 3;
+        const D3 m = yaw_about_y(D3{w[0], w[1], w[2]}, -yaw_deg);
+        float* o = model_xyz + (size_t)i * 3;
+        o[0] = (float)m.x; o[1] = (float)m.y; o[2] = (float)m.z;
+    }
+    return DSRT_OK;
+}
+
 int dsrt_camera_look_at(GPUCamera* out, const float from[3], const float at[3], float vfov_deg, int width, int height, int spp,
                         int max_depth) {
     if (!out || !from || !at || width < 2 || height < 2) { dsrt::set_error("dsrt_camera_look_at: bad argument"); return DSRT_ERR_INVALID; }

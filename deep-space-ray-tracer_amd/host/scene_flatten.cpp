@@ -152,6 +152,8 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_POSE: return sizeof(DsrtPose);
         case DSRT_SIZEOF_FRAME: return sizeof(DsrtFrame);
         case DSRT_SIZEOF_GBUFFER: return sizeof(DsrtGBuffer);
+        case DSRT_SIZEOF_RAYS: return sizeof(DsrtRays);
+        case DSRT_SIZEOF_RAY_HITS: return sizeof(DsrtRayHits);
         default: return 0;
     }
 }

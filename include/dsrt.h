@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -48,6 +48,8 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_POSE        4
 #define DSRT_SIZEOF_FRAME       5
 #define DSRT_SIZEOF_GBUFFER     6
+#define DSRT_SIZEOF_RAYS        7
+#define DSRT_SIZEOF_RAY_HITS    8
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -140,6 +142,12 @@ typedef struct DsrtFrame {
  * Returns DSRT_ERR_IO if the file cannot be opened or holds no valid pose (read_pose_file returns false). */
 int dsrt_read_pose_file(const char* path, DsrtPose* out, int cap, int* count);
 int dsrt_pose_to_frame(const DsrtPose* pose, DsrtFrame* out);
+/* World-frame points / directions of a pose's epoch (doubles, as the pose file has them) into the model frame that GPUScene lives in, for the ray queries
+ * (dsrt_trace_rays).  Points: yaw_about_y(p - model_pos_world, -yaw) in double, then narrowed to float -- exactly the operations dsrt_pose_to_frame applies to
+ * the camera, so dsrt_pose_points_to_model(cam_pos_world) == cam_in_model bit for bit.  Directions: yaw_about_y(d, -yaw), not normalised.
+ * `world_xyz` and `model_xyz` hold n x 3 values; DSRT_ERR_INVALID for a NULL pose, n < 0, or NULL arrays with n > 0. */
+int dsrt_pose_points_to_model(const DsrtPose* pose, int n, const double* world_xyz, float* model_xyz);
+int dsrt_pose_dirs_to_model(const DsrtPose* pose, int n, const double* world_xyz, float* model_xyz);
 /* point_camera_at + camera::initialize + toGPUCamera: vup (0,1,0), aperture 0, focus = |from - at|. */
 int dsrt_camera_look_at(GPUCamera* out, const float from[3], const float at[3], float vfov_deg, int width, int height,
                         int spp, int max_depth);
@@ -389,6 +397,54 @@ typedef struct DsrtGBuffer {
 int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, void* stream, DsrtStats* stats);
 /* The same into HOST buffers (each channel of `gb` a host pointer or NULL), synchronously. */
 int dsrt_render_gbuffer_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, DsrtStats* stats);
+
+/*
+ * RAY QUERIES.  Caller-supplied rays against the resident scene: for ray i, the reference's scene_hit(ray_i, t_min_i, t_max_i) (src/gpu_render.cu:509-551),
+ * bit for bit -- the triangle walk on the REFERENCE tree (also when the certified second tree is resident), then the spheres in order; equal t is accepted,
+ * so ties resolve by the reference's visit order.  t_min reaches every place the reference uses it (box entry, the triangle test, both sphere roots); t_max is
+ * the initial closest distance.  Rays are in the MODEL frame (dsrt_pose_points_to_model / dsrt_pose_dirs_to_model take pose-file coordinates there).
+ *
+ * One lane per ray, in the order given: the walk is fastest when neighbouring rays are coherent (similar origins and directions), and ordering them is the
+ * caller's business -- the library does not sort.
+ *
+ * Channels (DsrtRayHits, each optional, NULL = not written; `count` elements of the type and count of the G-buffer table above):
+ *   t, range (t * sqrtf(dot(d, d))), position, normal, uv, albedo, prim_id (triangle index, -2 - s for sphere s), material_id, flags,
+ *   on a miss +inf / +inf / 0 / 0 / 0 / 0 / -1 / -1 / 0.  flags: DSRT_GB_HIT, DSRT_GB_FRONT_FACE, DSRT_GB_SPHERE; DSRT_GB_SUN_VISIBLE is never set.
+ *
+ * Modes: DSRT_TRACE_CLOSEST, the closest hit and every channel asked for.  DSRT_TRACE_ANY, occlusion: `flags` only (any other channel is DSRT_ERR_INVALID),
+ * DSRT_GB_HIT iff scene_hit would report a hit; the walk stops at the first accepted triangle.
+ */
+typedef struct DsrtRays {            /* DEVICE pointers for dsrt_trace_rays, HOST pointers for the _to_host form */
+    const float* origins;            /* count x 3, model frame (the frame GPUScene lives in)             */
+    const float* dirs;               /* count x 3, need not be normalised (t is in units of |dir|)       */
+    const float* t_min;              /* count, or NULL = 0.001f                                          */
+    const float* t_max;              /* count, or NULL = 1e9f                                            */
+} DsrtRays;
+
+typedef struct DsrtRayHits {         /* every channel optional (NULL = not written); per-ray values as the G-buffer table defines them */
+    float*   t;
+    float*   range;
+    float*   position;
+    float*   normal;
+    float*   uv;
+    float*   albedo;
+    int32_t* prim_id;
+    int32_t* material_id;
+    uint8_t* flags;
+} DsrtRayHits;
+
+#define DSRT_TRACE_CLOSEST 0
+#define DSRT_TRACE_ANY     1
+
+/* Trace `count` rays from DEVICE buffers into DEVICE buffers.
+ * DSRT_ERR_INVALID: a NULL ctx, rays, hits, origins or dirs; count < 0; an unknown mode; no output channel; a channel other than flags with DSRT_TRACE_ANY;
+ * a pointer not 4-byte aligned; an output range that overlaps an input range.  DSRT_ERR_NO_SCENE before an upload.  count == 0: DSRT_OK, nothing launched.
+ * Asynchronous on `stream` unless `stats` is given; then the call synchronises and fills kernel_ms, waves_launched and device_flags (the rest is 0), and
+ * returns DSRT_ERR_DEVICE_FLAG when the kernel raised a status flag.  Like dsrt_render_gbuffer, the call waits for the context's previous launch, the next
+ * launch waits for it, and the context's camera, sun and working buffers are left untouched. */
+int dsrt_trace_rays(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, void* stream, DsrtStats* stats);
+/* The same from HOST buffers into HOST buffers, synchronously. */
+int dsrt_trace_rays_to_host(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, DsrtStats* stats);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
