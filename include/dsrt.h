@@ -235,7 +235,20 @@ typedef struct DsrtRenderDesc {
                                        1 = rocRAND Philox4x32-10, one sub-sequence per (pixel, sample): samples become
                                            independent work items (statistically equivalent image, not bit-identical to mode 0);
                                            a pixel's samples are summed as integers in units of 2^-20, so the image is a function
-                                           of (scene, camera, seed) alone -- not of sharding, scheduling or which lane drew what */
+                                           of (scene, camera, seed) alone -- not of sharding, scheduling or which lane drew what.
+                                       Mode 1, exactly (restated on the CPU by oracle/dsrt_oracle.c, dsrt_oracle_render_rect; tests/test_gpu_rng_mode1.py):
+                                         - key: `seed`, low 32-bit word first (key = {seed & 0xFFFFFFFF, seed >> 32});
+                                         - pixel (x, y), sample k (0 <= k < spp) draws from sub-sequence (x + y*W)*spp + k, a 64-bit number, with y = 0 the
+                                           BOTTOM row as in mode 0 (the kernel's y; the image stores that pixel in row H-1-y);
+                                         - draw n of a sample (n counted from 0 at the start of every sample) is word n & 3 of the Philox4x32-10 block with
+                                           counter {n >> 2, 0, sub & 0xFFFFFFFF, sub >> 32}: rocrand_init(seed, sub, 0) followed by n + 1 calls of rocrand();
+                                         - a draw maps to [0,1) as (word & 0xFFFFFF) / 2^24; the draws are consumed in mode 0's order (jitter x, jitter y,
+                                           then ray_color's);
+                                         - each sample's value: the sample's colour clamped to [0,1] (as mode 0), then (uint32_t)(c * 2^20 + 0.5f) in fp32;
+                                         - a pixel's sum over its spp samples is a 64-bit integer per channel;
+                                         - its mean is (float)((double)sum * (1.0 / 2^20 / spp)), computed in double and converted to float once;
+                                         - the tone map and the 8-bit store are mode 0's (clamp to [0,10], pow(1/gamma), clamp to [0,1], 255.99 * c);
+                                         - pixels of culled tiles are black (all-zero bytes and +0.0f), which is what they render to anyway */
     int      tile_size;             /* screen-tile edge in pixels, multiple of 8; 0 -> 8          */
     int      shard_rank;            /* this process renders tiles t with t % shard_count == shard_rank */
     int      shard_count;           /* 0 or 1 -> whole image                                      */

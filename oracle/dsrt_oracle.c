@@ -70,12 +70,55 @@ static inline void set_face_normal(Hit* h, const Ray* r, V3 outward) {
     h->normal = h->front_face ? outward : scale(outward, -1.0f);
 }
 
-typedef struct { uint32_t state; DsrtOracleCounters* c; } Rng;
+/* The random source of the sampling loop.  mode 0: the reference's LCG, one stream per pixel (`state`).  mode 1 (DsrtRenderDesc.rng_mode 1,
+ * written out in include/dsrt.h): Philox4x32-10 with key {key0, key1}, sub-sequence `sub`, draw `n` of the current sample. */
+typedef struct {
+    uint32_t state; DsrtOracleCounters* c; int mode; uint32_t key0, key1; uint64_t sub; uint64_t n;
+    uint64_t blk1; uint32_t w[4];                     /* mode 1: block (n >> 2) + 1 whose words are in w, 0 = none yet */
+} Rng;
 
-/* rand01 :77-80 */
+/* Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC11; the Random123 constants), one block of four
+ * words for a 128-bit counter {c[0], c[1], c[2], c[3]} (least significant word first) and a 64-bit key {k0, k1}. */
+static void philox4x32_10(uint32_t k0, uint32_t k1, const uint32_t c_in[4], uint32_t out[4]) {
+    uint32_t c0 = c_in[0], c1 = c_in[1], c2 = c_in[2], c3 = c_in[3];
+    for (int r = 0; r < 10; ++r) {
+        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+/* Word `i` of sub-sequence `sub` under key `seed`: word i & 3 of the block whose counter is {i >> 2 (64 bits), sub (64 bits)}. */
+static uint32_t philox_word(uint64_t seed, uint64_t sub, uint64_t i) {
+    const uint64_t blk = i >> 2;
+    const uint32_t ctr[4] = { (uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)sub, (uint32_t)(sub >> 32) };
+    uint32_t w[4];
+    philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), ctr, w);
+    return w[i & 3u];
+}
+
+void dsrt_oracle_philox_words(uint64_t seed, uint64_t sub, uint64_t first, int n, uint32_t* out) {
+    for (int i = 0; i < n; ++i) out[i] = philox_word(seed, sub, first + (uint64_t)i);
+}
+
+/* rand01 :77-80 (mode 0); the same mapping of a Philox word to [0,1) in mode 1 */
 static inline float rand01(Rng* g) {
-    g->state = g->state * 1664525u + 1013904223u;
     g->c->rng_draws++;
+    if (g->mode == 1) {
+        const uint64_t blk = g->n >> 2;
+        if (g->blk1 != blk + 1) {
+            const uint32_t ctr[4] = { (uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)g->sub, (uint32_t)(g->sub >> 32) };
+            philox4x32_10(g->key0, g->key1, ctr, g->w);
+            g->blk1 = blk + 1;
+        }
+        const uint32_t w = g->w[g->n++ & 3u];
+        return (float)(w & 0x00FFFFFFu) / 16777216.0f;
+    }
+    g->state = g->state * 1664525u + 1013904223u;
     return (float)(g->state & 0x00FFFFFFu) / 16777216.0f;
 }
 float dsrt_oracle_rand01(uint32_t* state) {
@@ -534,29 +577,51 @@ static Ray camera_ray(const GPUCamera* cam, int px, int py, int W, int H, float 
     return r;
 }
 
-/* render_kernel :973-1031 with the launcher's gamma default :1043-1045 */
-int dsrt_oracle_render_rows(const GPUScene* s, int W, int H, int y0, int y1, uint8_t* rgb8, float* rgb_f32,
+/* rng_mode 1: one sample's clamped colour in units of 2^-20, rounded to nearest (include/dsrt.h, DsrtRenderDesc.rng_mode) */
+uint32_t dsrt_oracle_mode1_quantize(float c) { return (uint32_t)(c * 1048576.0f + 0.5f); }
+/* rng_mode 1: a pixel's mean from its 64-bit sum, in double, converted to float once */
+float dsrt_oracle_mode1_mean(uint64_t sum, int spp) { return (float)((double)sum * (1.0 / 1048576.0 / (double)spp)); }
+
+/* render_kernel :973-1031 with the launcher's gamma default :1043-1045; rng_mode 1 as include/dsrt.h writes it out */
+int dsrt_oracle_render_rect(const GPUScene* s, int W, int H, int x0, int x1, int y0, int y1, int rng_mode, uint8_t* rgb8, float* rgb_f32,
                             DsrtOracleCounters* counters) {
     DsrtOracleCounters local;
     memset(&local, 0, sizeof local);
-    if (!s || W < 2 || H < 2 || y0 < 0 || y1 > H || y0 > y1) return -1;
+    if (!s || W < 2 || H < 2 || y0 < 0 || y1 > H || y0 > y1 || x0 < 0 || x1 > W || x0 > x1 || (rng_mode != 0 && rng_mode != 1)) return -1;
     const float gamma = (s->params.gamma > 0.0f) ? s->params.gamma : 1.0f;
     const float inv_gamma = 1.0f / gamma;
     int spp = s->params.samples_per_pixel;
     if (spp < 1) spp = 1;
 
     for (int y = y0; y < y1; ++y) {
-        for (int x = 0; x < W; ++x) {
-            Rng g = { (uint32_t)(x + y * W) ^ (uint32_t)(s->seed & 0xFFFFFFFFu), &local };
-            V3 accum = v3(0, 0, 0);
-            for (int k = 0; k < spp; ++k) {
-                float jx = ((float)k + rand01(&g)) / (float)spp;
-                float jy = ((float)k + rand01(&g)) / (float)spp;
-                Ray ray = camera_ray(&s->camera, x, y, W, H, jx, jy);
-                accum = add(accum, ray_color(s, ray, &g, &local));
+        for (int x = x0; x < x1; ++x) {
+            V3 color;
+            if (rng_mode == 0) {
+                Rng g = { .state = (uint32_t)(x + y * W) ^ (uint32_t)(s->seed & 0xFFFFFFFFu), .c = &local };
+                V3 accum = v3(0, 0, 0);
+                for (int k = 0; k < spp; ++k) {
+                    float jx = ((float)k + rand01(&g)) / (float)spp;
+                    float jy = ((float)k + rand01(&g)) / (float)spp;
+                    Ray ray = camera_ray(&s->camera, x, y, W, H, jx, jy);
+                    accum = add(accum, ray_color(s, ray, &g, &local));
+                }
+                float inv_spp = 1.0f / (float)spp;
+                color = scale(accum, inv_spp);
+            } else {
+                uint64_t sum[3] = { 0, 0, 0 };
+                const uint64_t pixel = (uint64_t)x + (uint64_t)y * (uint64_t)W;
+                for (int k = 0; k < spp; ++k) {
+                    Rng g = { .c = &local, .mode = 1, .key0 = (uint32_t)s->seed, .key1 = (uint32_t)(s->seed >> 32), .sub = pixel * (uint64_t)spp + (uint64_t)k };
+                    float jx = ((float)k + rand01(&g)) / (float)spp;
+                    float jy = ((float)k + rand01(&g)) / (float)spp;
+                    Ray ray = camera_ray(&s->camera, x, y, W, H, jx, jy);
+                    V3 L = ray_color(s, ray, &g, &local);              /* already clamped to [0,1] (:935) */
+                    sum[0] += dsrt_oracle_mode1_quantize(L.x);
+                    sum[1] += dsrt_oracle_mode1_quantize(L.y);
+                    sum[2] += dsrt_oracle_mode1_quantize(L.z);
+                }
+                color = v3(dsrt_oracle_mode1_mean(sum[0], spp), dsrt_oracle_mode1_mean(sum[1], spp), dsrt_oracle_mode1_mean(sum[2], spp));
             }
-            float inv_spp = 1.0f / (float)spp;
-            V3 color = scale(accum, inv_spp);
             color.x = fmaxf(color.x, 0.0f); color.y = fmaxf(color.y, 0.0f); color.z = fmaxf(color.z, 0.0f);
             color.x = fminf(color.x, 10.0f); color.y = fminf(color.y, 10.0f); color.z = fminf(color.z, 10.0f);
             color.x = O_POWF(color.x, inv_gamma);
@@ -584,6 +649,11 @@ int dsrt_oracle_render_rows(const GPUScene* s, int W, int H, int y0, int y1, uin
     return 0;
 }
 
+int dsrt_oracle_render_rows(const GPUScene* s, int W, int H, int y0, int y1, uint8_t* rgb8, float* rgb_f32,
+                            DsrtOracleCounters* counters) {
+    return dsrt_oracle_render_rect(s, W, H, 0, W, y0, y1, 0, rgb8, rgb_f32, counters);
+}
+
 int dsrt_oracle_bbox_hit(const float lo[3], const float hi[3], const float orig[3], const float dir[3], float t_min, float t_max) {
     DsrtOracleCounters c;
     memset(&c, 0, sizeof c);
@@ -598,13 +668,13 @@ int dsrt_oracle_bbox_hit(const float lo[3], const float hi[3], const float orig[
 /* Test hooks for the known-answer vectors of the reference's device helpers (tests/golden/ref_devkat.json). */
 void dsrt_oracle_random_in_unit_sphere(uint32_t* state, float out[3]) {
     DsrtOracleCounters c; memset(&c, 0, sizeof c);
-    Rng g = { *state, &c };
+    Rng g = { .state = *state, .c = &c };
     V3 p = random_in_unit_sphere(&g);
     *state = g.state; out[0] = p.x; out[1] = p.y; out[2] = p.z;
 }
 void dsrt_oracle_random_cosine_direction(uint32_t* state, float out[3]) {
     DsrtOracleCounters c; memset(&c, 0, sizeof c);
-    Rng g = { *state, &c };
+    Rng g = { .state = *state, .c = &c };
     V3 p = random_cosine_direction(&g);
     *state = g.state; out[0] = p.x; out[1] = p.y; out[2] = p.z;
 }
@@ -629,7 +699,7 @@ void dsrt_oracle_normalize(const float v[3], float out[3]) {
 }
 int dsrt_oracle_scatter_metal(const float dir[3], const float n[3], float fuzz, uint32_t* state, float out_dir[3]) {
     DsrtOracleCounters c; memset(&c, 0, sizeof c);
-    Rng g = { *state, &c };
+    Rng g = { .state = *state, .c = &c };
     GPUMaterial m; memset(&m, 0, sizeof m); m.fuzz = fuzz;
     Ray in = { v3(0, 0, 0), v3(dir[0], dir[1], dir[2]) }, sc;
     Hit rec; memset(&rec, 0, sizeof rec); rec.normal = v3(n[0], n[1], n[2]);
@@ -640,7 +710,7 @@ int dsrt_oracle_scatter_metal(const float dir[3], const float n[3], float fuzz, 
 }
 void dsrt_oracle_scatter_dielectric(const float dir[3], const float n[3], int front_face, float ref_idx, uint32_t* state, float out_dir[3]) {
     DsrtOracleCounters c; memset(&c, 0, sizeof c);
-    Rng g = { *state, &c };
+    Rng g = { .state = *state, .c = &c };
     GPUMaterial m; memset(&m, 0, sizeof m); m.ref_idx = ref_idx;
     Ray in = { v3(0, 0, 0), v3(dir[0], dir[1], dir[2]) }, sc;
     Hit rec; memset(&rec, 0, sizeof rec); rec.normal = v3(n[0], n[1], n[2]); rec.front_face = front_face;

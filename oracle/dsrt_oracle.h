@@ -82,6 +82,23 @@ typedef struct DsrtOracleCounters {
 int dsrt_oracle_render_rows(const GPUScene* scene, int W, int H, int y0, int y1,
                             uint8_t* rgb8, float* rgb_f32, DsrtOracleCounters* counters);
 
+/*
+ * The same loop over the pixel rectangle x in [x0, x1), y in [y0, y1) (kernel coordinates as above), with the random source chosen by
+ * rng_mode: 0 = the reference's LCG stream per pixel (dsrt_oracle_render_rows is this with x0 = 0, x1 = W, rng_mode 0); 1 = the
+ * product's DsrtRenderDesc.rng_mode 1 exactly as include/dsrt.h writes it out -- Philox4x32-10 keyed by scene->seed, sub-sequence
+ * (x + y*W)*spp + k per sample, per-sample values quantised to 2^-20 and summed in 64 bits, mean in double, mode 0's tone map.
+ * Pixels outside the rectangle are not written.  Returns 0, or a negative number for invalid arguments.
+ */
+int dsrt_oracle_render_rect(const GPUScene* scene, int W, int H, int x0, int x1, int y0, int y1, int rng_mode,
+                            uint8_t* rgb8, float* rgb_f32, DsrtOracleCounters* counters);
+
+/* Philox4x32-10 in counter form: words first .. first+n-1 of sub-sequence `sub` under key `seed` (word i is word i & 3 of the block
+ * with counter {i >> 2, sub}) -- what rocrand_init(seed, sub, first) followed by n calls of rocrand() returns. */
+void dsrt_oracle_philox_words(uint64_t seed, uint64_t sub, uint64_t first, int n, uint32_t* out);
+/* rng_mode 1's per-sample quantisation ((uint32_t)(c * 2^20 + 0.5f)) and per-pixel mean ((float)((double)sum / 2^20 / spp)), as the render uses them. */
+uint32_t dsrt_oracle_mode1_quantize(float c);
+float dsrt_oracle_mode1_mean(uint64_t sum, int spp);
+
 /* rand01 of src/gpu_render.cu:77-80, exposed for the known-answer test. */
 float dsrt_oracle_rand01(uint32_t* state);
 

@@ -147,7 +147,8 @@ def test_certified_tree_in_shards_batches_far_cameras_and_rng_mode_1(dsrt, cert_
     got = out.cpu().numpy().reshape(n, H, W, 3)
     for k in range(n):
         assert np.array_equal(got[k], want[k]), (frames[k], "batch")
-    # rng_mode 1 has no reference counterpart: on the certified tree it must be what the plain walk gives in the same mode (every BVH answer is the same)
+    # rng_mode 1 is not the reference's stream; its CPU oracle (dsrt_oracle_render_rect) holds the certified tree to its bytes in tests/test_gpu_rng_mode1.py.
+    # Here: on the certified tree it must be what the plain walk gives in the same mode (every BVH answer is the same)
     cert_ctx.set_camera_sun(cams[3], suns[3])
     a, _, _ = cert_ctx.render_to_host(dsrt.make_desc(W, H, spp, depth, rng_mode=1))
     b, _, _ = cert_ctx.render_to_host(dsrt.make_desc(W, H, spp, depth, rng_mode=1, tune=(0, 0, 0, 64)))

@@ -279,7 +279,8 @@ def test_philox_stream_equals_rocrand(gpu_ctx):
 @pytest.mark.parametrize("name", ["station_near", "lights", "c1_spheres"])
 def test_rng_mode1_is_deterministic_shard_invariant_and_statistically_mode0(dsrt, gpu_ctx, oracle, name):
     """rng_mode 1 (one Philox sub-sequence per (pixel, sample)) is NOT bit-identical to the reference's LCG mode by design;
-    it must be reproducible, independent of sharding / hand-out order, and the same image up to Monte-Carlo noise."""
+    it must be reproducible, independent of sharding / hand-out order, and the same image up to Monte-Carlo noise.  Its bytes are held to
+    the CPU oracle's rng_mode 1 in tests/test_gpu_rng_mode1.py."""
     import torch
     hs, scene, W, H, _, depth = _scene(dsrt, name)
     spp = 256

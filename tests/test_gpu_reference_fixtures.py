@@ -114,7 +114,7 @@ def test_station_pose_frames_equal_the_reference_kernels_images(dsrt, gpu_ctx, f
 
 def test_both_math_modes_through_shards_batch_and_rng_mode_1(dsrt, gpu_ctx, fixtures):
     """Each compilation of the kernels has launch paths of its own (device_api.hip: devlibm::launch_render_batch, launch_resolve, sharded launches).  In rng_mode 0 each must give the
-    REFERENCE KERNEL's image (the fixture); in rng_mode 1 -- which has no reference counterpart -- each must give what a single whole-frame launch gives in the same modes."""
+    REFERENCE KERNEL's image (the fixture); in rng_mode 1 -- which is not the reference's stream (its CPU oracle is dsrt_oracle_render_rect: tests/test_gpu_rng_mode1.py) -- each must give what a single whole-frame launch gives in the same modes."""
     import torch
     cache = {}
     mm = fixtures["math_mode"]
