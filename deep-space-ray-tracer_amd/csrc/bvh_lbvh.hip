@@ -16,6 +16,18 @@
 //      sums -- kept internal nodes first, in radix-tree order, so the root is node 0, then the leaves -- and written as GPUBVHNode.
 //      (Round 2's first version cut the Morton order into runs of 4 whatever lay between them and used 30-bit codes: a run that straddles
 //      a gap of the hierarchy makes a leaf box as big as the gap, and the near frame took 1850 ms on that tree.)
+// Determinism contract (the output is a pure function of the triangles; tests/_oracle_lbvh.py restates it on the CPU and
+// tests/test_gpu_lbvh.py holds every node word, tri_indices and the stack need to it):
+//   - a triangle's box is its vertex min / max; the scene box the min / max of those; extent = the largest axis span, pad = extent * 2^-12
+//     (1e-6 when extent is 0); float32 arithmetic, IEEE division, no contraction (Makefile flags)
+//   - code: centroid 0.5f*(lo+hi) of the UNPADDED box, u = (c - lo_scene) / ext_axis (0 on an axis with no extent), * 2^21, clamped to
+//     [0, 2^21 - 1], truncated; interleaved with x in the top bit of each triple.  Then an axis of zero thickness is widened by pad
+//   - order: a stable radix sort of the 63-bit codes (equal codes keep input order)
+//   - topology: keys extended by their sorted position; a range splits at its one adjacent pair of shortest common prefix; the node over
+//     [lo, g] is index g, the one over [g + 1, hi] index g + 1, the root node 0
+//   - boxes: exact fminf / fmaxf unions (on gfx950 -0.0 orders below +0.0), the padded triangle boxes at the bottom; N <= 4 is one leaf
+//     over the padded boxes as well
+//   - numbering: kept internal nodes in radix-node order, then the leaves in item order (internal nodes 0..N-2, then triangles 0..N-1)
 // The result is copied into the host scene's vectors (a 1 M-triangle tree is 20 MB), because the scene's home is the host
 // (DsrtHostScene) and dsrt_scene_upload re-lays it out for traversal anyway.
 #include <hip/hip_runtime.h>
@@ -205,6 +217,18 @@ __global__ void emit_kernel(int n, int kept, const int2* __restrict__ children, 
     nodes[at] = out;
 }
 
+// n <= kLeafMax: the whole mesh is one leaf, its box the union of the padded triangle boxes that morton_kernel left in tb (merged in
+// sorted order, as fit_kernel merges, so a zero on a box face gets the same sign as on every other tree this file builds)
+__global__ void single_leaf_kernel(const Bounds* __restrict__ tb, const uint32_t* __restrict__ sorted_index, int n, GPUBVHNode* __restrict__ nodes) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Bounds b = tb[sorted_index[0]];
+    for (int t = 1; t < n; ++t) b = merged(b, tb[sorted_index[t]]);
+    GPUBVHNode out;
+    out.bbox_min = DsrtF3{b.lo[0], b.lo[1], b.lo[2]}; out.bbox_max = DsrtF3{b.hi[0], b.hi[1], b.hi[2]};
+    out.left = out.right = -1; out.tri_offset = 0; out.tri_count = n;
+    nodes[0] = out;
+}
+
 template <typename T>
 struct Dev {
     T* p = nullptr;
@@ -253,6 +277,7 @@ extern "C" int dsrt_host_scene_build_bvh_gpu(DsrtHostScene* hs, int device, floa
             size_t bytes = tmp_bytes;
             good = ok(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, bytes, d_code.p, d_code2.p, d_idx.p, d_idx2.p, N, 0, 63), "hipcub sort");
         }
+        if (good && N <= kLeafMax) hipLaunchKernelGGL(single_leaf_kernel, dim3(1), dim3(64), 0, nullptr, d_tb.p, d_idx2.p, N, d_nodes.p);
         if (good && N > kLeafMax) {
             good = ok(hipMemsetAsync(d_arrived.p, 0, n * sizeof(int), nullptr), "hipMemsetAsync");
             if (good) {
@@ -283,24 +308,10 @@ extern "C" int dsrt_host_scene_build_bvh_gpu(DsrtHostScene* hs, int device, floa
         std::vector<uint32_t> order(n);
         if (!ok(hipMemcpy(order.data(), d_idx2.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy order")) return DSRT_ERR_HIP;
         hs->tri_indices.assign(order.begin(), order.end());
-        int total;
-        if (N <= kLeafMax) {                                          // the whole mesh is one leaf (it sits at index 0)
-            total = 1;
-            GPUBVHNode leaf;
-            float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-            for (const GPUTriangle& t : hs->tris) {
-                const float v[3][3] = {{t.v0.x, t.v1.x, t.v2.x}, {t.v0.y, t.v1.y, t.v2.y}, {t.v0.z, t.v1.z, t.v2.z}};
-                for (int a = 0; a < 3; ++a) for (int c = 0; c < 3; ++c) { lo[a] = std::fmin(lo[a], v[a][c]); hi[a] = std::fmax(hi[a], v[a][c]); }
-            }
-            leaf.bbox_min = DsrtF3{lo[0], lo[1], lo[2]}; leaf.bbox_max = DsrtF3{hi[0], hi[1], hi[2]};
-            leaf.left = leaf.right = -1; leaf.tri_offset = 0; leaf.tri_count = N;
-            hs->nodes.assign(1, leaf);
-        } else {
-            total = kept + leaf_count;
-            if (kept < 1 || leaf_count < 2 || total > items) { set_error("LBVH collapse produced an impossible node count"); return DSRT_ERR_INVALID; }
-            hs->nodes.resize((size_t)total);
-            if (!ok(hipMemcpy(hs->nodes.data(), d_nodes.p, (size_t)total * sizeof(GPUBVHNode), hipMemcpyDeviceToHost), "hipMemcpy nodes")) return DSRT_ERR_HIP;
-        }
+        const int total = N <= kLeafMax ? 1 : kept + leaf_count;          // (N <= kLeafMax: the one leaf of single_leaf_kernel)
+        if (N > kLeafMax && (kept < 1 || leaf_count < 2 || total > items)) { set_error("LBVH collapse produced an impossible node count"); return DSRT_ERR_INVALID; }
+        hs->nodes.resize((size_t)total);
+        if (!ok(hipMemcpy(hs->nodes.data(), d_nodes.p, (size_t)total * sizeof(GPUBVHNode), hipMemcpyDeviceToHost), "hipMemcpy nodes")) return DSRT_ERR_HIP;
         // height = levels on the longest root-to-leaf path (the traversal stack needs height - 1 entries): one pass over the nodes
         std::vector<int> level((size_t)total, 0);
         int height = 1;

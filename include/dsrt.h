@@ -99,7 +99,8 @@ int dsrt_host_scene_build_bvh_sah(DsrtHostScene* hs);
  * node format (leaf <= 4), copied into the host scene.  The "GPU-side BVH build" of SURVEY.md 8(f) n4: milliseconds instead of the
  * seconds of the host builders, for hosts that rebuild per frame as the reference does (src/main.cpp:405).  Same parity status as the
  * SAH tree: a statistically equivalent image, exact agreement between the kernel and the oracle on this tree.  `build_ms` (optional)
- * receives the device time of the construction kernels, `total_ms` the whole call including the triangle upload and the copy back. */
+ * receives the device time of the construction kernels, `total_ms` the whole call including the triangle upload and the copy back.
+ * The tree is deterministic, bit for bit: a pure function of the triangles (contract: the header comment of csrc/bvh_lbvh.hip). */
 int dsrt_host_scene_build_bvh_gpu(DsrtHostScene* hs, int device, float* build_ms, float* total_ms);
 
 /* Fill `out` with HOST pointers into the scene's arrays (valid until the scene is modified or

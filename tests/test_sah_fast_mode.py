@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from _bvh_check import check_bvh
 from conftest import ASSETS
 from test_oracle import CASES, SUN
 
@@ -25,24 +26,6 @@ def _load(dsrt, world, kind):
     return hs
 
 
-def _flat_pad(verts):
-    """host_internal.hpp flat_box_pad: the non-parity builders widen a triangle box that has zero thickness on an axis by this much to either side
-    (a leaf box of zero thickness is never hit by the reference's slab test)."""
-    ext = np.float32((verts.reshape(-1, 3).max(axis=0) - verts.reshape(-1, 3).min(axis=0)).max())
-    return np.float32(ext * np.float32(1.0 / 4096.0)) if ext > 0 else np.float32(1e-6)
-
-
-def _assert_tight(v, nd, pad):
-    """Leaf box = the exact float bounds of its triangles, each triangle's own box first widened by `pad` on an axis where it is flat."""
-    tri = v.reshape(-1, 3, 3)
-    lo, hi = tri.min(axis=1).astype(np.float32), tri.max(axis=1).astype(np.float32)
-    flat = lo == hi
-    lo = np.where(flat, lo - pad, lo).astype(np.float32)
-    hi = np.where(flat, hi + pad, hi).astype(np.float32)
-    assert np.array_equal(lo.min(axis=0), nd["bbox_min"]) and np.array_equal(hi.max(axis=0), nd["bbox_max"])
-    assert (nd["bbox_max"] > nd["bbox_min"]).all()                        # never a box of zero thickness
-
-
 def _scene(dsrt, name, kind):
     world, cam_args, spp = CASES[name]
     hs = _load(dsrt, world, kind)
@@ -55,31 +38,7 @@ def _scene(dsrt, name, kind):
 def test_sah_tree_is_a_valid_bvh(dsrt, world):
     hs = _load(dsrt, world, "sah")
     a = hs.arrays()
-    nodes, idx, tris = a["nodes"], a["idx"], a["tris"]
-    assert sorted(idx.tolist()) == list(range(len(tris)))                 # a permutation: every triangle in exactly one leaf
-    verts = tris["v"]                                                     # [N, 3 vertices, xyz]
-    pad = _flat_pad(verts)
-    seen_nodes, covered = set(), np.zeros(len(tris), bool)
-    todo = [(0, None)]
-    while todo:
-        n, parent = todo.pop()
-        assert n not in seen_nodes
-        seen_nodes.add(n)
-        nd = nodes[n]
-        if parent is not None:                                            # child box inside the parent's
-            assert (nd["bbox_min"] >= nodes[parent]["bbox_min"]).all() and (nd["bbox_max"] <= nodes[parent]["bbox_max"]).all()
-        if nd["tri_count"] > 0:
-            assert nd["left"] == -1 and nd["right"] == -1 and nd["tri_count"] <= 4
-            sl = idx[nd["tri_offset"]:nd["tri_offset"] + nd["tri_count"]]
-            assert not covered[sl].any()
-            covered[sl] = True
-            v = verts[sl].reshape(-1, 3)
-            _assert_tight(v, nd, pad)
-        else:
-            assert nd["left"] == n + 1 and nd["right"] > nd["left"]       # pre-order numbering
-            todo += [(int(nd["right"]), n), (int(nd["left"]), n)]
-    assert covered.all() and len(seen_nodes) == len(nodes)
-    assert hs.stack_need <= 64
+    check_bvh(a["nodes"], a["idx"], a["tris"]["v"], hs.stack_need, preorder=True)
 
 
 def test_sah_image_is_the_median_image_up_to_desynchronised_pixels_and_costs_less(dsrt, oracle):
@@ -119,28 +78,8 @@ def test_gpu_built_lbvh_is_a_valid_tree_and_the_kernel_matches_the_oracle_on_it(
     hs, scene, W, H, spp, depth = _scene(dsrt, name, "lbvh")
     assert hs.lbvh_build_ms > 0 and hs.lbvh_total_ms >= hs.lbvh_build_ms
     a = hs.arrays()
-    nodes, idx, tris = a["nodes"], a["idx"], a["tris"]
-    assert sorted(idx.tolist()) == list(range(len(tris)))
-    verts = tris["v"]
-    pad = _flat_pad(verts)
-    covered, seen, todo = np.zeros(len(tris), bool), set(), [(0, None)]
-    while todo:
-        n, parent = todo.pop()
-        assert n not in seen
-        seen.add(n)
-        nd = nodes[n]
-        if parent is not None:
-            assert (nd["bbox_min"] >= nodes[parent]["bbox_min"]).all() and (nd["bbox_max"] <= nodes[parent]["bbox_max"]).all()
-        if nd["tri_count"] > 0:
-            assert nd["left"] == -1 and nd["right"] == -1 and nd["tri_count"] <= 4
-            sl = idx[nd["tri_offset"]:nd["tri_offset"] + nd["tri_count"]]
-            assert not covered[sl].any()
-            covered[sl] = True
-            v = verts[sl].reshape(-1, 3)
-            _assert_tight(v, nd, pad)
-        else:
-            todo += [(int(nd["right"]), n), (int(nd["left"]), n)]
-    assert covered.all() and len(seen) == len(nodes) and hs.stack_need <= 64
+    nodes, idx = a["nodes"], a["idx"]
+    check_bvh(nodes, idx, a["tris"]["v"], hs.stack_need)
     want_rgb, want_f32, want_cnt = oracle.render(scene, W, H)
     gpu_ctx.upload(scene)
     rgb, f32, st = gpu_ctx.render_to_host(dsrt.make_desc(W, H, spp, depth, collect_counters=2), want_f32=True)
