@@ -2,7 +2,7 @@
 #
 #   make lib      deep-space-ray-tracer_amd/libdsrt_hip.so   (kernels + C ABI + host scene builder)
 #   make tools    deep-space-ray-tracer_amd/dsrt_render       (CLI frame driver, mirrors src/main.cpp's flags)
-#   make oracle   oracle/libdsrt_oracle*.so and, where /root/reference exists, oracle/_ref/ref_host
+#   make oracle   oracle/libdsrt_oracle*.so and, where /root/reference exists, oracle/_ref/ref_host; tests/liboracle_sample_sets.so (a test helper on top of the oracle)
 #   make all      everything
 #
 # hipcc cross-compiles for gfx950 without a GPU present.  -ffp-contract=off and the absence of any fast-math
@@ -51,11 +51,17 @@ $(PKG)/dsrt_render: $(PKG)/tools/dsrt_render.cpp $(PKG)/libdsrt_hip.so $(HEADERS
 $(PKG)/main_flow_driver: $(PKG)/tools/main_flow_driver.cpp $(PKG)/libdsrt_hip.so $(HEADERS)
 	$(CXX) $(CXXFLAGS) -o $@ $< -L$(PKG) -ldsrt_hip -Wl,-rpath,'$$ORIGIN' -Wl,-rpath-link,/opt/rocm/lib
 
-oracle:
+oracle: tests/liboracle_sample_sets.so
 	$(MAKE) -C oracle all
 
+# The CPU model of sample sets (tests/oracle_sample_sets.c includes oracle/dsrt_oracle.c), built with the oracle's own flags (oracle/Makefile, CFLAGS).
+ORACLE_CC     ?= gcc
+ORACLE_CFLAGS := -std=c11 -O2 -fPIC -ffp-contract=off -fno-fast-math -mfma -Wall -Wextra -Wno-unused-parameter
+tests/liboracle_sample_sets.so: tests/oracle_sample_sets.c oracle/dsrt_oracle.c oracle/dsrt_oracle.h include/dsrt_detmath.h include/dsrt_scene_abi.h
+	$(ORACLE_CC) $(ORACLE_CFLAGS) -shared -o $@ $< -lm
+
 clean:
-	rm -rf $(BUILD) $(PKG)/libdsrt_hip.so $(PKG)/dsrt_render $(PKG)/main_flow_driver
+	rm -rf $(BUILD) $(PKG)/libdsrt_hip.so $(PKG)/dsrt_render $(PKG)/main_flow_driver tests/liboracle_sample_sets.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib tools oracle clean

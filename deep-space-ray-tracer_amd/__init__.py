@@ -17,7 +17,7 @@ except ImportError:  # pragma: no cover
     _torch = None
 
 from . import capi
-from .capi import (DsrtFrame, DsrtGBuffer, DsrtPose, DsrtRayHits, DsrtRays, DsrtRenderDesc, DsrtStats, GPUCamera, GPUScene)
+from .capi import (DsrtAccum, DsrtFrame, DsrtGBuffer, DsrtPose, DsrtRayHits, DsrtRays, DsrtRenderDesc, DsrtStats, GPUCamera, GPUScene)
 
 lib = capi.load()
 
@@ -455,6 +455,54 @@ class Context:
                        "dsrt_trace_rays_to_host")
         return (out, st) if want_stats else out
 
+    # ---- sample sets (include/dsrt.h, dsrt_render_accumulate): rng_mode 1 sums in caller-owned int64 device tensors ----
+    def _sum_tensor(self, desc, x, what, required=True):
+        if x is None:
+            if required:
+                raise ValueError(f"{what} is required")
+            return None
+        if _torch is None or not isinstance(x, _torch.Tensor):
+            raise TypeError(f"{what} must be a torch tensor")
+        if x.dtype != _torch.int64:
+            raise TypeError(f"{what} must be int64, not {x.dtype}")
+        if x.device.type != "cuda" or x.device.index != self.device:
+            raise ValueError(f"{what} is on {x.device}, the context is on cuda:{self.device}")
+        if not x.is_contiguous() or x.numel() != desc.width * desc.height * 3:
+            raise ValueError(f"{what} must be contiguous with width*height*3 = {desc.width * desc.height * 3} elements")
+        return x
+
+    def _raw_stream(self, stream):
+        if isinstance(stream, _torch.cuda.Stream):
+            return stream.cuda_stream
+        return int(stream) if stream else _torch.cuda.current_stream(self.device).cuda_stream
+
+    def render_accumulate(self, desc, first, count, stride=1, sums=None, sum_sq=None, stream=None, want_stats=False):
+        """dsrt_render_accumulate: ADD the sums of samples {first + j*stride : 0 <= j < count} of every pixel (a frame planned at desc.spp, rng_mode 1)
+        to `sums` (and the squared samples to `sum_sq`, if given): int64 device tensors of width*height*3 elements, zeroed by the caller once.  On
+        `stream` (a torch.cuda.Stream or a raw hipStream_t; default: torch's current stream); with want_stats the call synchronises and returns DsrtStats."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=False)
+        acc = DsrtAccum(C.c_void_p(sums.data_ptr()), C.c_void_p(sum_sq.data_ptr()) if sum_sq is not None else None)
+        st = DsrtStats() if want_stats else None
+        _check(lib.dsrt_render_accumulate(self._h, C.byref(desc), int(first), int(count), int(stride), C.byref(acc), C.c_void_p(self._raw_stream(stream)),
+                                          C.byref(st) if st is not None else None), "dsrt_render_accumulate")
+        return st
+
+    def resolve_accumulated(self, desc, sums, samples_done, sum_sq=None, want_rgb8=True, want_f32=False, want_var=False, stream=None):
+        """dsrt_resolve_accumulated: the image of `sums` after `samples_done` samples per pixel.  Returns (rgb8, f32, var) as device tensors of shape
+        (height, width, 3) -- uint8, float32, float32 (the variance of the mean; needs sum_sq) -- None for what was not asked for."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=want_var)
+        shape, dev = (desc.height, desc.width, 3), sums.device
+        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
+        f32 = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_f32 else None
+        var = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_var else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
+        _check(lib.dsrt_resolve_accumulated(self._h, C.byref(desc), C.byref(acc), int(samples_done), ptr(rgb), ptr(f32), ptr(var),
+                                            C.c_void_p(self._raw_stream(stream))), "dsrt_resolve_accumulated")
+        return rgb, f32, var
+
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""
         old = C.c_uint32()
@@ -478,6 +526,55 @@ class Context:
         out = np.zeros_like(x)
         _check(lib.dsrt_selftest_math(self._h, int(fn), x.ctypes.data, float(y), out.ctypes.data, int(x.size)), "dsrt_selftest_math")
         return out
+
+
+class Accumulator:
+    """The sums of one rng_mode 1 frame (include/dsrt.h, SAMPLE SETS) and how many samples per pixel they hold.  Render sets into it with any context on
+    the same device (`ctx` defaults to the one given here), resolve it whenever, and add another accumulator's sums to it with `+=` (sample sharding:
+    contexts, streams or -- after a copy or an all-reduce of the int64 tensors -- devices that rendered disjoint sets of the same frame).
+
+        acc = Accumulator(ctx, desc, moments=True)
+        for p in range(4):                       # four interleaved passes: a preview after each
+            acc.render(p, count, stride=4)       # count = len(range(p, desc.spp, 4))
+            rgb, _, var = acc.resolve(want_var=True)
+    """
+
+    def __init__(self, ctx, desc, moments=False):
+        if desc.rng_mode != 1:
+            raise ValueError("sample sets are rng_mode 1's")
+        self.ctx, self.desc = ctx, desc
+        n = desc.width * desc.height * 3
+        self.sum = _torch.zeros(n, dtype=_torch.int64, device=f"cuda:{ctx.device}")
+        self.sum_sq = _torch.zeros(n, dtype=_torch.int64, device=f"cuda:{ctx.device}") if moments else None
+        self.samples_done = 0
+
+    @staticmethod
+    def pass_count(spp, first, stride):
+        """Samples in the set {first, first + stride, ...} below spp."""
+        return len(range(first, spp, stride))
+
+    def render(self, first, count=None, stride=1, ctx=None, stream=None, want_stats=False):
+        """Add the set {first + j*stride : 0 <= j < count} (count: all of them below spp by default) and count its samples."""
+        count = self.pass_count(self.desc.spp, first, stride) if count is None else count
+        st = (ctx or self.ctx).render_accumulate(self.desc, first, count, stride, self.sum, self.sum_sq, stream=stream, want_stats=want_stats)
+        self.samples_done += count
+        return st
+
+    def __iadd__(self, other):
+        d, o = self.desc, other.desc
+        if (d.width, d.height, d.spp, d.seed) != (o.width, o.height, o.spp, o.seed):
+            raise ValueError("accumulators of different frames (width, height, spp or seed differ)")
+        if self.sum_sq is not None and other.sum_sq is None:
+            raise ValueError("this accumulator sums squared samples and the other does not")
+        self.sum += other.sum.to(self.sum.device)
+        if self.sum_sq is not None:
+            self.sum_sq += other.sum_sq.to(self.sum_sq.device)
+        self.samples_done += other.samples_done
+        return self
+
+    def resolve(self, want_rgb8=True, want_f32=False, want_var=False, stream=None):
+        """(rgb8, f32, var) device tensors of the current sums (Context.resolve_accumulated)."""
+        return self.ctx.resolve_accumulated(self.desc, self.sum, self.samples_done, self.sum_sq if want_var else None, want_rgb8, want_f32, want_var, stream)
 
 
 class Multi:

@@ -24,12 +24,14 @@
 #include "device_layout.h"
 
 namespace dsrt {
-hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream);
+hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, bool sets, bool moments,
+                         hipStream_t stream);
 hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
 hipError_t launch_render_batch(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
 hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
                               uint32_t* total_items, hipStream_t stream);
-hipError_t launch_resolve(const unsigned long long* sums, int spp, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32, hipStream_t stream);
+hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
 hipError_t launch_philox(unsigned long long seed, unsigned long long sub, int n, uint32_t* ours, uint32_t* theirs, hipStream_t stream);
 hipError_t launch_deinterleave(const uint8_t* gathered, uint8_t* image, int W, int H, int tile, int tiles_x, int shard_count,
                                size_t shard_stride_bytes, hipStream_t stream);
@@ -44,10 +46,12 @@ hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream); 
 hipError_t launch_raycast(const RaycastArgs& a, bool any_hit, int blocks, hipStream_t stream);                  // raycast_kernel.hip
 // DsrtRenderDesc.math_mode 1: the same kernels compiled against the device math library's sinf / cosf / powf (render_kernel.hip, second compilation)
 namespace devlibm {
-hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream);
+hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, bool sets, bool moments,
+                         hipStream_t stream);
 hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
 hipError_t launch_render_batch(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
-hipError_t launch_resolve(const unsigned long long* sums, int spp, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32, hipStream_t stream);
+hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
 }  // namespace devlibm
 }  // namespace dsrt
 
@@ -601,9 +605,13 @@ int dsrt_shard_layout(const DsrtRenderDesc* desc, int* tiles_total, int* tiles_t
 
 // What a batch launch adds to a render: the frames' cameras and sun directions (the context's own camera is not used).
 struct BatchInput { int frames; const GPUCamera* cameras; const DsrtF3* sun_dirs; };
+// What an accumulate launch changes (dsrt_render_accumulate, checked there): the samples rendered -- {first + j*stride : 0 <= j < count} of a frame
+// planned at desc->spp -- and where their sums go (the caller's buffers, added to, never cleared; no resolve).
+struct AccumInput { int first, count, stride; unsigned long long* sum; unsigned long long* sum_sq; };
 
-static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, void* stream_v, DsrtStats* stats, const BatchInput* batch) {
-    if (!ctx || !desc || !d_rgb8) { set_error("dsrt_render: null argument"); return DSRT_ERR_INVALID; }
+static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, void* stream_v, DsrtStats* stats, const BatchInput* batch,
+                       const AccumInput* acc = nullptr) {
+    if (!ctx || !desc || (!d_rgb8 && !acc)) { set_error("dsrt_render: null argument"); return DSRT_ERR_INVALID; }
     if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
     if (desc->rng_mode != 0 && desc->rng_mode != 1) { set_error("dsrt_render: rng_mode must be 0 (reference LCG stream per pixel) or 1 (Philox4x32-10 stream per sample)"); return DSRT_ERR_INVALID; }
     if (desc->math_mode != 0 && desc->math_mode != 1) { set_error("dsrt_render: math_mode must be 0 (deterministic sin / cos / pow shared with the CPU oracle) or 1 (the device math library's)"); return DSRT_ERR_INVALID; }
@@ -634,7 +642,10 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     f.sun_radiance[0] = ctx->sun_radiance.x; f.sun_radiance[1] = ctx->sun_radiance.y; f.sun_radiance[2] = ctx->sun_radiance.z;
     f.sun_enabled = ctx->sun_enabled;
     f.width = desc->width; f.height = desc->height;
-    f.spp = desc->spp < 1 ? 1 : desc->spp;                              // src/gpu_render.cu:987-988
+    f.plan_spp = desc->spp < 1 ? 1 : desc->spp;                         // src/gpu_render.cu:987-988
+    f.spp = acc ? acc->count : f.plan_spp;                               // what the launch renders of each pixel: work items, slices and the pre-pass count these
+    f.sample_first = acc ? acc->first : 0;
+    f.sample_stride = acc ? acc->stride : 1;
     f.max_depth = desc->max_depth > 0 ? desc->max_depth : 12;           // :723-725
     const float gamma = desc->gamma > 0.0f ? desc->gamma : 1.0f;        // :1043
     f.inv_gamma = 1.0f / gamma;
@@ -644,9 +655,10 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     f.shard_rank = desc->shard_rank; f.shard_count = desc->shard_count > 1 ? desc->shard_count : 1;
     f.local_tiles = t.mine;
     if ((unsigned long long)t.mine * (unsigned long long)(t.tile * t.tile) >= (1ull << 31)) { set_error("dsrt_render: image too large (2^31 pixels per shard)"); return DSRT_ERR_INVALID; }
-    f.total_items = (uint32_t)t.mine * (uint32_t)(t.tile * t.tile);
+    uint32_t total_items = (uint32_t)t.mine * (uint32_t)(t.tile * t.tile);
     f.compact_output = desc->shard_count > 1 ? 1 : 0;
-    f.chunks = 1; f.chunk_len = f.spp; f.light_chunk_len = f.spp;
+    int chunks = 1, chunk_len = f.spp;
+    f.light_chunk_len = f.spp;
     const int frames = batch ? batch->frames : 1;
     if (batch) {
         if (frames < 1 || !batch->cameras || !batch->sun_dirs) { set_error("dsrt_render_batch: no frames"); return DSRT_ERR_INVALID; }
@@ -665,11 +677,16 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         // stealing on: 1 / 2 / 4 / 8 / 16 / 32 / 64 slices = 307 / 289 / 188 / 171 / 181 / 191 / 203 ms; whole frame on one GPU
         // 1091 / 1076 / 1063 / 1050 / 1047 (profiles/r02/README.md).  An item's integer sums are 32-bit in units of 2^-20: at most 4095
         // samples per item, so with more samples than that every pixel is sliced, whatever its tile sees.
-        f.chunk_len = (f.spp + 7) / 8;
-        if ((xp >> 8) & 0xFFFu) f.chunk_len = (f.spp + (int)((xp >> 8) & 0xFFFu) - 1) / (int)((xp >> 8) & 0xFFFu);   // experiment: slices per pixel
-        if (f.chunk_len < 1) f.chunk_len = 1;
-        if (f.chunk_len > 4095) f.chunk_len = 4095;
-        f.chunks = (f.spp + f.chunk_len - 1) / f.chunk_len;
+        chunk_len = (f.spp + 7) / 8;
+        if ((xp >> 8) & 0xFFFu) chunk_len = (f.spp + (int)((xp >> 8) & 0xFFFu) - 1) / (int)((xp >> 8) & 0xFFFu);   // experiment: slices per pixel
+        // Sample sets: a set of few samples per pixel (one of many interleaved passes) is not cut below kSetMinItem samples per item.  One of ten passes
+        // of the 1080p x 1000 near frame (100 samples): 8 slices of 13 = 114.6 ms, 4 / 2 / 1 slices = 87 / 86 / 88 ms; passes of 250 samples: 189 ms with 8
+        // slices, 190-198 with fewer (slices forced by development switch bits 8-19).  dsrt_render keeps its own cut.
+        constexpr int kSetMinItem = 32;
+        if (acc && !((xp >> 8) & 0xFFFu)) chunk_len = std::max(chunk_len, std::min(f.spp, kSetMinItem));
+        if (chunk_len < 1) chunk_len = 1;
+        if (chunk_len > 4095) chunk_len = 4095;
+        chunks = (f.spp + chunk_len - 1) / chunk_len;
         // Background pixels (tiles that see no geometry) are cut too, but not below kLightLen samples per item: uncut, their 1000-sample
         // items are the longest jobs of a frame and the light queue is served last (one of 8 shares of the near frame 166 -> 149 ms, frame
         // 70 60 -> 43 ms); cut as finely as the heavy pixels, their three 64-bit atomics per item cost the 250-spp sequence, whose frames
@@ -677,16 +694,21 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         {
             const int code = (int)((xp >> 28) & 3u);                                          // experiment
             const int kLightLen = code == 0 ? 128 : (code == 1 ? 64 : (code == 2 ? 256 : 512));
-            f.light_chunk_len = (xp & 0x80000000u) ? f.spp : std::max(f.chunk_len, kLightLen);
+            f.light_chunk_len = (xp & 0x80000000u) ? f.spp : std::max(chunk_len, kLightLen);
             if (f.light_chunk_len > 4095) f.light_chunk_len = 4095;
         }
         if (desc->width > 65535 || desc->height > 65535) { set_error("dsrt_render: rng_mode 1 hands samples between lanes with 16-bit pixel coordinates (width, height <= 65535)"); return DSRT_ERR_INVALID; }
-        if ((unsigned long long)f.total_items * 64ull >= (1ull << 32)) { set_error("dsrt_render: image too large for rng_mode 1 (more than 2^32 sample slices)"); return DSRT_ERR_INVALID; }
-        f.total_items *= 64u;                                   // upper bound (the pre-pass picks 8 to 64 slices per heavy pixel): sizes the grid only
-        const size_t words = out_pixels * 3;
-        if (ctx->accum_fixed.n < words) { int rc = ctx->accum_fixed.alloc(words); if (rc) return rc; }
-        HIP_TRY(hipMemsetAsync(ctx->accum_fixed.p, 0, words * sizeof(unsigned long long), stream));       // 24 bytes per pixel
-        a.accum_fixed = ctx->accum_fixed.p;
+        if ((unsigned long long)total_items * 64ull >= (1ull << 32)) { set_error("dsrt_render: image too large for rng_mode 1 (more than 2^32 sample slices)"); return DSRT_ERR_INVALID; }
+        total_items *= 64u;                                     // upper bound (the pre-pass picks 8 to 64 slices per heavy pixel): sizes the grid only
+        if (acc) {                                              // the caller's sums, added to
+            a.accum_fixed = acc->sum;
+            a.accum_sq = acc->sum_sq;
+        } else {
+            const size_t words = out_pixels * 3;
+            if (ctx->accum_fixed.n < words) { int rc = ctx->accum_fixed.alloc(words); if (rc) return rc; }
+            HIP_TRY(hipMemsetAsync(ctx->accum_fixed.p, 0, words * sizeof(unsigned long long), stream));       // 24 bytes per pixel
+            a.accum_fixed = ctx->accum_fixed.p;
+        }
     }
     a.out_rgb8 = d_rgb8;
     a.out_f32 = d_f32;
@@ -703,7 +725,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     int blocks = resident_blocks;                                         // persistent: exactly the resident set
     if ((xp >> 20) & 7u) blocks = std::max(1, resident_blocks >> ((xp >> 20) & 7u));     // experiment: a fraction of it (frames that overlap)
     {
-        const long long needed = ((long long)f.total_items + threads_per_block - 1) / threads_per_block;
+        const long long needed = ((long long)total_items + threads_per_block - 1) / threads_per_block;
         if (needed < blocks && !batch) blocks = (int)(needed > 0 ? needed : 1);
     }
     const int spill_entries = sc.view.stack_need > K ? sc.view.stack_need - K : 0;
@@ -782,7 +804,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
             ctx->batch_host[(size_t)frames + (size_t)i] = e;                                  // the frame's second entry (device_layout.h, BatchFrame)
         }
         HIP_TRY(hipMemcpyAsync(ctx->batch_table.p, ctx->batch_host.data(), 2 * (size_t)frames * sizeof(BatchFrame), hipMemcpyHostToDevice, stream));
-        HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, sched, (uint32_t)f.chunks, 0u, cull, stream,
+        HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, sched, (uint32_t)chunks, 0u, cull, stream,
                                   ctx->batch_table.p, (uint32_t)frames, (uint32_t)pre_stride));
         // rng_mode 0 at enough samples for a pixel to be a long chain: every frame's heavy tiles re-sorted by measured cost, as for a single
         // frame (the probe launch below in this function) -- one probe per frame, 6 ms each at 1080p, against a frame of a second
@@ -792,7 +814,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
                 RenderArgs pa = a;
                 std::memcpy(pa.frame.cam, ctx->batch_host[(size_t)i].cam, sizeof pa.frame.cam);
                 std::memcpy(pa.frame.sun_dir, ctx->batch_host[(size_t)i].sun_dir, 3 * sizeof(float));
-                pa.frame.spp = 4; pa.frame.chunks = 1; pa.frame.chunk_len = 4;
+                pa.frame.spp = 4;
                 pa.out_f32 = nullptr; pa.accum_fixed = nullptr; pa.counters = nullptr;
                 pa.sched = sched + pre_stride * (size_t)i;
                 pa.frame.tile_order = ctx->tile_order.p + pre_stride * (size_t)i;
@@ -813,11 +835,11 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     } else
     if ((flags & 3u) != DSRT_TUNE_NATURAL_ORDER && t.mine > 0) {
         const bool cull = (flags & 3u) != DSRT_TUNE_NO_CULLING && desc->collect_counters == 0;
-        if (cull) {                                             // culled pixels are never written: they are the zeros put here
+        if (cull && d_rgb8) {                                   // culled pixels are never written: they are the zeros put here (an accumulate launch adds nothing for them)
             HIP_TRY(hipMemsetAsync(d_rgb8, 0, out_pixels * 3, stream));
             if (d_f32) HIP_TRY(hipMemsetAsync(d_f32, 0, out_pixels * 3 * sizeof(float), stream));
         }
-        HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, sched, (uint32_t)f.chunks,
+        HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, sched, (uint32_t)chunks,
                                   (uint32_t)blocks * (uint32_t)threads_per_block, cull, stream));
         a.frame.tile_order = ctx->tile_order.p;
         // Probe: the render kernel itself at kProbeSpp samples per pixel (reference stream, nothing stored)
@@ -831,7 +853,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         if (!(flags & DSRT_TUNE_NO_PROBE) && desc->rng_mode == 0 && f.spp >= 64 * kProbeSpp) {
             RenderArgs pa = a;
             const int probe_spp = (xp & 64u) ? 2 * kProbeSpp : kProbeSpp;                  // experiment
-            pa.frame.spp = probe_spp; pa.frame.chunks = 1; pa.frame.chunk_len = probe_spp;
+            pa.frame.spp = probe_spp;
             pa.out_f32 = nullptr; pa.accum_fixed = nullptr; pa.counters = nullptr;
             pa.tile_work = ctx->tile_work.p;
             if (ctx->probe_queue.n < 1024) { int rc = ctx->probe_queue.alloc(1024); if (rc) return rc; }
@@ -845,16 +867,20 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     } else {
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sched, t.mine, 2, stream));           // every tile in the heavy queue, natural order
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 2), 64, 1, stream));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 3), f.chunks, 1, stream));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 4), f.chunk_len, 1, stream));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 3), chunks, 1, stream));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 4), chunk_len, 1, stream));
     }
     if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
     const bool count = desc->collect_counters != 0;
     if (batch) HIP_TRY(libm ? devlibm::launch_render_batch(a, desc->rng_mode, blocks, lean, stream) : launch_render_batch(a, desc->rng_mode, blocks, lean, stream));
-    else if (libm) HIP_TRY(devlibm::launch_render(a, K, desc->rng_mode, blocks, count, count || desc->checked != 0, desc->collect_counters != 2, lean, stream));
-    else HIP_TRY(launch_render(a, K, desc->rng_mode, blocks, count, count || desc->checked != 0, desc->collect_counters != 2, lean, stream));
-    if (desc->rng_mode == 1) HIP_TRY(libm ? devlibm::launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, stream)
-                                          : launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, stream));
+    else {
+        const bool sets = acc != nullptr, moments = acc && acc->sum_sq;
+        if (libm) HIP_TRY(devlibm::launch_render(a, K, desc->rng_mode, blocks, count, count || desc->checked != 0, desc->collect_counters != 2, lean, sets, moments, stream));
+        else HIP_TRY(launch_render(a, K, desc->rng_mode, blocks, count, count || desc->checked != 0, desc->collect_counters != 2, lean, sets, moments, stream));
+    }
+    if (desc->rng_mode == 1 && !acc)
+        HIP_TRY(libm ? devlibm::launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, nullptr, nullptr, stream)
+                     : launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, nullptr, nullptr, stream));
     HIP_TRY(hipEventRecord(ctx->done, stream));
     ctx->done_valid = true;
     if (stats) {
@@ -984,6 +1010,114 @@ int dsrt_render_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* h
 
 // The G-buffer pass (gbuffer_kernel.hip): the context's camera and sun, the reference tree, one launch.  It reads the resident scene and writes the
 // caller's buffers and one status word of its own; the context's working buffers, camera and sun are not touched.
+// ---- Sample sets (include/dsrt.h, dsrt_render_accumulate): rng_mode 1 sums of any set of a pixel's samples, added into caller-owned buffers ----
+namespace {
+int accum_fail(const char* fn, const char* why) { set_error(std::string(fn) + ": " + why); return DSRT_ERR_INVALID; }
+
+// Everything dsrt_render_accumulate refuses, checked before anything is launched or written.
+int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc) {
+    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
+    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL (it is required; sum_sq is the optional one)");
+    if (!ctx->scene || !ctx->scene->valid) { set_error(std::string(fn) + ": no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (desc->rng_mode != 1) return accum_fail(fn, "sample sets need rng_mode 1 (rng_mode 0 draws a pixel's samples from one serial stream)");
+    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
+    if (first < 0) return accum_fail(fn, "first < 0");
+    if (count < 1) return accum_fail(fn, "count < 1");
+    if (stride < 1) return accum_fail(fn, "stride < 1");
+    const long long spp = desc->spp < 1 ? 1 : desc->spp;
+    if ((long long)first + (long long)(count - 1) * (long long)stride >= spp) return accum_fail(fn, "the set reaches past the frame's planned samples (first + (count - 1) * stride >= spp)");
+    return DSRT_OK;
+}
+
+int check_resolve(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const void* rgb8, const void* f32, const void* var) {
+    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
+    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL");
+    if (desc->rng_mode != 1) return accum_fail(fn, "accumulated sums are rng_mode 1's");
+    if (desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
+    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
+    if (desc->width < 2 || desc->height < 2) return accum_fail(fn, "width and height must be >= 2");
+    if (samples_done < 1) return accum_fail(fn, "samples_done < 1");
+    if (!rgb8 && !f32 && !var) return accum_fail(fn, "no output");
+    if (var && !acc->sum_sq) return accum_fail(fn, "the variance needs DsrtAccum.sum_sq");
+    if (var && samples_done < 2) return accum_fail(fn, "the variance needs samples_done >= 2");
+    return DSRT_OK;
+}
+}  // namespace
+
+int dsrt_render_accumulate(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, void* stream, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_accumulate", [&]() -> int {
+    const int rc = check_accumulate("dsrt_render_accumulate", ctx, desc, first, count, stride, acc);
+    if (rc) return rc;
+    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq};
+    return render_impl(ctx, desc, nullptr, nullptr, stream, stats, nullptr, &in);
+    });
+}
+
+int dsrt_render_accumulate_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_accumulate_to_host", [&]() -> int {
+    int rc = check_accumulate("dsrt_render_accumulate_to_host", ctx, desc, first, count, stride, h_acc);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t words = (size_t)desc->width * desc->height * 3;
+    DevBuf<uint64_t> dsum, dsq;
+    if ((rc = dsum.alloc(words))) return rc;
+    if (h_acc->sum_sq && (rc = dsq.alloc(words))) return rc;
+    HIP_TRY(hipMemcpy(dsum.p, h_acc->sum, words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (h_acc->sum_sq) HIP_TRY(hipMemcpy(dsq.p, h_acc->sum_sq, words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    const DsrtAccum d{dsum.p, dsq.p};
+    DsrtStats local;
+    if ((rc = dsrt_render_accumulate(ctx, desc, first, count, stride, &d, nullptr, stats ? stats : &local))) return rc;
+    HIP_TRY(hipMemcpy(h_acc->sum, dsum.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (h_acc->sum_sq) HIP_TRY(hipMemcpy(h_acc->sum_sq, dsq.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return DSRT_OK;
+    });
+}
+
+int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, uint8_t* d_rgb8, float* d_f32,
+                             float* d_var_of_mean, void* stream_v) {
+    return dsrt::guarded("dsrt_resolve_accumulated", [&]() -> int {
+    const int rc = check_resolve("dsrt_resolve_accumulated", ctx, desc, acc, samples_done, d_rgb8, d_f32, d_var_of_mean);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // the context's last launch (an accumulate into these sums, maybe) comes first
+    const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
+    const size_t px = (size_t)desc->width * desc->height;
+    const unsigned long long* sum = (const unsigned long long*)acc->sum;
+    const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;
+    HIP_TRY(desc->math_mode == 1 ? devlibm::launch_resolve(sum, samples_done, inv_gamma, px, d_rgb8, d_f32, sq, d_var_of_mean, stream)
+                                 : launch_resolve(sum, samples_done, inv_gamma, px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
+    return DSRT_OK;
+    });
+}
+
+int dsrt_resolve_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, uint8_t* h_rgb8, float* h_f32,
+                                     float* h_var_of_mean) {
+    return dsrt::guarded("dsrt_resolve_accumulated_to_host", [&]() -> int {
+    int rc = check_resolve("dsrt_resolve_accumulated_to_host", ctx, desc, h_acc, samples_done, h_rgb8, h_f32, h_var_of_mean);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * desc->height;
+    DevBuf<uint64_t> dsum, dsq;
+    DevBuf<uint8_t> d8;
+    DevBuf<float> d32, dvar;
+    if ((rc = dsum.alloc(px * 3))) return rc;
+    HIP_TRY(hipMemcpy(dsum.p, h_acc->sum, px * 3 * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (h_var_of_mean) {
+        if ((rc = dsq.alloc(px * 3)) || (rc = dvar.alloc(px * 3))) return rc;
+        HIP_TRY(hipMemcpy(dsq.p, h_acc->sum_sq, px * 3 * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    if (h_rgb8 && (rc = d8.alloc(px * 3))) return rc;
+    if (h_f32 && (rc = d32.alloc(px * 3))) return rc;
+    const DsrtAccum d{dsum.p, dsq.p};
+    if ((rc = dsrt_resolve_accumulated(ctx, desc, &d, samples_done, d8.p, d32.p, dvar.p, nullptr))) return rc;
+    if (h_rgb8) HIP_TRY(hipMemcpy(h_rgb8, d8.p, px * 3, hipMemcpyDeviceToHost));
+    if (h_f32) HIP_TRY(hipMemcpy(h_f32, d32.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_var_of_mean) HIP_TRY(hipMemcpy(h_var_of_mean, dvar.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return DSRT_OK;
+    });
+}
+
 int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, void* stream_v, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_gbuffer", [&]() -> int {
     if (!ctx || !desc || !gb) { set_error("dsrt_render_gbuffer: null argument"); return DSRT_ERR_INVALID; }

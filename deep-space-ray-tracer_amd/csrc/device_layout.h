@@ -91,13 +91,15 @@ struct FrameParams {
     float inv_gamma;
     uint32_t seed32;
     uint32_t seed_hi;          // rng_mode 1: upper half of the 64-bit seed (Philox key.y)
-    int   chunks, chunk_len;   // rng_mode 1: a pixel's spp samples are split into `chunks` work items of `chunk_len` samples
+    int   sample_first, sample_stride;   // rng_mode 1: sample j (0 <= j < spp) of this launch is sample k = sample_first + j * sample_stride of the frame
+                               //   (dsrt_render_accumulate, include/dsrt.h; 0 and 1 for dsrt_render).  Work items, slices and stealing count j.
     int   light_chunk_len;     // rng_mode 1: samples per work item of a background pixel (path_machine.h, ST_FETCH)
     int   tile;                // tile edge in pixels (multiple of 8)
     int   tiles_x, tiles_y;
     int   shard_rank, shard_count;
     int   local_tiles;         // tiles owned by this shard
-    uint32_t total_items;      // local_tiles * tile * tile
+    int   plan_spp;            // rng_mode 1: the frame's planned samples per pixel, which sub-sequence numbers and the jitter divide by; `spp`
+                               //   above is what this launch renders of each pixel (equal for dsrt_render)
     int   compact_output;      // 1: tile-major shard buffer, 0: image order
     const uint32_t* tile_order; // processing order of this shard's tiles (local tile numbers, costliest first); null = natural order
 };
@@ -135,7 +137,12 @@ struct RenderArgs {
     const BatchFrame* batch;   // batch launch only: the table, batch_frames entries (two per frame)
     const uint32_t* batch_order; //   the frames' tile orders, BatchFrame::order_base apart
     uint32_t  batch_frames, batch_frame_pixels;   // table entries in the launch; output pixels per frame (W*H, or a shard's padded tile buffer)
-    uint32_t* tile_work;       // probe launch only (null otherwise): rays traced per local tile, the measured cost the order is refined by
+    union {
+        uint32_t* tile_work;   // probe launch only (null otherwise): rays traced per local tile, the measured cost the order is refined by
+        unsigned long long* accum_sq;   // MOMENTS launches only (rng_mode 1, dsrt_render_accumulate with sum_sq): [output pixel][3] sums of the
+                               //   squared quantised samples, units of 2^-20 (path_machine.h, end_sample).  Shares the slot: the two kinds of
+                               //   launch are never the same one, and the argument block keeps the layout the other kernels were built for
+    };
     uint64_t* counters;        // kNumCounters entries (counting build only)
     uint32_t* flags;           // checked-mode status word
     unsigned long long* accum_fixed; // rng_mode 1: [output pixel][3] sample sums in units of 2^-20, added with integer atomics (exact, so the

@@ -77,6 +77,13 @@ struct Lane {
     float* pend = nullptr;                      // &strip[0][lane of block], element i at pend[i * kPendStride]
 };
 
+// MOMENTS launches (advance_step): the lane also carries its item's sums of squared quantised samples, as bit patterns like `accum`.  A type of
+// its own, so that the other kernels' lanes stay exactly what they were.
+struct LaneMoments : Lane {
+    F3 accum_sq = {0, 0, 0};
+};
+template <bool MOMENTS> using LaneOf = typename std::conditional<MOMENTS, LaneMoments, Lane>::type;
+
 constexpr int kPendStride = 256;                // = threads per block of the render kernel
 constexpr int kPendWords = 14;                  // 13 words of continuation + one row for the shadow-ray request table
 __device__ __forceinline__ void pend_put(const Lane& ln, int i, F3 v) { ln.pend[(i + 0) * kPendStride] = v.x; ln.pend[(i + 1) * kPendStride] = v.y; ln.pend[(i + 2) * kPendStride] = v.z; }
@@ -104,15 +111,19 @@ __device__ __forceinline__ void mark_time(const RenderArgs& args, int which) {
     }
 }
 
+// rng_mode 1: the frame's sample number of the lane's sample j -- what sub-sequence and jitter are made of (FrameParams::sample_first)
+__device__ __forceinline__ int frame_sample(const FrameParams& P, int j) { return P.sample_first + j * P.sample_stride; }
+
 template <int RNGMODE> struct RngOf;
 template <> struct RngOf<0> { using type = uint32_t&; };
 template <> struct RngOf<1> { using type = PhiloxStream; };
-template <int RNGMODE>
+template <int RNGMODE, bool SETS>
 __device__ __forceinline__ typename RngOf<RNGMODE>::type make_rng(Lane& ln, const FrameParams& P) {
     if constexpr (RNGMODE == 0) {
         return ln.rng;
     } else {
-        const unsigned long long sub = (unsigned long long)(uint32_t)(ln.px + ln.ky * P.width) * (unsigned long long)(uint32_t)P.spp + (unsigned long long)(uint32_t)ln.sample;
+        const unsigned long long sub = (unsigned long long)(uint32_t)(ln.px + ln.ky * P.width) * (unsigned long long)(uint32_t)(SETS ? P.plan_spp : P.spp) +
+                                       (unsigned long long)(uint32_t)(SETS ? frame_sample(P, ln.sample) : ln.sample);
         return PhiloxStream{P.seed32, P.seed_hi, (uint32_t)sub, (uint32_t)(sub >> 32), ln.rng};
     }
 }
@@ -121,8 +132,11 @@ __device__ __forceinline__ typename RngOf<RNGMODE>::type make_rng(Lane& ln, cons
 // (device_api.hip: pack_scene) -- which is what an OBJ mesh with plain Kd materials is, the headline mesh included.  The blocks for the other material
 // classes, the sphere loops, the mixture branch and the texture fetch are then not compiled at all: exact by construction (they are the branches such a scene
 // never takes) and ~20 scalar registers the advance pass no longer keeps alive.
-template <bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false>
-__device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, uint32_t* c, uint32_t& flags) {
+// SETS (rng_mode 1 only; dsrt_render_accumulate): the lane's sample j is the frame's sample first + j*stride (FrameParams::sample_first); dsrt_render's
+// kernels are built without it and do not pay for the arithmetic.  MOMENTS (with SETS; sum_sq given): every sample also adds its squared quantised
+// value to a second set of sums.
+template <bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false, bool SETS = false, bool MOMENTS = false>
+__device__ __forceinline__ void advance_step(LaneOf<MOMENTS>& ln, const RenderArgs& args, uint32_t* c, uint32_t& flags) {
     const DeviceScene& S = args.scene;
     const int num_spheres = LEAN ? 0 : S.num_spheres;
     const FrameParams& P = args.frame;
@@ -135,10 +149,11 @@ __device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, u
     const int spp = P.spp;
     const int W = P.width, H = P.height;
     // the generator the body below draws from: the lane's LCG word itself, or a Philox stream rebuilt from (pixel, sample, draws)
-    typename RngOf<RNGMODE>::type rng = make_rng<RNGMODE>(ln, P);
+    typename RngOf<RNGMODE>::type rng = make_rng<RNGMODE, SETS>(ln, P);
     auto restream = [&]() {                      // rng_mode 1: point the generator at the current (pixel, sample), draw 0
         if constexpr (RNGMODE == 1) {
-            const unsigned long long sub = (unsigned long long)(uint32_t)(px + ky * W) * (unsigned long long)(uint32_t)spp + (unsigned long long)(uint32_t)sample;
+            const unsigned long long sub = (unsigned long long)(uint32_t)(px + ky * W) * (unsigned long long)(uint32_t)(SETS ? P.plan_spp : spp) +
+                                           (unsigned long long)(uint32_t)(SETS ? frame_sample(P, sample) : sample);
             rng.sub0 = (uint32_t)sub; rng.sub1 = (uint32_t)(sub >> 32); rng.n = 0;
         }
     };
@@ -151,9 +166,17 @@ __device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, u
             // associative, so the pixel's value is the same however its samples were cut into work items or handed between lanes.
             // The three words of `accum` hold the running sums as bit patterns; an item has at most 4095 samples (host), so no overflow.
             const F3 s01 = clamp01(L);
-            accum.x = __uint_as_float(__float_as_uint(accum.x) + (uint32_t)(s01.x * 1048576.0f + 0.5f));
-            accum.y = __uint_as_float(__float_as_uint(accum.y) + (uint32_t)(s01.y * 1048576.0f + 0.5f));
-            accum.z = __uint_as_float(__float_as_uint(accum.z) + (uint32_t)(s01.z * 1048576.0f + 0.5f));
+            const uint32_t qx = (uint32_t)(s01.x * 1048576.0f + 0.5f), qy = (uint32_t)(s01.y * 1048576.0f + 0.5f), qz = (uint32_t)(s01.z * 1048576.0f + 0.5f);
+            accum.x = __uint_as_float(__float_as_uint(accum.x) + qx);
+            accum.y = __uint_as_float(__float_as_uint(accum.y) + qy);
+            accum.z = __uint_as_float(__float_as_uint(accum.z) + qz);
+            if constexpr (MOMENTS) {
+                // q^2 in units of 2^-20, rounded: q <= 2^20, so q*q + 2^19 fits 64 bits and the result 2^20; 4095 of them fit 32 bits, like `accum`
+                auto sq = [](uint32_t q) { return (uint32_t)(((unsigned long long)q * q + (1ull << 19)) >> 20); };
+                ln.accum_sq.x = __uint_as_float(__float_as_uint(ln.accum_sq.x) + sq(qx));
+                ln.accum_sq.y = __uint_as_float(__float_as_uint(ln.accum_sq.y) + sq(qy));
+                ln.accum_sq.z = __uint_as_float(__float_as_uint(ln.accum_sq.z) + sq(qz));
+            }
         } else {
             accum = accum + clamp01(L);
         }
@@ -464,6 +487,12 @@ __device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, u
             atomicAdd(dst + 0, (unsigned long long)__float_as_uint(accum.x));
             atomicAdd(dst + 1, (unsigned long long)__float_as_uint(accum.y));
             atomicAdd(dst + 2, (unsigned long long)__float_as_uint(accum.z));
+            if constexpr (MOMENTS) {
+                unsigned long long* dsq = args.accum_sq + (size_t)out_index * 3;
+                atomicAdd(dsq + 0, (unsigned long long)__float_as_uint(ln.accum_sq.x));
+                atomicAdd(dsq + 1, (unsigned long long)__float_as_uint(ln.accum_sq.y));
+                atomicAdd(dsq + 2, (unsigned long long)__float_as_uint(ln.accum_sq.z));
+            }
         } else {
             // tone map + store :1003-1030
             float inv_spp = 1.0f / (float)spp;
@@ -583,6 +612,7 @@ __device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, u
                 out_index = P.compact_output ? (k * (uint32_t)(P.tile * P.tile) + in_y * (uint32_t)P.tile + in_x) : ((uint32_t)row * (uint32_t)W + (uint32_t)x);
                 if constexpr (BATCH) out_index += bf->image_slot * args.batch_frame_pixels;     // the batch's images (or shard buffers) lie one after another
                 accum = mk(0, 0, 0);
+                if constexpr (MOMENTS) ln.accum_sq = mk(0, 0, 0);
                 if (COUNT) ln.t0 = (uint32_t)wall_clock64();
                 if constexpr (RNGMODE == 0) {
                     rng = (uint32_t)(px + ky * W) ^ P.seed32;   // :990
@@ -640,6 +670,7 @@ __device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, u
                         ln.sample_end = (int)__float_as_uint(theirs[3 * kPendStride]);
                         if constexpr (BATCH) ln.frame = __float_as_uint(theirs[4 * kPendStride]);
                         accum = mk(0, 0, 0);                       // bit pattern 0: integer sums start at zero
+                        if constexpr (MOMENTS) ln.accum_sq = mk(0, 0, 0);
                         restream();
                         state = ST_GEN;
                     }
@@ -649,8 +680,10 @@ __device__ __forceinline__ void advance_step(Lane& ln, const RenderArgs& args, u
     }
     if (state == ST_GEN) {
         {
-            float jx = ((float)sample + rand01(rng)) / (float)spp;          // :995-996
-            float jy = ((float)sample + rand01(rng)) / (float)spp;
+            // (SETS: the frame's sample number over the frame's planned count; otherwise the launch renders the whole frame and j is k)
+            const int k = SETS ? frame_sample(P, sample) : sample, kspp = SETS ? P.plan_spp : spp;
+            float jx = ((float)k + rand01(rng)) / (float)kspp;          // :995-996
+            float jy = ((float)k + rand01(rng)) / (float)kspp;
             float u = ((float)px + jx) / (float)(W - 1);                     // :952-953
             float v = ((float)ky + jy) / (float)(H - 1);
             const float* cam = BATCH ? args.batch[ln.frame].cam : P.cam;

@@ -71,7 +71,7 @@ __device__ __forceinline__ bool apply_pair(Lane& ln, uint32_t* c, int slot_a, v2
 // Node-loop iterations per look at the loop's votes (1: +1.4 % time, 3: no better than 2; profiles/r03/ab_node_loop_unroll.jsonl).
 constexpr int kNodeUnroll = 2;
 
-template <int K, bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false>
+template <int K, bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false, bool SETS = false, bool MOMENTS = false>
 __device__ __forceinline__ void render_body(const RenderArgs& args) {
     const DeviceScene& S = args.scene;
     __shared__ uint2 lds_stack[kWavesPerBlock][K + 1][64];       // entry K is a dump slot, see the node visit
@@ -81,7 +81,7 @@ __device__ __forceinline__ void render_body(const RenderArgs& args) {
     const uint32_t glane = blockIdx.x * blockDim.x + threadIdx.x;
 
     __shared__ float lds_pend[kPendWords][kPendStride];
-    Lane ln;
+    LaneOf<MOMENTS> ln;
     ln.pend = &lds_pend[0][threadIdx.x];
     ln.aux = (uint32_t)lane;
     int& state = ln.state; int& cur = ln.cur; int& sp = ln.sp;
@@ -119,7 +119,7 @@ __device__ __forceinline__ void render_body(const RenderArgs& args) {
                 typedef const RenderArgs __attribute__((address_space(4)))* KernargPtr;
                 KernargPtr kp = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(kp));
-                advance_step<COUNT, CHECKED, ANYHIT, RNGMODE, PROBE, BATCH, LEAN>(ln, *(const RenderArgs*)kp, c, flags);
+                advance_step<COUNT, CHECKED, ANYHIT, RNGMODE, PROBE, BATCH, LEAN, SETS, MOMENTS>(ln, *(const RenderArgs*)kp, c, flags);
             }
         }
 
@@ -345,10 +345,13 @@ __device__ __forceinline__ void render_body(const RenderArgs& args) {
 }
 
 // LEAN (path_machine.h): the instantiation for scenes of Lambertian triangles only, chosen by the host from what upload found in the scene.  Production builds only:
-// the counting and checked builds are the general code.
-template <int K, bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool LEAN = false>
+// the counting and checked builds are the general code.  SETS, MOMENTS (path_machine.h): the rng_mode 1 launches of dsrt_render_accumulate, built beside
+// dsrt_render's own.
+template <int K, bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool LEAN = false, bool SETS = false, bool MOMENTS = false>
 __global__ void __launch_bounds__(64 * kWavesPerBlock) DSRT_WAVES_ATTR dsrt_render_kernel(const RenderArgs args) {
-    render_body<K, COUNT, CHECKED, ANYHIT, RNGMODE, false, false, LEAN>(args);
+    static_assert(!SETS || RNGMODE == 1, "sample sets are rng_mode 1's");
+    static_assert(!MOMENTS || SETS, "second moments are summed by accumulate launches only");
+    render_body<K, COUNT, CHECKED, ANYHIT, RNGMODE, false, false, LEAN, SETS, MOMENTS>(args);
 }
 
 // Batch launch: many frames of one scene as one pool of work (path_machine.h, ST_FETCH).
@@ -658,37 +661,52 @@ hipError_t launch_devkat(int fn, const float* in, float* out, int n, hipStream_t
 
 #endif  // !DSRT_DEVICE_LIBM
 
-// rng_mode 1: a pixel's samples were summed as integers in units of 2^-20 (path_machine.h, end_sample); here the mean, the
-// reference's tone map and the 8-bit store (:1003-1030).  Pixels nobody sampled (culled tiles, padding) hold zero sums: black.
-__global__ void dsrt_resolve_kernel(const unsigned long long* __restrict__ sums, int spp, float inv_gamma, size_t n_pixels,
-                                    uint8_t* __restrict__ out_rgb8, float* __restrict__ out_f32) {
+// rng_mode 1: a pixel's samples were summed as integers in units of 2^-20 (path_machine.h, end_sample); here the mean over the
+// samples_done samples summed, the reference's tone map and the 8-bit store (:1003-1030).  Pixels nobody sampled (culled tiles, padding)
+// hold zero sums: black.  With sums_sq (dsrt_resolve_accumulated, include/dsrt.h) also the variance of the mean, in double, in exactly
+// the order the header writes down -- correctly rounded operations only, so that a CPU reproduces it bit for bit.
+__global__ void dsrt_resolve_kernel(const unsigned long long* __restrict__ sums, int samples_done, float inv_gamma, size_t n_pixels,
+                                    uint8_t* __restrict__ out_rgb8, float* __restrict__ out_f32,
+                                    const unsigned long long* __restrict__ sums_sq, float* __restrict__ out_var) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels) return;
-    const double unit = 1.0 / 1048576.0 / (double)spp;
+    if (out_var) {
+        const double n = (double)samples_done;
+        for (int ch = 0; ch < 3; ++ch) {
+            const double s = (double)sums[i * 3 + ch] * (1.0 / 1048576.0), s2 = (double)sums_sq[i * 3 + ch] * (1.0 / 1048576.0);
+            double v = (s2 - s * s / n) / (n - 1.0);
+            v = v > 0.0 ? v : 0.0;
+            out_var[i * 3 + ch] = (float)(v / n);
+        }
+    }
+    if (!out_rgb8 && !out_f32) return;
+    const double unit = 1.0 / 1048576.0 / (double)samples_done;
     F3 col = mk((float)((double)sums[i * 3 + 0] * unit), (float)((double)sums[i * 3 + 1] * unit), (float)((double)sums[i * 3 + 2] * unit));
     col = mk(fmaxf(col.x, 0.0f), fmaxf(col.y, 0.0f), fmaxf(col.z, 0.0f));
     col = mk(fminf(col.x, 10.0f), fminf(col.y, 10.0f), fminf(col.z, 10.0f));
     col = mk(dsrt_powf(col.x, inv_gamma), dsrt_powf(col.y, inv_gamma), dsrt_powf(col.z, inv_gamma));
     col = clamp01(col);
-    out_rgb8[i * 3 + 0] = (unsigned char)(255.99f * col.x);
-    out_rgb8[i * 3 + 1] = (unsigned char)(255.99f * col.y);
-    out_rgb8[i * 3 + 2] = (unsigned char)(255.99f * col.z);
+    if (out_rgb8) {
+        out_rgb8[i * 3 + 0] = (unsigned char)(255.99f * col.x);
+        out_rgb8[i * 3 + 1] = (unsigned char)(255.99f * col.y);
+        out_rgb8[i * 3 + 2] = (unsigned char)(255.99f * col.z);
+    }
     if (out_f32) { out_f32[i * 3 + 0] = col.x; out_f32[i * 3 + 1] = col.y; out_f32[i * 3 + 2] = col.z; }
 }
 
 // ---- launchers (called from device_api.hip) -----------------------------------------------------------
-template <int K, int RNGMODE>
+template <int K, int RNGMODE, bool SETS = false, bool MOMENTS = false>
 static hipError_t launch_k(const RenderArgs& a, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream) {
     const dim3 grid(blocks), block(64 * kWavesPerBlock);
     if (!count && !checked && lean) {
-        hipLaunchKernelGGL((dsrt_render_kernel<K, false, false, true, RNGMODE, true>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((dsrt_render_kernel<K, false, false, true, RNGMODE, true, SETS, MOMENTS>), grid, block, 0, stream, a);
     } else if (count) {
-        if (anyhit) hipLaunchKernelGGL((dsrt_render_kernel<K, true, true, true, RNGMODE>), grid, block, 0, stream, a);
-        else        hipLaunchKernelGGL((dsrt_render_kernel<K, true, true, false, RNGMODE>), grid, block, 0, stream, a);
+        if (anyhit) hipLaunchKernelGGL((dsrt_render_kernel<K, true, true, true, RNGMODE, false, SETS, MOMENTS>), grid, block, 0, stream, a);
+        else        hipLaunchKernelGGL((dsrt_render_kernel<K, true, true, false, RNGMODE, false, SETS, MOMENTS>), grid, block, 0, stream, a);
     } else if (checked) {
-        hipLaunchKernelGGL((dsrt_render_kernel<K, false, true, true, RNGMODE>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((dsrt_render_kernel<K, false, true, true, RNGMODE, false, SETS, MOMENTS>), grid, block, 0, stream, a);
     } else {
-        hipLaunchKernelGGL((dsrt_render_kernel<K, false, false, true, RNGMODE>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((dsrt_render_kernel<K, false, false, true, RNGMODE, false, SETS, MOMENTS>), grid, block, 0, stream, a);
     }
     return hipGetLastError();
 }
@@ -716,15 +734,22 @@ hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream) {
+// sets: the SETS instantiations (rng_mode 1, dsrt_render_accumulate); moments: with MOMENTS as well (a.accum_sq is set)
+hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, bool sets, bool moments,
+                         hipStream_t stream) {
     if (lds_entries != 8) return hipErrorInvalidValue;     // the only short-stack size built
-    if (rng_mode == 0) return launch_k<8, 0>(a, blocks, count, checked, anyhit, lean, stream);
-    if (rng_mode == 1) return launch_k<8, 1>(a, blocks, count, checked, anyhit, lean, stream);
+    if (rng_mode == 0 && !sets && !moments) return launch_k<8, 0>(a, blocks, count, checked, anyhit, lean, stream);
+    if (rng_mode == 1 && !sets && !moments) return launch_k<8, 1>(a, blocks, count, checked, anyhit, lean, stream);
+    if (rng_mode == 1 && sets && !moments) return launch_k<8, 1, true>(a, blocks, count, checked, anyhit, lean, stream);
+    if (rng_mode == 1 && sets && moments) return launch_k<8, 1, true, true>(a, blocks, count, checked, anyhit, lean, stream);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_resolve(const unsigned long long* sums, int spp, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32, hipStream_t stream) {
-    hipLaunchKernelGGL(dsrt_resolve_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, spp, inv_gamma, n_pixels, out_rgb8, out_f32);
+hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream) {
+    if (!n_pixels) return hipSuccess;
+    hipLaunchKernelGGL(dsrt_resolve_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, samples_done, inv_gamma, n_pixels, out_rgb8, out_f32,
+                       sums_sq, out_var);
     return hipGetLastError();
 }
 

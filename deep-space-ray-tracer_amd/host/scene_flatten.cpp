@@ -154,6 +154,7 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_GBUFFER: return sizeof(DsrtGBuffer);
         case DSRT_SIZEOF_RAYS: return sizeof(DsrtRays);
         case DSRT_SIZEOF_RAY_HITS: return sizeof(DsrtRayHits);
+        case DSRT_SIZEOF_ACCUM: return sizeof(DsrtAccum);
         default: return 0;
     }
 }

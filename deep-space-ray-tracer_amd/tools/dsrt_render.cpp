@@ -11,6 +11,9 @@
 //   * PPM (or PNG with --png): there is no ImageMagick shell-out (:28-36) and no upscaling step (:438-447);
 //   * --gbuffer also writes each frame's ground truth next to it (include/dsrt.h, dsrt_render_gbuffer): <frame>_range.pfm, <frame>_normal.pfm,
 //     <frame>_mask.pgm (255 where the centre ray hits) and <frame>_sunlit.pgm (255 where that hit sees the Sun).
+//   * rng_mode 1 only: --passes P renders each frame as P interleaved sample sets and writes <frame>_pass<p>of<P> after each (a preview that
+//     sharpens), then <frame> itself -- the last pass's image, byte for byte the one-launch image; --variance also writes the variance of every
+//     pixel's mean as <frame>_var.pfm (include/dsrt.h, SAMPLE SETS).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,8 +40,8 @@ static int fail(const char* what) {
 
 int main(int argc, char** argv) {
     std::string pose_file, out_dir = "output", obj;
-    int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0;
-    bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false;
+    int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0, passes = 0;
+    bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -62,10 +65,16 @@ int main(int argc, char** argv) {
         else if (a == "--strict-textures") strict_textures = true;  // refuse a mesh whose texture maps this library cannot decode (include/dsrt.h)
         else if (a == "--gbuffer") gbuffer = true;                  // ground-truth channels of every frame next to its image (include/dsrt.h, dsrt_render_gbuffer)
         else if (a == "--png") png = true;                          // frames as PNG instead of PPM (the reference converts with ImageMagick)
+        else if (a == "--passes") passes = std::atoi(next("--passes"));   // rng_mode 1: each frame as P interleaved sample sets, an image after each (include/dsrt.h, SAMPLE SETS)
+        else if (a == "--variance") variance = true;                // rng_mode 1: also the variance of each pixel's mean, <frame>_var.pfm
         else if (a == "--upscale") std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
+    if ((passes != 0 || variance) && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --passes and --variance need --rng-mode 1 (or --fast)\n"); return 2; }
+    if (passes < 0 || passes > std::max(spp, 1)) { std::fprintf(stderr, "dsrt_render: --passes must be between 1 and --spp\n"); return 2; }
+    if (variance && spp < 2) { std::fprintf(stderr, "dsrt_render: --variance needs --spp 2 or more\n"); return 2; }
+    if ((passes != 0 || variance) && gbuffer) { std::fprintf(stderr, "dsrt_render: --gbuffer does not combine with --passes / --variance\n"); return 2; }
     mkdir(out_dir.c_str(), 0777);
 
     std::vector<DsrtPose> poses;
@@ -136,6 +145,46 @@ int main(int argc, char** argv) {
     std::memset(&d, 0, sizeof d);
     d.width = width; d.height = height; d.spp = spp; d.max_depth = depth; d.gamma = 2.0f; d.seed = 1337; d.rng_mode = rng_mode; d.math_mode = math_mode;
     const size_t image_bytes = (size_t)width * height * 3;
+    if (passes != 0 || variance) {
+        // Each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
+        // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).
+        const int P = passes > 0 ? passes : 1;
+        std::vector<uint64_t> sum(image_bytes), sq(variance ? image_bytes : 0);
+        std::vector<uint8_t> img(image_bytes);
+        std::vector<float> var(variance ? image_bytes : 0);
+        const DsrtAccum acc{sum.data(), variance ? sq.data() : nullptr};
+        for (size_t q = 0; q < ids.size(); ++q) {
+            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
+            std::fill(sum.begin(), sum.end(), 0ull);
+            std::fill(sq.begin(), sq.end(), 0ull);
+            int done = 0;
+            char stem[64];
+            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
+            const std::string base = out_dir + stem, ext = png ? ".png" : ".ppm";
+            for (int p = 0; p < P; ++p) {
+                const int count = (spp - p + P - 1) / P;
+                DsrtStats st;
+                if (dsrt_render_accumulate_to_host(ctx, &d, p, count, P, &acc, &st) != DSRT_OK) return fail("rendering a pass");
+                done += count;
+                if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, done, img.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving a pass");
+                const std::string path = p + 1 < P || passes > 0 ? base + "_pass" + std::to_string(p + 1) + "of" + std::to_string(P) + ext : base + ext;
+                if ((png ? dsrt_write_png(path.c_str(), img.data(), width, height) : dsrt_write_ppm(path.c_str(), img.data(), width, height)) != DSRT_OK) return fail("writing the frame");
+                std::printf("pass %d/%d: %d samples per pixel, kernel %.3f ms; saved %s\n", p + 1, P, done, st.kernel_ms, path.c_str());
+            }
+            if (passes > 0 && (png ? dsrt_write_png((base + ext).c_str(), img.data(), width, height) : dsrt_write_ppm((base + ext).c_str(), img.data(), width, height)) != DSRT_OK)
+                return fail("writing the frame");
+            if (variance) {
+                if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, done, nullptr, nullptr, var.data()) != DSRT_OK) return fail("resolving the variance");
+                if (dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
+                std::printf("Saved %s_var.pfm\n", base.c_str());
+            }
+            std::printf("Saved %s%s\n", base.c_str(), ext.c_str());
+        }
+        dsrt_ctx_destroy(ctx);
+        dsrt_host_scene_destroy(hs);
+        std::printf("Done.\n");
+        return 0;
+    }
     size_t per_launch = 32;
     while (per_launch > 1 && (unsigned long long)per_launch * width * height * (rng_mode == 1 ? 16ull : 1ull) >= (1ull << 32)) per_launch /= 2;
     std::vector<uint8_t> fb(image_bytes * std::min(per_launch, std::max<size_t>(ids.size(), 1)));

@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -50,6 +50,7 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_GBUFFER     6
 #define DSRT_SIZEOF_RAYS        7
 #define DSRT_SIZEOF_RAY_HITS    8
+#define DSRT_SIZEOF_ACCUM       9
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -249,7 +250,20 @@ typedef struct DsrtRenderDesc {
                                          - a pixel's sum over its spp samples is a 64-bit integer per channel;
                                          - its mean is (float)((double)sum * (1.0 / 2^20 / spp)), computed in double and converted to float once;
                                          - the tone map and the 8-bit store are mode 0's (clamp to [0,10], pow(1/gamma), clamp to [0,1], 255.99 * c);
-                                         - pixels of culled tiles are black (all-zero bytes and +0.0f), which is what they render to anyway */
+                                         - pixels of culled tiles are black (all-zero bytes and +0.0f), which is what they render to anyway.
+                                       SAMPLE SETS (dsrt_render_accumulate below): sample k of a pixel is defined by (seed, pixel, spp, k) alone -- sub-sequence
+                                       (x + y*W)*spp + k, jitter (k + r)/spp with spp the PLANNED count -- so it does not matter which launch draws it.  A launch
+                                       with (first, count, stride) renders, for every pixel, the set {first + j*stride : 0 <= j < count} of a frame planned at spp
+                                       samples and ADDS its sums to the caller's; the sums over disjoint sets add up to the sum over their union, exactly, and
+                                       resolved at samples_done = spp the union of sets that cover [0, spp) is dsrt_render's image byte for byte.
+                                         - a partial set is a valid image, stratified differently: the jitter keeps sample k in the k-th strip of its pixel, so a
+                                           contiguous [0, n) covers only part of every pixel.  Interleaved passes (first = p, stride = P, p = 0 .. P-1) are the form
+                                           for previews: after pass p every pixel has samples spread over its whole area;
+                                         - second moment (optional): per sample and channel, with q the quantised value above, sq = (uint32_t)(((uint64_t)q*q + 2^19) >> 20),
+                                           the squared clamped sample in units of 2^-20, rounded; summed as a 64-bit integer like q;
+                                         - resolve with n = samples_done: the mean, tone map and bytes are the ones above with spp replaced by n; the variance of the
+                                           mean, per pixel and channel, in double and in exactly this order (correctly rounded operations only, no sqrt):
+                                             s = (double)S * 2^-20;  s2 = (double)S2 * 2^-20;  v = (s2 - s * s / n) / (n - 1);  v = v > 0 ? v : 0;  out = (float)(v / n) */
     int      tile_size;             /* screen-tile edge in pixels, multiple of 8; 0 -> 8          */
     int      shard_rank;            /* this process renders tiles t with t % shard_count == shard_rank */
     int      shard_count;           /* 0 or 1 -> whole image                                      */
@@ -459,6 +473,32 @@ typedef struct DsrtRayHits {         /* every channel optional (NULL = not writt
 int dsrt_trace_rays(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, void* stream, DsrtStats* stats);
 /* The same from HOST buffers into HOST buffers, synchronously. */
 int dsrt_trace_rays_to_host(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, DsrtStats* stats);
+
+/*
+ * SAMPLE SETS (rng_mode 1; definitions with DsrtRenderDesc.rng_mode above): progressive preview, time-budgeted rendering, sample sharding between contexts,
+ * streams or devices, and a per-pixel noise estimate.  The caller owns the sums; every accumulate launch ADDS to them.
+ *   dsrt_render_accumulate: renders {first + j*stride : 0 <= j < count} of every pixel of the frame `desc` plans (desc->spp samples), with the context's camera
+ *     and sun, into acc->sum (and acc->sum_sq when it is not NULL: the kernel that also sums squared samples is used only then).  Culled tiles get no additions.
+ *     Asynchronous on `stream` unless `stats` is given (then as dsrt_render: synchronises and fills it; `samples` counts this launch's samples in a counting
+ *     build).  collect_counters, checked, math_mode, tune and the certified second tree work as in dsrt_render.
+ *     DSRT_ERR_INVALID: a NULL ctx, desc, acc or acc->sum; rng_mode != 1; shard_count > 1; first < 0, count < 1, stride < 1, first + (count-1)*stride >= spp.
+ *     DSRT_ERR_NO_SCENE before an upload.  A refused call touches no buffer.
+ *   dsrt_resolve_accumulated: the image of the sums after `samples_done` samples per pixel (rgb8, f32 as dsrt_render's; either may be NULL) and, if
+ *     d_var_of_mean is not NULL, the variance of the mean (width*height*3 floats, needs acc->sum_sq and samples_done >= 2).  Waits for the context's last launch.
+ *     DSRT_ERR_INVALID: a NULL ctx, desc, acc or acc->sum; rng_mode != 1; shard_count > 1; samples_done < 1; no output; the variance without sum_sq or with
+ *     samples_done < 2.  Needs no scene.
+ * The _to_host forms take HOST buffers (sums in and out, images out) and are synchronous.
+ */
+typedef struct DsrtAccum {          /* DEVICE buffers (HOST for the _to_host forms), width*height*3 uint64 each, image order (top row first), as dsrt_render's */
+    uint64_t* sum;                  /* required: per-channel sums of q (units of 2^-20); the caller zeroes it once, every launch ADDS */
+    uint64_t* sum_sq;               /* optional: per-channel sums of sq as defined above; NULL = the second moment is not summed */
+} DsrtAccum;
+int dsrt_render_accumulate(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, void* stream, DsrtStats* stats);
+int dsrt_render_accumulate_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, DsrtStats* stats);
+int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, uint8_t* d_rgb8, float* d_f32,
+                             float* d_var_of_mean, void* stream);
+int dsrt_resolve_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, uint8_t* h_rgb8, float* h_f32,
+                                     float* h_var_of_mean);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
