@@ -22,37 +22,10 @@
 #include "../../include/dsrt.h"
 #include "../host/host_internal.hpp"
 #include "device_layout.h"
+#include "launchers.h"
 
 namespace dsrt {
-hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, bool sets, bool moments,
-                         hipStream_t stream);
-hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
-hipError_t launch_render_batch(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
-hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
-                              uint32_t* total_items, hipStream_t stream);
-hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
-                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
-hipError_t launch_philox(unsigned long long seed, unsigned long long sub, int n, uint32_t* ours, uint32_t* theirs, hipStream_t stream);
-hipError_t launch_deinterleave(const uint8_t* gathered, uint8_t* image, int W, int H, int tile, int tiles_x, int shard_count,
-                               size_t shard_stride_bytes, hipStream_t stream);
-hipError_t launch_math(int fn, const float* x, float y, float* out, int n, hipStream_t stream);
-hipError_t launch_devkat(int fn, const float* in, float* out, int n, hipStream_t stream);
-int kernel_waves_per_block();
-hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_t* cost, uint32_t* order, uint32_t* sched, uint32_t items_per_pixel,
-                             uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch = nullptr, uint32_t frames = 1, uint32_t stride = 0);
-hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream);
-hipError_t launch_content_hash(const uint32_t* words, size_t n_words, uint64_t salt, uint64_t* d_hash2, hipStream_t stream);
-hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream);          // gbuffer_kernel.hip
-hipError_t launch_raycast(const RaycastArgs& a, bool any_hit, int blocks, hipStream_t stream);                  // raycast_kernel.hip
-// DsrtRenderDesc.math_mode 1: the same kernels compiled against the device math library's sinf / cosf / powf (render_kernel.hip, second compilation)
-namespace devlibm {
-hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, bool sets, bool moments,
-                         hipStream_t stream);
-hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
-hipError_t launch_render_batch(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
-hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
-                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
-}  // namespace devlibm
+const RenderLaunchers& render_launchers(bool device_libm) { return device_libm ? devlibm::compiled_render_launchers() : compiled_render_launchers(); }
 }  // namespace dsrt
 
 using namespace dsrt;
@@ -118,6 +91,14 @@ struct PackedScene {
 };
 
 float4 as_f4(float a, float b, float c, float d) { return make_float4(a, b, c, d); }
+
+// The 12-float camera block of FrameParams / BatchFrame / GBufferArgs (device_layout.h, kCamOrigin ...).
+void pack_camera(const GPUCamera& c, float (&cam)[12]) {
+    const float cam12[12] = {c.origin.x, c.origin.y, c.origin.z, c.lower_left_corner.x, c.lower_left_corner.y, c.lower_left_corner.z,
+                             c.horizontal.x, c.horizontal.y, c.horizontal.z, c.vertical.x, c.vertical.y, c.vertical.z};
+    std::memcpy(cam, cam12, sizeof cam12);
+}
+
 float bits(int i) { float f; std::memcpy(&f, &i, 4); return f; }
 
 // Leaf size of the certified second tree (its structure is free: any tree over the reachable triangles will do).  Development override: DSRT_SECOND_TREE_LEAF=1..7.
@@ -615,7 +596,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
     if (desc->rng_mode != 0 && desc->rng_mode != 1) { set_error("dsrt_render: rng_mode must be 0 (reference LCG stream per pixel) or 1 (Philox4x32-10 stream per sample)"); return DSRT_ERR_INVALID; }
     if (desc->math_mode != 0 && desc->math_mode != 1) { set_error("dsrt_render: math_mode must be 0 (deterministic sin / cos / pow shared with the CPU oracle) or 1 (the device math library's)"); return DSRT_ERR_INVALID; }
-    const bool libm = desc->math_mode == 1;
+    const RenderLaunchers& rl = render_launchers(desc->math_mode == 1);
     const bool lean = ctx->scene->lean && !(experiment_word() & (1u << 24));
     if (desc->tune[3] & ~DSRT_TUNE_FLAG_MASK) { set_error("dsrt_render: tune[3] has bits set that this ABI version does not define (DSRT_TUNE_* in include/dsrt.h)"); return DSRT_ERR_INVALID; }
     const uint32_t flags = (uint32_t)desc->tune[3];
@@ -631,13 +612,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     std::memset(&a, 0, sizeof a);
     a.scene = sc.view;
     FrameParams& f = a.frame;
-    const GPUCamera& c = ctx->camera;
-    {
-        const float cam12[12] = {c.origin.x, c.origin.y, c.origin.z, c.lower_left_corner.x, c.lower_left_corner.y, c.lower_left_corner.z,
-                                 c.horizontal.x, c.horizontal.y, c.horizontal.z, c.vertical.x, c.vertical.y, c.vertical.z};
-        static_assert(sizeof cam12 == sizeof f.cam, "camera block");
-        std::memcpy(f.cam, cam12, sizeof cam12);
-    }
+    pack_camera(ctx->camera, f.cam);
     f.sun_dir[0] = ctx->sun_dir.x; f.sun_dir[1] = ctx->sun_dir.y; f.sun_dir[2] = ctx->sun_dir.z;
     f.sun_radiance[0] = ctx->sun_radiance.x; f.sun_radiance[1] = ctx->sun_radiance.y; f.sun_radiance[2] = ctx->sun_radiance.z;
     f.sun_enabled = ctx->sun_enabled;
@@ -720,7 +695,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     // LDS short-stack: 8 entries per lane (what fits beside the tree top and the continuation strip); deeper entries spill.
     const int K = 8;
     if (desc->stack_entries != 0 && desc->stack_entries != 8) { set_error("dsrt_render: stack_entries must be 0 or 8"); return DSRT_ERR_INVALID; }
-    const int threads_per_block = 64 * kernel_waves_per_block();
+    const int threads_per_block = 64 * kWavesPerBlock;
     const int resident_blocks = ctx->num_cus * 4;                         // 4 waves per SIMD = 4 workgroups of 4 waves per CU (render_kernel.hip)
     int blocks = resident_blocks;                                         // persistent: exactly the resident set
     if ((xp >> 20) & 7u) blocks = std::max(1, resident_blocks >> ((xp >> 20) & 7u));     // experiment: a fraction of it (frames that overlap)
@@ -792,12 +767,8 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         if (ctx->batch_table.n < 2 * (size_t)frames) { int rc = ctx->batch_table.alloc(2 * (size_t)frames); if (rc) return rc; }
         ctx->batch_host.assign(2 * (size_t)frames, BatchFrame{});
         for (int i = 0; i < frames; ++i) {
-            const GPUCamera& bc = batch->cameras[i];
             BatchFrame& e = ctx->batch_host[(size_t)i];
-            const float cam12[12] = {bc.origin.x, bc.origin.y, bc.origin.z, bc.lower_left_corner.x, bc.lower_left_corner.y, bc.lower_left_corner.z,
-                                     bc.horizontal.x, bc.horizontal.y, bc.horizontal.z, bc.vertical.x, bc.vertical.y, bc.vertical.z};
-            static_assert(sizeof cam12 == sizeof e.cam, "camera block");
-            std::memcpy(e.cam, cam12, sizeof cam12);
+            pack_camera(batch->cameras[i], e.cam);
             e.sun_dir[0] = batch->sun_dirs[i].x; e.sun_dir[1] = batch->sun_dirs[i].y; e.sun_dir[2] = batch->sun_dirs[i].z;
             e.order_base = (uint32_t)(pre_stride * (size_t)i);
             e.image_slot = (uint32_t)i;
@@ -823,7 +794,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
                 HIP_TRY(hipMemsetAsync(ctx->probe_queue.p, 0, 1024 * sizeof(uint32_t), stream));
                 HIP_TRY(hipMemsetAsync(ctx->tile_work.p, 0, (size_t)t.mine * sizeof(uint32_t), stream));
                 HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
-                HIP_TRY(libm ? devlibm::launch_probe(pa, blocks, lean, stream) : launch_probe(pa, blocks, lean, stream));
+                HIP_TRY(rl.launch_probe(pa, blocks, lean, stream));
                 HIP_TRY(launch_tile_reorder(ctx->tile_work.p, ctx->tile_order.p + pre_stride * (size_t)i, ctx->tile_tmp.p, sched + pre_stride * (size_t)i, stream));
             }
             HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
@@ -860,7 +831,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
             HIP_TRY(hipMemsetAsync(ctx->probe_queue.p, 0, 1024 * sizeof(uint32_t), stream));
             pa.probe_queue = ctx->probe_queue.p;
             HIP_TRY(hipMemsetAsync(ctx->tile_work.p, 0, (size_t)t.mine * sizeof(uint32_t), stream));
-            HIP_TRY(libm ? devlibm::launch_probe(pa, blocks, lean, stream) : launch_probe(pa, blocks, lean, stream));
+            HIP_TRY(rl.launch_probe(pa, blocks, lean, stream));
             HIP_TRY(launch_tile_reorder(ctx->tile_work.p, ctx->tile_order.p, ctx->tile_tmp.p, sched, stream));
             HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
         }
@@ -872,15 +843,15 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     }
     if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
     const bool count = desc->collect_counters != 0;
-    if (batch) HIP_TRY(libm ? devlibm::launch_render_batch(a, desc->rng_mode, blocks, lean, stream) : launch_render_batch(a, desc->rng_mode, blocks, lean, stream));
+    if (batch) HIP_TRY(rl.launch_render_batch(a, desc->rng_mode, blocks, lean, stream));
     else {
-        const bool sets = acc != nullptr, moments = acc && acc->sum_sq;
-        if (libm) HIP_TRY(devlibm::launch_render(a, K, desc->rng_mode, blocks, count, count || desc->checked != 0, desc->collect_counters != 2, lean, sets, moments, stream));
-        else HIP_TRY(launch_render(a, K, desc->rng_mode, blocks, count, count || desc->checked != 0, desc->collect_counters != 2, lean, sets, moments, stream));
+        RenderVariant v{};
+        v.rng_mode = desc->rng_mode;
+        v.count = count; v.checked = count || desc->checked != 0; v.anyhit = desc->collect_counters != 2;
+        v.lean = lean; v.sets = acc != nullptr; v.moments = acc && acc->sum_sq;
+        HIP_TRY(rl.launch_render(a, v, blocks, stream));
     }
-    if (desc->rng_mode == 1 && !acc)
-        HIP_TRY(libm ? devlibm::launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, nullptr, nullptr, stream)
-                     : launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, nullptr, nullptr, stream));
+    if (desc->rng_mode == 1 && !acc) HIP_TRY(rl.launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, nullptr, nullptr, stream));
     HIP_TRY(hipEventRecord(ctx->done, stream));
     ctx->done_valid = true;
     if (stats) {
@@ -1085,8 +1056,7 @@ int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const
     const size_t px = (size_t)desc->width * desc->height;
     const unsigned long long* sum = (const unsigned long long*)acc->sum;
     const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;
-    HIP_TRY(desc->math_mode == 1 ? devlibm::launch_resolve(sum, samples_done, inv_gamma, px, d_rgb8, d_f32, sq, d_var_of_mean, stream)
-                                 : launch_resolve(sum, samples_done, inv_gamma, px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
+    HIP_TRY(render_launchers(desc->math_mode == 1).launch_resolve(sum, samples_done, inv_gamma, px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
     return DSRT_OK;
     });
 }
@@ -1132,10 +1102,7 @@ int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const Dsrt
     std::memset(&a, 0, sizeof a);
     a.scene = sc.view;
     const GPUCamera& c = ctx->camera;
-    const float cam12[12] = {c.origin.x, c.origin.y, c.origin.z, c.lower_left_corner.x, c.lower_left_corner.y, c.lower_left_corner.z,
-                             c.horizontal.x, c.horizontal.y, c.horizontal.z, c.vertical.x, c.vertical.y, c.vertical.z};
-    static_assert(sizeof cam12 == sizeof a.cam, "camera block");
-    std::memcpy(a.cam, cam12, sizeof cam12);
+    pack_camera(c, a.cam);
     a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
     a.sun_dir[0] = ctx->sun_dir.x; a.sun_dir[1] = ctx->sun_dir.y; a.sun_dir[2] = ctx->sun_dir.z;
     a.sun_enabled = ctx->sun_enabled;

@@ -38,6 +38,8 @@
 
 namespace dsrt {
 
+constexpr int kWavesPerBlock = 4;          // waves in a workgroup of the render, batch and probe kernels (render_kernel.hip)
+
 constexpr int kLeafBit = (int)0x80000000u;
 // Node references as a lane's `cur` holds them.  Every sentinel and every class boundary is an INLINE constant of the ISA (integers -16 .. 64 cost no
 // register and no literal): the traversal loop's compares and selects name them directly, where 0x7FFFFFFE cost a move per iteration and a register.

@@ -12,6 +12,7 @@
 //   * Second phase of the same launch: the lanes whose hit faces the Sun trace the shadow ray as an any-hit walk.  It stops at the first accepted
 //     triangle: until then it performs exactly the closest-hit walk's steps (closest is still 1e9 in both), so "blocked" is scene_hit's boolean.
 //   * No sinf / cosf / powf on this path: compiled once, whatever DsrtRenderDesc.math_mode says.
+#include "launchers.h"
 #include "walk_common.h"
 
 namespace dsrt {

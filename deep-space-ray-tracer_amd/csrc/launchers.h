@@ -1,0 +1,45 @@
+// launchers.h -- the one declaration of every host-side launcher that crosses a translation unit.  device_api.hip calls them; every .hip file that defines
+// one includes this header too, so a definition is checked against its declaration where it is compiled.
+#pragma once
+
+#include "device_layout.h"
+
+namespace dsrt {
+
+// Which instantiation of dsrt_render_kernel a launch wants (render_kernel.hip: launch_render picks it and refuses what is not built).
+//   count, checked: the counting / checked builds (never LEAN)      anyhit: shadow rays stop at the first accepted triangle
+//   lean: a scene of Lambertian triangles only (path_machine.h)     sets, moments: the rng_mode 1 launches of dsrt_render_accumulate
+struct RenderVariant { int rng_mode; bool count, checked, anyhit, lean, sets, moments; };
+
+// The launchers of render_kernel.hip.  That file is compiled twice -- with the deterministic sin / cos / pow shared with the CPU oracle, and against the device
+// math library's (DsrtRenderDesc.math_mode 1, namespace devlibm) -- and each compilation exports its four launchers as one table.
+struct RenderLaunchers {
+    hipError_t (*launch_render)(const RenderArgs& a, const RenderVariant& v, int blocks, hipStream_t stream);
+    hipError_t (*launch_render_batch)(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
+    hipError_t (*launch_probe)(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
+    hipError_t (*launch_resolve)(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                                 const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
+};
+const RenderLaunchers& compiled_render_launchers();
+namespace devlibm { const RenderLaunchers& compiled_render_launchers(); }
+const RenderLaunchers& render_launchers(bool device_libm);          // device_api.hip: the table of one of the two
+
+// render_kernel.hip, first compilation only: the scheduling pre-pass ...
+hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_t* cost, uint32_t* order, uint32_t* sched, uint32_t items_per_pixel,
+                             uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch = nullptr, uint32_t frames = 1, uint32_t stride = 0);
+hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream);
+hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
+                              uint32_t* total_items, hipStream_t stream);
+
+// ... tile de-interleave, the drop-in layer's content hash and the self-test hooks
+hipError_t launch_deinterleave(const uint8_t* gathered, uint8_t* image, int W, int H, int tile, int tiles_x, int shard_count,
+                               size_t shard_stride_bytes, hipStream_t stream);
+hipError_t launch_content_hash(const uint32_t* words, size_t n_words, uint64_t salt, uint64_t* d_hash2, hipStream_t stream);
+hipError_t launch_math(int fn, const float* x, float y, float* out, int n, hipStream_t stream);
+hipError_t launch_devkat(int fn, const float* in, float* out, int n, hipStream_t stream);
+hipError_t launch_philox(unsigned long long seed, unsigned long long sub, int n, uint32_t* ours, uint32_t* theirs, hipStream_t stream);
+
+hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream);                                  // gbuffer_kernel.hip
+hipError_t launch_raycast(const RaycastArgs& a, bool any_hit, int blocks, hipStream_t stream);                   // raycast_kernel.hip
+
+}  // namespace dsrt

@@ -10,6 +10,7 @@
 //     by DeviceScene.stack_need: no private arrays, no scratch.
 //   * A lane-refill form (persistent waves that hand finished lanes new ray indices) was built and measured: +13 % on incoherent rays, -20 % on coherent
 //     ones, so it is not kept.
+#include "launchers.h"
 #include "walk_common.h"
 
 namespace dsrt {

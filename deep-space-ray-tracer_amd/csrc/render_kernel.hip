@@ -29,6 +29,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no fast-math: IEEE div/sqrt are part of the contract).
 #include <rocrand/rocrand_kernel.h>
 
+#include "launchers.h"
 #include "path_machine.h"
 #include "walk_common.h"
 
@@ -39,7 +40,6 @@ namespace dsrt {
 // (pre-pass, table, de-interleave, hash, test hooks) is compiled once, in the first pass.
 namespace devlibm {
 #endif
-constexpr int kWavesPerBlock = 4;
 // Register budget: 4 waves per SIMD (= 4 blocks per CU, which is also what the blocks' 31 KB of LDS allow).
 #ifndef DSRT_WAVES_ATTR
 #define DSRT_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(4)))
@@ -600,7 +600,7 @@ hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* 
 }
 
 hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_t* cost, uint32_t* order, uint32_t* sched, uint32_t items_per_pixel,
-                             uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch = nullptr, uint32_t frames = 1, uint32_t stride = 0) {
+                             uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch, uint32_t frames, uint32_t stride) {
     const uint32_t waves = (uint32_t)P.local_tiles * (uint32_t)((P.tile >> 3) * (P.tile >> 3));
     for (uint32_t f = 0; f < frames; ++f) {                           // (the cost words only: the arrays carry the sched words behind them)
         hipError_t e = hipMemsetAsync(cost + (size_t)f * stride, 0, (size_t)P.local_tiles * sizeof(uint32_t), stream);
@@ -694,7 +694,7 @@ __global__ void dsrt_resolve_kernel(const unsigned long long* __restrict__ sums,
     if (out_f32) { out_f32[i * 3 + 0] = col.x; out_f32[i * 3 + 1] = col.y; out_f32[i * 3 + 2] = col.z; }
 }
 
-// ---- launchers (called from device_api.hip) -----------------------------------------------------------
+// ---- launchers (declared in launchers.h; the four of the twice-compiled kernels go out as this compilation's table) -----
 template <int K, int RNGMODE, bool SETS = false, bool MOMENTS = false>
 static hipError_t launch_k(const RenderArgs& a, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream) {
     const dim3 grid(blocks), block(64 * kWavesPerBlock);
@@ -711,7 +711,7 @@ static hipError_t launch_k(const RenderArgs& a, int blocks, bool count, bool che
     return hipGetLastError();
 }
 
-hipError_t launch_render_batch(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream) {
+static hipError_t launch_render_batch(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream) {
     const dim3 grid(blocks), block(64 * kWavesPerBlock);
     if (rng_mode == 0) { if (lean) hipLaunchKernelGGL((dsrt_render_batch_kernel<0, true>), grid, block, 0, stream, a); else hipLaunchKernelGGL((dsrt_render_batch_kernel<0, false>), grid, block, 0, stream, a); }
     else if (rng_mode == 1) { if (lean) hipLaunchKernelGGL((dsrt_render_batch_kernel<1, true>), grid, block, 0, stream, a); else hipLaunchKernelGGL((dsrt_render_batch_kernel<1, false>), grid, block, 0, stream, a); }
@@ -728,29 +728,33 @@ hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t
 
 #endif
 
-hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t stream) {
+static hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipStream_t stream) {
     if (lean) hipLaunchKernelGGL(dsrt_probe_kernel<true>, dim3(blocks), dim3(64 * kWavesPerBlock), 0, stream, a);
     else hipLaunchKernelGGL(dsrt_probe_kernel<false>, dim3(blocks), dim3(64 * kWavesPerBlock), 0, stream, a);
     return hipGetLastError();
 }
 
 // sets: the SETS instantiations (rng_mode 1, dsrt_render_accumulate); moments: with MOMENTS as well (a.accum_sq is set)
-hipError_t launch_render(const RenderArgs& a, int lds_entries, int rng_mode, int blocks, bool count, bool checked, bool anyhit, bool lean, bool sets, bool moments,
-                         hipStream_t stream) {
-    if (lds_entries != 8) return hipErrorInvalidValue;     // the only short-stack size built
-    if (rng_mode == 0 && !sets && !moments) return launch_k<8, 0>(a, blocks, count, checked, anyhit, lean, stream);
-    if (rng_mode == 1 && !sets && !moments) return launch_k<8, 1>(a, blocks, count, checked, anyhit, lean, stream);
-    if (rng_mode == 1 && sets && !moments) return launch_k<8, 1, true>(a, blocks, count, checked, anyhit, lean, stream);
-    if (rng_mode == 1 && sets && moments) return launch_k<8, 1, true, true>(a, blocks, count, checked, anyhit, lean, stream);
+// (K = 8 is the only short-stack size built)
+static hipError_t launch_render(const RenderArgs& a, const RenderVariant& v, int blocks, hipStream_t stream) {
+    if (v.rng_mode == 0 && !v.sets && !v.moments) return launch_k<8, 0>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
+    if (v.rng_mode == 1 && !v.sets && !v.moments) return launch_k<8, 1>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
+    if (v.rng_mode == 1 && v.sets && !v.moments) return launch_k<8, 1, true>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
+    if (v.rng_mode == 1 && v.sets && v.moments) return launch_k<8, 1, true, true>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
-                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream) {
+static hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                                 const unsigned long long* sums_sq, float* out_var, hipStream_t stream) {
     if (!n_pixels) return hipSuccess;
     hipLaunchKernelGGL(dsrt_resolve_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, samples_done, inv_gamma, n_pixels, out_rgb8, out_f32,
                        sums_sq, out_var);
     return hipGetLastError();
+}
+
+const RenderLaunchers& compiled_render_launchers() {
+    static const RenderLaunchers table = {launch_render, launch_render_batch, launch_probe, launch_resolve};
+    return table;
 }
 
 #ifndef DSRT_DEVICE_LIBM
@@ -805,8 +809,6 @@ hipError_t launch_math(int fn, const float* x, float y, float* out, int n, hipSt
     hipLaunchKernelGGL(dsrt_math_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, x, y, out, n);
     return hipGetLastError();
 }
-
-int kernel_waves_per_block() { return kWavesPerBlock; }
 
 #endif  // !DSRT_DEVICE_LIBM
 
