@@ -9,19 +9,22 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dsrt.h"
 #include "../host/host_internal.hpp"
 #include "device_layout.h"
+#include "hip_check.h"
 #include "launchers.h"
 
 namespace dsrt {
@@ -41,13 +44,6 @@ void hw_queues_default() {
     static std::once_flag once;
     std::call_once(once, [] { (void)setenv("GPU_MAX_HW_QUEUES", "16", 0); });
 }
-
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return false;
-}
-#define HIP_TRY(expr) do { if (!hip_ok((expr), #expr)) return DSRT_ERR_HIP; } while (0)
 
 template <typename T>
 struct DevBuf {
@@ -70,7 +66,16 @@ struct DevBuf {
         n = count;
         return DSRT_OK;
     }
+    int grow(size_t count) { return n < count ? alloc(count) : DSRT_OK; }      // contents are not kept
 };
+
+// What changes from frame to frame: set by an upload, replaced per context by dsrt_scene_set_camera_sun and the drop-in.
+struct FrameState {
+    GPUCamera camera{};
+    DsrtF3 sun_dir{}, sun_radiance{};
+    int sun_enabled = 0;
+};
+FrameState frame_of(const GPUScene& s) { return FrameState{s.camera, s.sun_dir, s.sun_radiance, s.sun_enabled ? 1 : 0}; }
 
 // The scene in traversal layout, owning its device memory.
 struct PackedScene {
@@ -81,9 +86,7 @@ struct PackedScene {
     DevBuf<GPUTextureHeader> tex_headers;
     DevBuf<float> tex_pool;
     DeviceScene view{};
-    GPUCamera camera{};
-    DsrtF3 sun_dir{}, sun_radiance{};
-    int sun_enabled = 0;
+    FrameState frame;
     bool has_second_tree = false;   // the certified second tree is resident (pack_scene)
     float scene_extent = 0.0f, scene_centre[3] = {0, 0, 0};
     bool lean = false;              // no spheres, no textures, Lambertian materials only: the production launches use the kernels' LEAN instantiation (path_machine.h)
@@ -242,7 +245,7 @@ int pack_scene(const GPUScene& h, PackedScene& out, bool second_tree) {
             // otherwise.  What the check needs from here: (a) the triangles the reference walk can never reach -- a zero-thickness box on their root-to-leaf path:
             // bbox_hit's `t_max <= t_min` holds with equality, src/gpu_render.cu:312 -- are left OUT of the second tree; (b) every triangle's leaf box ON THE
             // REFERENCE TREE rides with its slot (tri_cert); (c) the second tree's boxes are widened by 2^-16 of the scene's extent, so that no rounding of the slab
-            // arithmetic makes a ray miss the box of a triangle it hits (ray origins up to 30 extents away: render_impl checks the camera).
+            // arithmetic makes a ray miss the box of a triangle it hits (ray origins up to 30 extents away: plan_render checks the camera).
             SecondTree st2;
             int rc = prepare_second_tree(h, second_tree_leaf_max(), st2);        // host/bvh_sah.cpp: unreachable triangles, reference-leaf boxes, the widened SAH tree, the checks
             if (rc != DSRT_OK) return rc;
@@ -314,8 +317,7 @@ int pack_scene(const GPUScene& h, PackedScene& out, bool second_tree) {
     v.num_pairs = (int)(pairs.size() / 4); v.num_tri_pairs = (int)(isect.size() / 5); v.num_big_leaves = (int)big.size();
     v.num_materials = h.num_materials; v.num_spheres = h.num_spheres; v.num_lights = num_lights;
     v.num_textures = (int)out.tex_headers.n; v.tex_pool_floats = (int)out.tex_pool.n;
-    out.camera = h.camera;
-    out.sun_dir = h.sun_dir; out.sun_radiance = h.sun_radiance; out.sun_enabled = h.sun_enabled ? 1 : 0;
+    out.frame = frame_of(h);
     out.lean = h.num_spheres == 0 && out.tex_headers.n == 0;
     for (int i = 0; i < h.num_materials && out.lean; ++i) out.lean = h.materials[i].type == MAT_LAMBERTIAN;
     out.valid = true;
@@ -330,9 +332,7 @@ struct DsrtContext {
     // The resident scene is shared between a context and its clones (dsrt_ctx_clone): one copy in HBM however many frames are in
     // flight.  Camera and sun are per context (they are what changes per frame); so are the working buffers below.
     std::shared_ptr<PackedScene> scene;
-    GPUCamera camera{};
-    DsrtF3 sun_dir{}, sun_radiance{};
-    int sun_enabled = 0;
+    FrameState frame;
     bool want_second_tree = false;  // dsrt_ctx_set_certified_tree / DSRT_CERTIFIED_TREE: the next upload also builds and packs the certified second tree
     DevBuf<uint32_t> ctrl;          // [0] queue, [1] flags, then counters (uint64 x kNumCounters) at byte 16
     DevBuf<uint2> spill;
@@ -357,8 +357,7 @@ int install_scene(DsrtContext* ctx, const GPUScene& host_layout) {
     const int rc = pack_scene(host_layout, *fresh, ctx->want_second_tree);
     if (rc) return rc;
     ctx->scene = std::move(fresh);
-    ctx->camera = ctx->scene->camera;
-    ctx->sun_dir = ctx->scene->sun_dir; ctx->sun_radiance = ctx->scene->sun_radiance; ctx->sun_enabled = ctx->scene->sun_enabled;
+    ctx->frame = ctx->scene->frame;
     return DSRT_OK;
 }
 
@@ -420,12 +419,105 @@ void experiment_from_environment() {            // once per process
 
 uint32_t experiment_word() { return g_experiment.load(); }
 
-// Ray queries (raycast_kernel.hip).  Argument checks shared by the device and the host form: every range is known from `count`.
-struct Range { const void* p; size_t bytes; };
+// The context's resident scene, or null ...
+const PackedScene* scene_of(const DsrtContext* ctx) { return ctx && ctx->scene && ctx->scene->valid ? ctx->scene.get() : nullptr; }
+// ... and for an entry point that needs one: null leaves "<fn>: no scene uploaded" as the error, and the caller returns DSRT_ERR_NO_SCENE.
+const PackedScene* resident_scene(const DsrtContext* ctx, const char* fn) {
+    const PackedScene* sc = scene_of(ctx);
+    if (!sc) set_error(std::string(fn) + ": no scene uploaded");
+    return sc;
+}
 
-bool ranges_overlap(const Range& a, const Range& b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+// ONE LAUNCH AT A TIME PER CONTEXT.  A context's working buffers and status words serve one launch, so every entry point that launches goes through
+//   launch_begin    the context's previous launch (on whatever stream it went) comes first; then this launch's device words are zeroed, in the order given
+//   launch_clock    what is enqueued from here on is DsrtStats.kernel_ms (a pre-pass is enqueued before it)
+//   launch_finish   `done` is recorded for the next launch to wait for; a caller that wants stats waits here and gets them zeroed but for kernel_ms
+//   flags_result    the status word of a checked kernel, as a return code
+struct Zeroed { void* p; size_t bytes; };
+int launch_begin(DsrtContext* ctx, hipStream_t stream, std::initializer_list<Zeroed> zeroed) {
+    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));
+    for (const Zeroed& z : zeroed) if (z.p) HIP_TRY(hipMemsetAsync(z.p, 0, z.bytes, stream));
+    return DSRT_OK;
+}
+int launch_clock(DsrtContext* ctx, hipStream_t stream, const DsrtStats* stats) { if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream)); return DSRT_OK; }
+int launch_finish(DsrtContext* ctx, hipStream_t stream, DsrtStats* stats) {
+    HIP_TRY(hipEventRecord(ctx->done, stream));
+    ctx->done_valid = true;
+    if (!stats) return DSRT_OK;
+    HIP_TRY(hipEventRecord(ctx->ev1, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    std::memset(stats, 0, sizeof *stats);
+    HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, ctx->ev0, ctx->ev1));
+    return DSRT_OK;
+}
+int flags_result(const char* kernel, uint32_t flags) {
+    if (!flags) return DSRT_OK;
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "%s kernel raised status flags 0x%x", kernel, flags);
+    set_error(buf);
+    return DSRT_ERR_DEVICE_FLAG;
+}
+// All of it around a kernel without a pre-pass and with one status word of its own (the G-buffer pass, the ray queries).
+template <typename Launch>
+int launch_enveloped(DsrtContext* ctx, hipStream_t stream, uint32_t* status, DsrtStats* stats, const char* kernel, int waves, Launch&& launch) {
+    int rc;
+    if ((rc = launch_begin(ctx, stream, {{status, sizeof(uint32_t)}})) || (rc = launch_clock(ctx, stream, stats))) return rc;
+    HIP_TRY(launch(stream));
+    if ((rc = launch_finish(ctx, stream, stats)) || !stats) return rc;
+    HIP_TRY(hipMemcpy(&stats->device_flags, status, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    stats->waves_launched = waves;
+    return flags_result(kernel, stats->device_flags);
+}
+
+// STAGED HOST CALLS: the _to_host form of an entry point is its device form on device mirrors of the caller's host buffers.  A null host pointer (a channel
+// not asked for) has no mirror; inputs are copied in before the call, results out after a successful one.
+enum class Dir { In, Out, InOut };
+struct Staged { const void* host; size_t bytes; Dir dir; };
+template <size_t N, typename Call>
+int staged_call(const Staged (&s)[N], Call&& call) {          // call(void* const* mirrors) -> return code
+    DevBuf<uint8_t> mirror[N];
+    void* dev[N] = {nullptr};
+    for (size_t k = 0; k < N; ++k) {
+        if (!s[k].host) continue;
+        if (int rc = mirror[k].alloc(s[k].bytes)) return rc;
+        dev[k] = mirror[k].p;
+        if (dev[k] && s[k].dir != Dir::Out) HIP_TRY(hipMemcpy(dev[k], s[k].host, s[k].bytes, hipMemcpyHostToDevice));
+    }
+    if (int rc = call(dev)) return rc;
+    for (size_t k = 0; k < N; ++k)
+        if (dev[k] && s[k].dir != Dir::In) HIP_TRY(hipMemcpy(const_cast<void*>(s[k].host), dev[k], s[k].bytes, hipMemcpyDeviceToHost));
+    return DSRT_OK;
+}
+
+// Bytes per element of the channels of include/dsrt.h's structs of pointers, in the order of their members.
+constexpr size_t kRayBytes[4] = {12, 12, 4, 4};                                // DsrtRays: origins, dirs, t_min, t_max
+constexpr size_t kRayHitBytes[9] = {4, 4, 12, 12, 8, 12, 4, 4, 1};             // DsrtRayHits: t, range, position, normal, uv, albedo, prim_id, material_id, flags
+constexpr size_t kGBufferBytes[11] = {4, 4, 4, 12, 12, 8, 12, 4, 4, 4, 1};     // DsrtGBuffer: t, range, depth, position, normal, uv, albedo, prim_id, material_id, sun_cos, flags
+static_assert(sizeof(DsrtRays) == 4 * sizeof(void*), "kRayBytes has one entry per pointer of DsrtRays");
+static_assert(sizeof(DsrtRayHits) == 9 * sizeof(void*), "kRayHitBytes has one entry per pointer of DsrtRayHits");
+static_assert(sizeof(DsrtGBuffer) == 11 * sizeof(void*), "kGBufferBytes has one entry per pointer of DsrtGBuffer");
+constexpr int kRayHitFlags = 8;                                               // `flags` in kRayHitBytes: the one channel DSRT_TRACE_ANY writes
+static_assert(offsetof(DsrtRayHits, flags) == kRayHitFlags * sizeof(void*) && kRayHitBytes[kRayHitFlags] == 1, "kRayHitFlags is the place of DsrtRayHits.flags");
+static_assert(sizeof(DsrtAccum) == 2 * sizeof(void*), "DsrtAccum is {sum, sum_sq}: the first two mirrors of the accumulate and resolve host forms");
+
+// Such a struct's channels of `n` elements each as Staged entries, and the struct again from the mirrors of those entries.
+template <typename S, size_t N>
+void channels(const S& s, const size_t (&bytes_per)[N], size_t n, Dir dir, Staged* out) {
+    static_assert(sizeof(S) == N * sizeof(void*), "one table entry per pointer of the struct");
+    const void* p[N];
+    std::memcpy(p, &s, sizeof p);
+    for (size_t k = 0; k < N; ++k) out[k] = Staged{p[k], n * bytes_per[k], dir};
+}
+template <typename S>
+S pointers_as(void* const* mirrors) {              // the caller's list has sizeof(S) / sizeof(void*) entries from `mirrors` on, in S's order
+    static_assert(std::is_trivially_copyable_v<S> && sizeof(S) % sizeof(void*) == 0, "a struct of pointers and nothing else");
+    S s; std::memcpy(&s, mirrors, sizeof s); return s;
+}
+
+// Ray queries (raycast_kernel.hip).  Argument checks shared by the device and the host form: every range is known from `count`.
+bool ranges_overlap(const Staged& a, const Staged& b) {
+    if (!a.host || !b.host || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = (uintptr_t)a.host, b0 = (uintptr_t)b.host;
     return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
 }
 
@@ -435,19 +527,33 @@ int check_trace_args(const char* fn, const DsrtContext* ctx, int count, const Ds
     if (!rays->origins || !rays->dirs) return fail("null origins or dirs");
     if (count < 0) return fail("count < 0");
     if (mode != DSRT_TRACE_CLOSEST && mode != DSRT_TRACE_ANY) return fail("unknown mode");
-    const size_t n = (size_t)count;
-    const Range in[4] = {{rays->origins, n * 12}, {rays->dirs, n * 12}, {rays->t_min, n * 4}, {rays->t_max, n * 4}};
-    const Range out[9] = {{hits->t, n * 4}, {hits->range, n * 4}, {hits->position, n * 12}, {hits->normal, n * 12}, {hits->uv, n * 8},
-                          {hits->albedo, n * 12}, {hits->prim_id, n * 4}, {hits->material_id, n * 4}, {hits->flags, n}};
+    Staged in[4], out[9];
+    channels(*rays, kRayBytes, (size_t)count, Dir::In, in);
+    channels(*hits, kRayHitBytes, (size_t)count, Dir::Out, out);
     bool any_out = false, non_flag_out = false;
-    for (int k = 0; k < 9; ++k) if (out[k].p) { any_out = true; if (k != 8) non_flag_out = true; }
+    for (int k = 0; k < 9; ++k) if (out[k].host) { any_out = true; if (k != kRayHitFlags) non_flag_out = true; }
     if (!any_out) return fail("no output channel");
     if (mode == DSRT_TRACE_ANY && non_flag_out) return fail("DSRT_TRACE_ANY writes `flags` only");
-    for (const Range& r : in) if ((uintptr_t)r.p & 3u) return fail("pointer not 4-byte aligned");
-    for (const Range& r : out) if ((uintptr_t)r.p & 3u) return fail("pointer not 4-byte aligned");
-    for (const Range& o : out)
-        for (const Range& i : in)
+    for (const Staged& r : in) if ((uintptr_t)r.host & 3u) return fail("pointer not 4-byte aligned");
+    for (const Staged& r : out) if ((uintptr_t)r.host & 3u) return fail("pointer not 4-byte aligned");
+    for (const Staged& o : out)
+        for (const Staged& i : in)
             if (ranges_overlap(o, i)) return fail("an output range overlaps an input range");
+    return DSRT_OK;
+}
+
+// GPUScene's seven arrays, each as f(pointer, elements): `elements` is the array's count where the pointer is set and 0 where it is null; tri_indices has no count
+// of its own but one entry per triangle, and bvh_tri_indices is its alias (include/dsrt_scene_abi.h).  f may replace the pointer; the first non-zero return ends the walk.
+constexpr size_t kSceneArrays = 7;                 // calls of f per walk (what a caller keeps per array is sized by this)
+template <typename Scene, typename F>
+int for_each_scene_array(Scene& s, F&& f) {
+    auto elements = [](const void* p, int count) { return p ? (size_t)count : (size_t)0; };
+    int rc;
+    if ((rc = f(s.triangles, elements(s.triangles, s.num_triangles))) || (rc = f(s.spheres, elements(s.spheres, s.num_spheres))) ||
+        (rc = f(s.materials, elements(s.materials, s.num_materials))) || (rc = f(s.tri_indices, elements(s.tri_indices, s.num_triangles)))) return rc;
+    if constexpr (!std::is_const_v<Scene>) s.bvh_tri_indices = const_cast<int*>(s.tri_indices);
+    if ((rc = f(s.bvh_nodes, elements(s.bvh_nodes, s.num_bvh_nodes))) || (rc = f(s.textures, elements(s.textures, s.num_textures))) ||
+        (rc = f(s.texture_pool, elements(s.texture_pool, s.texture_pool_floats)))) return rc;
     return DSRT_OK;
 }
 
@@ -501,8 +607,7 @@ int dsrt_ctx_clone(const DsrtContext* src, DsrtContext** out) {
     if (rc) return rc;
     (*out)->scene = src->scene;                    // shared, read-only on the device
     (*out)->want_second_tree = src->want_second_tree;
-    (*out)->camera = src->camera;
-    (*out)->sun_dir = src->sun_dir; (*out)->sun_radiance = src->sun_radiance; (*out)->sun_enabled = src->sun_enabled;
+    (*out)->frame = src->frame;
     return DSRT_OK;
 }
 
@@ -514,7 +619,7 @@ int dsrt_ctx_set_certified_tree(DsrtContext* ctx, int on) {
     return DSRT_OK;
 }
 
-int dsrt_ctx_has_certified_tree(const DsrtContext* ctx) { return ctx && ctx->scene && ctx->scene->valid && ctx->scene->has_second_tree ? 1 : 0; }
+int dsrt_ctx_has_certified_tree(const DsrtContext* ctx) { const PackedScene* sc = scene_of(ctx); return sc && sc->has_second_tree ? 1 : 0; }
 
 void dsrt_ctx_destroy(DsrtContext* ctx) {
     if (!ctx) return;
@@ -538,39 +643,27 @@ int dsrt_scene_upload_device(DsrtContext* ctx, const GPUScene* d) {
         set_error("scene has a negative count"); return DSRT_ERR_INVALID;
     }
     // Bring the reference-layout arrays back to the host, then convert as usual.
-    std::vector<GPUTriangle> tris((size_t)(d->triangles ? d->num_triangles : 0));
-    std::vector<GPUSphere> sph((size_t)(d->spheres ? d->num_spheres : 0));
-    std::vector<GPUMaterial> mats((size_t)(d->materials ? d->num_materials : 0));
-    std::vector<int> idx((size_t)(d->tri_indices ? d->num_triangles : 0));
-    std::vector<GPUBVHNode> nodes((size_t)(d->bvh_nodes ? d->num_bvh_nodes : 0));
-    std::vector<GPUTextureHeader> th((size_t)(d->textures ? d->num_textures : 0));
-    std::vector<float> pool((size_t)(d->texture_pool ? d->texture_pool_floats : 0));
-    auto pull = [](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    HIP_TRY(pull(tris.data(), d->triangles, tris.size() * sizeof(GPUTriangle)));
-    HIP_TRY(pull(sph.data(), d->spheres, sph.size() * sizeof(GPUSphere)));
-    HIP_TRY(pull(mats.data(), d->materials, mats.size() * sizeof(GPUMaterial)));
-    HIP_TRY(pull(idx.data(), d->tri_indices, idx.size() * sizeof(int)));
-    HIP_TRY(pull(nodes.data(), d->bvh_nodes, nodes.size() * sizeof(GPUBVHNode)));
-    HIP_TRY(pull(th.data(), d->textures, th.size() * sizeof(GPUTextureHeader)));
-    HIP_TRY(pull(pool.data(), d->texture_pool, pool.size() * sizeof(float)));
     GPUScene h = *d;
-    h.triangles = tris.empty() ? nullptr : tris.data();
-    h.spheres = sph.empty() ? nullptr : sph.data();
-    h.materials = mats.empty() ? nullptr : mats.data();
-    h.tri_indices = idx.empty() ? nullptr : idx.data();
-    h.bvh_tri_indices = const_cast<int*>(h.tri_indices);
-    h.bvh_nodes = nodes.empty() ? nullptr : nodes.data();
-    h.textures = th.empty() ? nullptr : th.data();
-    h.texture_pool = pool.empty() ? nullptr : pool.data();
+    std::vector<uint8_t> host[kSceneArrays];                          // (bytes from operator new: aligned for every element type of the scene)
+    size_t k = 0;
+    const int rc = for_each_scene_array(h, [&](auto*& p, size_t n) -> int {
+        assert(k < kSceneArrays);
+        std::vector<uint8_t>& to = host[k++];
+        to.resize(n * sizeof(*p));
+        if (n) HIP_TRY(hipMemcpy(to.data(), p, to.size(), hipMemcpyDeviceToHost));
+        p = n ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(to.data()) : nullptr;
+        return DSRT_OK;
+    });
+    if (rc) return rc;
     return install_scene(ctx, h);
     });
 }
 
 int dsrt_scene_set_camera_sun(DsrtContext* ctx, const GPUCamera* cam, const float sun_dir_model[3]) {
     if (!ctx || !cam) { set_error("dsrt_scene_set_camera_sun: null argument"); return DSRT_ERR_INVALID; }
-    if (!ctx->scene || !ctx->scene->valid) { set_error("no scene uploaded"); return DSRT_ERR_NO_SCENE; }
-    ctx->camera = *cam;
-    if (sun_dir_model) ctx->sun_dir = DsrtF3{sun_dir_model[0], sun_dir_model[1], sun_dir_model[2]};
+    if (!resident_scene(ctx, "dsrt_scene_set_camera_sun")) return DSRT_ERR_NO_SCENE;
+    ctx->frame.camera = *cam;
+    if (sun_dir_model) ctx->frame.sun_dir = DsrtF3{sun_dir_model[0], sun_dir_model[1], sun_dir_model[2]};
     return DSRT_OK;
 }
 
@@ -590,32 +683,56 @@ struct BatchInput { int frames; const GPUCamera* cameras; const DsrtF3* sun_dirs
 // planned at desc->spp -- and where their sums go (the caller's buffers, added to, never cleared; no resolve).
 struct AccumInput { int first, count, stride; unsigned long long* sum; unsigned long long* sum_sq; };
 
-static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, void* stream_v, DsrtStats* stats, const BatchInput* batch,
-                       const AccumInput* acc = nullptr) {
+// ---- A render launch (dsrt_render, dsrt_render_batch, dsrt_render_accumulate), in stages: plan_render refuses or decides everything, without a HIP call;
+// grow_render_buffers sizes the context's working buffers; one of the three pre-passes orders the tiles; launch_and_resolve; read_render_stats. ----
+namespace {
+
+constexpr int kLdsStackEntries = 8;                      // LDS short-stack: 8 entries per lane (what fits beside the tree top and the continuation strip); deeper entries spill.
+constexpr int kThreadsPerBlock = 64 * kWavesPerBlock;
+constexpr int kProbeSpp = 4;          // x every pixel of the heavy tiles: 7 ms at 1080p, near frame.  (1, 2, 4 or 8 samples order the tiles equally well.)
+
+enum class PrePass { Batch, Ordered, Natural };
+
+struct RenderPlan {
+    Tiling t;
+    RenderArgs a;                     // complete but for what grow_render_buffers (accum_fixed of the context's own sums, spill, sched) and the pre-pass (tile order, batch table) add
+    RenderVariant variant;
+    const RenderLaunchers* rl;
+    PrePass pre;
+    bool cull, probe;                 // the pre-pass removes provably empty tiles / re-sorts the heavy tiles by measured cost ...
+    int probe_spp;                    // ... at this many samples per pixel
+    bool own_sums;                    // rng_mode 1 of dsrt_render(_batch): the sums are the context's, zeroed before and resolved behind the launch
+    int frames, chunks, chunk_len, blocks;
+    size_t out_pixels, pre_stride;    // pre_stride, per frame: tile costs / order, then the sched words
+    uint32_t* sched;                  // {tiles that see geometry, tiles in the order, heavy lanes per wave}: the words 32 entries past the cost array (grow_render_buffers)
+};
+
+}  // namespace
+
+static int plan_render(const DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, const BatchInput* batch, const AccumInput* acc, RenderPlan& p) {
     if (!ctx || !desc || (!d_rgb8 && !acc)) { set_error("dsrt_render: null argument"); return DSRT_ERR_INVALID; }
-    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    const PackedScene* scp = resident_scene(ctx, "dsrt_render");
+    if (!scp) return DSRT_ERR_NO_SCENE;
+    const PackedScene& sc = *scp;
     if (desc->rng_mode != 0 && desc->rng_mode != 1) { set_error("dsrt_render: rng_mode must be 0 (reference LCG stream per pixel) or 1 (Philox4x32-10 stream per sample)"); return DSRT_ERR_INVALID; }
     if (desc->math_mode != 0 && desc->math_mode != 1) { set_error("dsrt_render: math_mode must be 0 (deterministic sin / cos / pow shared with the CPU oracle) or 1 (the device math library's)"); return DSRT_ERR_INVALID; }
-    const RenderLaunchers& rl = render_launchers(desc->math_mode == 1);
-    const bool lean = ctx->scene->lean && !(experiment_word() & (1u << 24));
+    p.rl = &render_launchers(desc->math_mode == 1);
     if (desc->tune[3] & ~DSRT_TUNE_FLAG_MASK) { set_error("dsrt_render: tune[3] has bits set that this ABI version does not define (DSRT_TUNE_* in include/dsrt.h)"); return DSRT_ERR_INVALID; }
     const uint32_t flags = (uint32_t)desc->tune[3];
     const uint32_t xp = experiment_word();
-    Tiling t;
+    const bool lean = sc.lean && !(xp & (1u << 24));
+    Tiling& t = p.t;
     if (!make_tiling(*desc, t)) { set_error("dsrt_render: bad size, tile or shard"); return DSRT_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const PackedScene& sc = *ctx->scene;
-    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // a context's working buffers serve one render at a time
 
-    RenderArgs a;
+    RenderArgs& a = p.a;
     std::memset(&a, 0, sizeof a);
     a.scene = sc.view;
     FrameParams& f = a.frame;
-    pack_camera(ctx->camera, f.cam);
-    f.sun_dir[0] = ctx->sun_dir.x; f.sun_dir[1] = ctx->sun_dir.y; f.sun_dir[2] = ctx->sun_dir.z;
-    f.sun_radiance[0] = ctx->sun_radiance.x; f.sun_radiance[1] = ctx->sun_radiance.y; f.sun_radiance[2] = ctx->sun_radiance.z;
-    f.sun_enabled = ctx->sun_enabled;
+    const FrameState& fs = ctx->frame;
+    pack_camera(fs.camera, f.cam);
+    f.sun_dir[0] = fs.sun_dir.x; f.sun_dir[1] = fs.sun_dir.y; f.sun_dir[2] = fs.sun_dir.z;
+    f.sun_radiance[0] = fs.sun_radiance.x; f.sun_radiance[1] = fs.sun_radiance.y; f.sun_radiance[2] = fs.sun_radiance.z;
+    f.sun_enabled = fs.sun_enabled;
     f.width = desc->width; f.height = desc->height;
     f.plan_spp = desc->spp < 1 ? 1 : desc->spp;                         // src/gpu_render.cu:987-988
     f.spp = acc ? acc->count : f.plan_spp;                               // what the launch renders of each pixel: work items, slices and the pre-pass count these
@@ -632,19 +749,20 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     if ((unsigned long long)t.mine * (unsigned long long)(t.tile * t.tile) >= (1ull << 31)) { set_error("dsrt_render: image too large (2^31 pixels per shard)"); return DSRT_ERR_INVALID; }
     uint32_t total_items = (uint32_t)t.mine * (uint32_t)(t.tile * t.tile);
     f.compact_output = desc->shard_count > 1 ? 1 : 0;
-    int chunks = 1, chunk_len = f.spp;
+    p.chunks = 1; p.chunk_len = f.spp;
     f.light_chunk_len = f.spp;
-    const int frames = batch ? batch->frames : 1;
+    p.frames = batch ? batch->frames : 1;
     if (batch) {
-        if (frames < 1 || !batch->cameras || !batch->sun_dirs) { set_error("dsrt_render_batch: no frames"); return DSRT_ERR_INVALID; }
+        if (p.frames < 1 || !batch->cameras || !batch->sun_dirs) { set_error("dsrt_render_batch: no frames"); return DSRT_ERR_INVALID; }
         if (desc->collect_counters || desc->checked) { set_error("dsrt_render_batch uses the production kernel only (no counters, not checked)"); return DSRT_ERR_INVALID; }
         // 32-bit output indices and work-item numbers: frames x pixels (x 8 sample slices in rng_mode 1) stay below 2^32
         const unsigned long long frame_px = desc->shard_count > 1 ? (unsigned long long)t.padded * t.tile * t.tile : (unsigned long long)desc->width * desc->height;
-        if ((unsigned long long)frames * frame_px * (desc->rng_mode == 1 ? 16ull : 1ull) >= (1ull << 32)) {
+        if ((unsigned long long)p.frames * frame_px * (desc->rng_mode == 1 ? 16ull : 1ull) >= (1ull << 32)) {
             set_error("dsrt_render_batch: too many pixels in one batch (split the sequence)"); return DSRT_ERR_INVALID;
         }
     }
-    const size_t out_pixels = (desc->shard_count > 1 ? (size_t)t.padded * t.tile * t.tile : (size_t)desc->width * desc->height) * (size_t)frames;
+    p.out_pixels = (desc->shard_count > 1 ? (size_t)t.padded * t.tile * t.tile : (size_t)desc->width * desc->height) * (size_t)p.frames;
+    p.own_sums = desc->rng_mode == 1 && !acc;
     if (desc->rng_mode == 1) {
         // a pixel's samples are independent streams: pixels of tiles that see geometry are split into 8 work items.  More slices cost
         // more in half-empty advance passes than their shorter tail saves; fewer leave whole waves without work at the end of a small
@@ -652,7 +770,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         // stealing on: 1 / 2 / 4 / 8 / 16 / 32 / 64 slices = 307 / 289 / 188 / 171 / 181 / 191 / 203 ms; whole frame on one GPU
         // 1091 / 1076 / 1063 / 1050 / 1047 (profiles/r02/README.md).  An item's integer sums are 32-bit in units of 2^-20: at most 4095
         // samples per item, so with more samples than that every pixel is sliced, whatever its tile sees.
-        chunk_len = (f.spp + 7) / 8;
+        int chunk_len = (f.spp + 7) / 8;
         if ((xp >> 8) & 0xFFFu) chunk_len = (f.spp + (int)((xp >> 8) & 0xFFFu) - 1) / (int)((xp >> 8) & 0xFFFu);   // experiment: slices per pixel
         // Sample sets: a set of few samples per pixel (one of many interleaved passes) is not cut below kSetMinItem samples per item.  One of ten passes
         // of the 1080p x 1000 near frame (100 samples): 8 slices of 13 = 114.6 ms, 4 / 2 / 1 slices = 87 / 86 / 88 ms; passes of 250 samples: 189 ms with 8
@@ -661,7 +779,8 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         if (acc && !((xp >> 8) & 0xFFFu)) chunk_len = std::max(chunk_len, std::min(f.spp, kSetMinItem));
         if (chunk_len < 1) chunk_len = 1;
         if (chunk_len > 4095) chunk_len = 4095;
-        chunks = (f.spp + chunk_len - 1) / chunk_len;
+        p.chunk_len = chunk_len;
+        p.chunks = (f.spp + chunk_len - 1) / chunk_len;
         // Background pixels (tiles that see no geometry) are cut too, but not below kLightLen samples per item: uncut, their 1000-sample
         // items are the longest jobs of a frame and the light queue is served last (one of 8 shares of the near frame 166 -> 149 ms, frame
         // 70 60 -> 43 ms); cut as finely as the heavy pixels, their three 64-bit atomics per item cost the 250-spp sequence, whose frames
@@ -675,14 +794,9 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         if (desc->width > 65535 || desc->height > 65535) { set_error("dsrt_render: rng_mode 1 hands samples between lanes with 16-bit pixel coordinates (width, height <= 65535)"); return DSRT_ERR_INVALID; }
         if ((unsigned long long)total_items * 64ull >= (1ull << 32)) { set_error("dsrt_render: image too large for rng_mode 1 (more than 2^32 sample slices)"); return DSRT_ERR_INVALID; }
         total_items *= 64u;                                     // upper bound (the pre-pass picks 8 to 64 slices per heavy pixel): sizes the grid only
-        if (acc) {                                              // the caller's sums, added to
+        if (acc) {                                              // the caller's sums, added to (the context's own: grow_render_buffers; 24 bytes per pixel)
             a.accum_fixed = acc->sum;
             a.accum_sq = acc->sum_sq;
-        } else {
-            const size_t words = out_pixels * 3;
-            if (ctx->accum_fixed.n < words) { int rc = ctx->accum_fixed.alloc(words); if (rc) return rc; }
-            HIP_TRY(hipMemsetAsync(ctx->accum_fixed.p, 0, words * sizeof(unsigned long long), stream));       // 24 bytes per pixel
-            a.accum_fixed = ctx->accum_fixed.p;
         }
     }
     a.out_rgb8 = d_rgb8;
@@ -692,26 +806,16 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     a.flags = ctx->ctrl.p + 1;
     a.counters = (uint64_t*)(ctx->ctrl.p + 4);
 
-    // LDS short-stack: 8 entries per lane (what fits beside the tree top and the continuation strip); deeper entries spill.
-    const int K = 8;
-    if (desc->stack_entries != 0 && desc->stack_entries != 8) { set_error("dsrt_render: stack_entries must be 0 or 8"); return DSRT_ERR_INVALID; }
-    const int threads_per_block = 64 * kWavesPerBlock;
+    if (desc->stack_entries != 0 && desc->stack_entries != kLdsStackEntries) { set_error("dsrt_render: stack_entries must be 0 or 8"); return DSRT_ERR_INVALID; }
     const int resident_blocks = ctx->num_cus * 4;                         // 4 waves per SIMD = 4 workgroups of 4 waves per CU (render_kernel.hip)
-    int blocks = resident_blocks;                                         // persistent: exactly the resident set
-    if ((xp >> 20) & 7u) blocks = std::max(1, resident_blocks >> ((xp >> 20) & 7u));     // experiment: a fraction of it (frames that overlap)
+    p.blocks = resident_blocks;                                           // persistent: exactly the resident set
+    if ((xp >> 20) & 7u) p.blocks = std::max(1, resident_blocks >> ((xp >> 20) & 7u));     // experiment: a fraction of it (frames that overlap)
     {
-        const long long needed = ((long long)total_items + threads_per_block - 1) / threads_per_block;
-        if (needed < blocks && !batch) blocks = (int)(needed > 0 ? needed : 1);
+        const long long needed = ((long long)total_items + kThreadsPerBlock - 1) / kThreadsPerBlock;
+        if (needed < p.blocks && !batch) p.blocks = (int)(needed > 0 ? needed : 1);
     }
-    const int spill_entries = sc.view.stack_need > K ? sc.view.stack_need - K : 0;
-    const size_t lanes = (size_t)blocks * threads_per_block;
-    if (spill_entries > 0 && ctx->spill.n < lanes * (size_t)spill_entries) {
-        int rc = ctx->spill.alloc(lanes * (size_t)spill_entries);
-        if (rc) return rc;
-    }
-    a.spill = ctx->spill.p;
-    a.spill_stride = (uint32_t)lanes;
-    a.spill_entries = spill_entries;
+    a.spill_entries = sc.view.stack_need > kLdsStackEntries ? sc.view.stack_need - kLdsStackEntries : 0;
+    a.spill_stride = (uint32_t)((size_t)p.blocks * kThreadsPerBlock);                  // lanes
     a.min_walk_iters = desc->tune[0] > 0 ? desc->tune[0] : 64;      // (192 when the rays walk the certified second tree: set below, once a.accel is known)
     a.advance_budget = desc->tune[1] > 0 ? desc->tune[1] : 12;
     a.leaf_ratio4 = desc->tune[2] > 0 ? desc->tune[2] : 10;            // (16 until the node loop looked at its votes every other iteration: profiles/r03/ab_loop_knobs_after_unroll.jsonl)
@@ -727,7 +831,7 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         };
         bool ok = true;
         if (batch) { for (int i = 0; i < batch->frames && ok; ++i) ok = near_enough(batch->cameras[i].origin); }
-        else ok = near_enough(ctx->camera.origin);
+        else ok = near_enough(fs.camera.origin);
         a.accel = ok ? 1 : 0;
     }
     a.audit = a.accel && desc->collect_counters == 3 ? 1 : 0;
@@ -744,163 +848,197 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
     // the order above the rest) were tried in round 2 and moved nothing consistently (profiles/r02/ab_issue_priority.jsonl); they are gone.
     a.hot = (flags & DSRT_TUNE_NO_PRIORITY) ? 0 : 1;
 
-    HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
     // Pre-pass for this camera: costliest-first tile order (scheduling only) and removal of tiles that are provably empty (exact:
     // see dsrt_tile_cost_kernel).  DSRT_TUNE_NATURAL_ORDER switches both off, DSRT_TUNE_NO_CULLING keeps the order but culls nothing; counting builds never
     // cull, so that their counters cover every sample.  The words 32 and 48 entries past the cost array receive the number of
     // tiles that see geometry and the number of tiles in the order.
-    const size_t pre_stride = (size_t)t.mine + 64;          // per frame: tile costs / order, then the sched words
-    if (pre_stride * (size_t)frames >= ((size_t)1 << 32)) { set_error("dsrt_render_batch: too many tiles in one batch (split the sequence)"); return DSRT_ERR_INVALID; }
-    for (DevBuf<uint32_t>* b : {&ctx->tile_cost, &ctx->tile_order, &ctx->tile_work, &ctx->tile_tmp}) {      // each by its own size: a failed
-        const size_t want = (b == &ctx->tile_cost || b == &ctx->tile_order) ? pre_stride * (size_t)frames : pre_stride;
-        if (b->n < want) { int rc = b->alloc(want); if (rc) return rc; }                                    // allocation leaves no stale sibling
-    }
-    uint32_t* sched = ctx->tile_cost.p + t.mine + 32;       // {tiles that see geometry, tiles in the order, heavy lanes per wave}
-    a.sched = sched;
-    if (batch) {
-        // Batch: every frame's pre-pass (exact culling + coverage order; no probe: the frames' chains overlap whatever their order), its
-        // results left pre_stride apart; then one small kernel turns the counts into the table the render kernel looks work items up in.
-        // Slices stay at the host's 8 (resident_lanes = 0: the pool is never short of heavy pixels).
-        const bool cull = (flags & 3u) == 0u;
-        HIP_TRY(hipMemsetAsync(d_rgb8, 0, out_pixels * 3, stream));                          // culled pixels are never written
-        if (d_f32) HIP_TRY(hipMemsetAsync(d_f32, 0, out_pixels * 3 * sizeof(float), stream));
-        if (ctx->batch_table.n < 2 * (size_t)frames) { int rc = ctx->batch_table.alloc(2 * (size_t)frames); if (rc) return rc; }
-        ctx->batch_host.assign(2 * (size_t)frames, BatchFrame{});
-        for (int i = 0; i < frames; ++i) {
-            BatchFrame& e = ctx->batch_host[(size_t)i];
-            pack_camera(batch->cameras[i], e.cam);
-            e.sun_dir[0] = batch->sun_dirs[i].x; e.sun_dir[1] = batch->sun_dirs[i].y; e.sun_dir[2] = batch->sun_dirs[i].z;
-            e.order_base = (uint32_t)(pre_stride * (size_t)i);
-            e.image_slot = (uint32_t)i;
-            ctx->batch_host[(size_t)frames + (size_t)i] = e;                                  // the frame's second entry (device_layout.h, BatchFrame)
-        }
-        HIP_TRY(hipMemcpyAsync(ctx->batch_table.p, ctx->batch_host.data(), 2 * (size_t)frames * sizeof(BatchFrame), hipMemcpyHostToDevice, stream));
-        HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, sched, (uint32_t)chunks, 0u, cull, stream,
-                                  ctx->batch_table.p, (uint32_t)frames, (uint32_t)pre_stride));
-        // rng_mode 0 at enough samples for a pixel to be a long chain: every frame's heavy tiles re-sorted by measured cost, as for a single
-        // frame (the probe launch below in this function) -- one probe per frame, 6 ms each at 1080p, against a frame of a second
-        if (!(flags & DSRT_TUNE_NO_PROBE) && desc->rng_mode == 0 && f.spp >= 256) {
-            if (ctx->probe_queue.n < 1024) { int rc = ctx->probe_queue.alloc(1024); if (rc) return rc; }
-            for (int i = 0; i < frames; ++i) {
-                RenderArgs pa = a;
-                std::memcpy(pa.frame.cam, ctx->batch_host[(size_t)i].cam, sizeof pa.frame.cam);
-                std::memcpy(pa.frame.sun_dir, ctx->batch_host[(size_t)i].sun_dir, 3 * sizeof(float));
-                pa.frame.spp = 4;
-                pa.out_f32 = nullptr; pa.accum_fixed = nullptr; pa.counters = nullptr;
-                pa.sched = sched + pre_stride * (size_t)i;
-                pa.frame.tile_order = ctx->tile_order.p + pre_stride * (size_t)i;
-                pa.tile_work = ctx->tile_work.p;
-                pa.probe_queue = ctx->probe_queue.p;
-                HIP_TRY(hipMemsetAsync(ctx->probe_queue.p, 0, 1024 * sizeof(uint32_t), stream));
-                HIP_TRY(hipMemsetAsync(ctx->tile_work.p, 0, (size_t)t.mine * sizeof(uint32_t), stream));
-                HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
-                HIP_TRY(rl.launch_probe(pa, blocks, lean, stream));
-                HIP_TRY(launch_tile_reorder(ctx->tile_work.p, ctx->tile_order.p + pre_stride * (size_t)i, ctx->tile_tmp.p, sched + pre_stride * (size_t)i, stream));
-            }
-            HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
-        }
-        HIP_TRY(launch_batch_table(ctx->batch_table.p, sched, (uint32_t)pre_stride, (uint32_t)frames, (uint32_t)(t.tile * t.tile), desc->rng_mode, f.spp,
-                                   f.light_chunk_len, ctx->ctrl.p + 2, stream));
-        a.batch = ctx->batch_table.p; a.batch_order = ctx->tile_order.p; a.batch_frames = 2u * (uint32_t)frames;
-        a.batch_frame_pixels = (uint32_t)(out_pixels / (size_t)frames);        // whole images, or the padded compact shard buffers, one after another
-    } else
-    if ((flags & 3u) != DSRT_TUNE_NATURAL_ORDER && t.mine > 0) {
-        const bool cull = (flags & 3u) != DSRT_TUNE_NO_CULLING && desc->collect_counters == 0;
-        if (cull && d_rgb8) {                                   // culled pixels are never written: they are the zeros put here (an accumulate launch adds nothing for them)
-            HIP_TRY(hipMemsetAsync(d_rgb8, 0, out_pixels * 3, stream));
-            if (d_f32) HIP_TRY(hipMemsetAsync(d_f32, 0, out_pixels * 3 * sizeof(float), stream));
-        }
-        HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, sched, (uint32_t)chunks,
-                                  (uint32_t)blocks * (uint32_t)threads_per_block, cull, stream));
-        a.frame.tile_order = ctx->tile_order.p;
-        // Probe: the render kernel itself at kProbeSpp samples per pixel (reference stream, nothing stored)
-        // measures what every tile costs; the heavy tiles are then re-sorted by that.  Worth its 0.5 % only when a pixel is a
-        // long chain; DSRT_TUNE_NO_PROBE switches it off.
-        constexpr int kProbeSpp = 4;          // x every pixel of the heavy tiles: 7 ms at 1080p, near frame.  (1, 2, 4 or 8 samples order the tiles equally well.)
-        // Its work items are tiny, so the probe has 64 queue words of its own (path_machine.h, ST_FETCH): on the frame's single queue word
-        // the same launch took 27 ms.
-        // Only with the reference's stream: in rng_mode 1 a pixel is cut into slices and lanes share samples, so there is no long chain to start
-        // early, and the coverage order alone is better (interleaved medians, near frame: 1046 -> 1037 ms, one of 8 shares 176 -> 167 ms).
-        if (!(flags & DSRT_TUNE_NO_PROBE) && desc->rng_mode == 0 && f.spp >= 64 * kProbeSpp) {
-            RenderArgs pa = a;
-            const int probe_spp = (xp & 64u) ? 2 * kProbeSpp : kProbeSpp;                  // experiment
-            pa.frame.spp = probe_spp;
-            pa.out_f32 = nullptr; pa.accum_fixed = nullptr; pa.counters = nullptr;
-            pa.tile_work = ctx->tile_work.p;
-            if (ctx->probe_queue.n < 1024) { int rc = ctx->probe_queue.alloc(1024); if (rc) return rc; }
-            HIP_TRY(hipMemsetAsync(ctx->probe_queue.p, 0, 1024 * sizeof(uint32_t), stream));
-            pa.probe_queue = ctx->probe_queue.p;
-            HIP_TRY(hipMemsetAsync(ctx->tile_work.p, 0, (size_t)t.mine * sizeof(uint32_t), stream));
-            HIP_TRY(rl.launch_probe(pa, blocks, lean, stream));
-            HIP_TRY(launch_tile_reorder(ctx->tile_work.p, ctx->tile_order.p, ctx->tile_tmp.p, sched, stream));
-            HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
-        }
-    } else {
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)sched, t.mine, 2, stream));           // every tile in the heavy queue, natural order
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 2), 64, 1, stream));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 3), chunks, 1, stream));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(sched + 4), chunk_len, 1, stream));
-    }
-    if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
+    p.pre_stride = (size_t)t.mine + 64;
+    if (p.pre_stride * (size_t)p.frames >= ((size_t)1 << 32)) { set_error("dsrt_render_batch: too many tiles in one batch (split the sequence)"); return DSRT_ERR_INVALID; }
+    p.pre = batch ? PrePass::Batch : ((flags & 3u) != DSRT_TUNE_NATURAL_ORDER && t.mine > 0 ? PrePass::Ordered : PrePass::Natural);
+    p.cull = batch ? (flags & 3u) == 0u : (flags & 3u) != DSRT_TUNE_NO_CULLING && desc->collect_counters == 0;
+    // The probe (probe_tiles) is worth its 0.5 % only when a pixel is a long chain; DSRT_TUNE_NO_PROBE switches it off.
+    // Only with the reference's stream: in rng_mode 1 a pixel is cut into slices and lanes share samples, so there is no long chain to start
+    // early, and the coverage order alone is better (interleaved medians, near frame: 1046 -> 1037 ms, one of 8 shares 176 -> 167 ms).
+    p.probe = p.pre != PrePass::Natural && !(flags & DSRT_TUNE_NO_PROBE) && desc->rng_mode == 0 && f.spp >= 64 * kProbeSpp;
+    p.probe_spp = (!batch && (xp & 64u)) ? 2 * kProbeSpp : kProbeSpp;                  // experiment (a batch's probes ignore it)
+
     const bool count = desc->collect_counters != 0;
-    if (batch) HIP_TRY(rl.launch_render_batch(a, desc->rng_mode, blocks, lean, stream));
-    else {
-        RenderVariant v{};
-        v.rng_mode = desc->rng_mode;
-        v.count = count; v.checked = count || desc->checked != 0; v.anyhit = desc->collect_counters != 2;
-        v.lean = lean; v.sets = acc != nullptr; v.moments = acc && acc->sum_sq;
-        HIP_TRY(rl.launch_render(a, v, blocks, stream));
+    RenderVariant& v = p.variant;
+    v = RenderVariant{};
+    v.rng_mode = desc->rng_mode;
+    v.count = count; v.checked = count || desc->checked != 0; v.anyhit = desc->collect_counters != 2;
+    v.lean = lean; v.sets = acc != nullptr; v.moments = acc && acc->sum_sq;
+    return DSRT_OK;
+}
+
+// Each buffer by its own size: a failed allocation leaves no stale sibling.
+static int grow_render_buffers(DsrtContext* ctx, RenderPlan& p) {
+    RenderArgs& a = p.a;
+    int rc;
+    if (p.own_sums) {
+        if ((rc = ctx->accum_fixed.grow(p.out_pixels * 3))) return rc;
+        a.accum_fixed = ctx->accum_fixed.p;
     }
-    if (desc->rng_mode == 1 && !acc) HIP_TRY(rl.launch_resolve(a.accum_fixed, f.spp, f.inv_gamma, out_pixels, d_rgb8, d_f32, nullptr, nullptr, stream));
-    HIP_TRY(hipEventRecord(ctx->done, stream));
-    ctx->done_valid = true;
-    if (stats) {
-        HIP_TRY(hipEventRecord(ctx->ev1, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        std::memset(stats, 0, sizeof *stats);
-        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, ctx->ev0, ctx->ev1));
-        uint32_t ctrl[kCtrlWords];
-        HIP_TRY(hipMemcpy(ctrl, ctx->ctrl.p, sizeof ctrl, hipMemcpyDeviceToHost));
-        stats->device_flags = ctrl[1];
-        stats->waves_launched = blocks * (threads_per_block / 64);
-        stats->lds_stack_entries = K;
-        uint64_t cnt[kNumCounters];
-        std::memcpy(cnt, &ctrl[4], sizeof cnt);
-        stats->samples = cnt[C_SAMPLES]; stats->rays = cnt[C_RAYS]; stats->primary_hits = cnt[C_PRIMARY_HITS];
-        stats->box_fetches = cnt[C_BOX_FETCHES]; stats->nodes_entered = cnt[C_NODES_ENTERED]; stats->internal_entered = cnt[C_INTERNAL_ENTERED];
-        stats->tri_tests = cnt[C_TRI_TESTS]; stats->hit_updates = cnt[C_HIT_UPDATES]; stats->sphere_tests = cnt[C_SPHERE_TESTS];
-        stats->shaded_hits = cnt[C_SHADED_HITS]; stats->tex_fetches = cnt[C_TEX_FETCHES]; stats->stack_spills = cnt[C_STACK_SPILLS];
-        stats->max_stack = cnt[C_MAX_STACK];
-        stats->node_slots = cnt[C_NODE_SLOTS]; stats->tri_slots = cnt[C_TRI_SLOTS]; stats->adv_slots = cnt[C_ADV_SLOTS]; stats->adv_active = cnt[C_ADV_ACTIVE];
-        stats->idle_at_leaf = cnt[C_IDLE_AT_LEAF]; stats->idle_waiting = cnt[C_IDLE_WAITING]; stats->idle_done = cnt[C_IDLE_DONE];
-        stats->wave_ticks = cnt[C_WAVE_TICKS];
-        stats->certificate_fallbacks = cnt[C_CERT_FALLBACKS];
-        stats->certificate_audited = cnt[C_AUDITED]; stats->certificate_audit_mismatches = cnt[C_AUDIT_MISMATCHES];
-        stats->certified_tree_used = a.accel;
-        {   // time marks relative to the first wave's start, in ms (0 when the mark was never passed)
-            const double t0 = (double)~cnt[C_T_FIRST];
-            stats->heavy_queue_empty_ms = cnt[C_T_HEAVY_EMPTY] ? (float)(((double)~cnt[C_T_HEAVY_EMPTY] - t0) * 1e-5) : 0.0f;
-            stats->light_queue_empty_ms = cnt[C_T_LIGHT_EMPTY] ? (float)(((double)~cnt[C_T_LIGHT_EMPTY] - t0) * 1e-5) : 0.0f;
-            stats->last_wave_exit_ms = cnt[C_T_LAST] ? (float)(((double)cnt[C_T_LAST] - t0) * 1e-5) : 0.0f;
+    if (a.spill_entries > 0 && (rc = ctx->spill.grow((size_t)a.spill_stride * (size_t)a.spill_entries))) return rc;
+    a.spill = ctx->spill.p;
+    if ((rc = ctx->tile_cost.grow(p.pre_stride * (size_t)p.frames)) || (rc = ctx->tile_order.grow(p.pre_stride * (size_t)p.frames)) ||
+        (rc = ctx->tile_work.grow(p.pre_stride)) || (rc = ctx->tile_tmp.grow(p.pre_stride))) return rc;
+    if (p.pre == PrePass::Batch && (rc = ctx->batch_table.grow(2 * (size_t)p.frames))) return rc;
+    if (p.probe && (rc = ctx->probe_queue.grow(1024))) return rc;
+    p.sched = ctx->tile_cost.p + p.t.mine + 32;
+    a.sched = p.sched;
+    return DSRT_OK;
+}
+
+// Probe: the render kernel itself at a few samples per pixel (reference stream, nothing stored) measures what every tile of the frame `pa` describes
+// costs; the heavy tiles of its order (`at` entries into the context's order and sched arrays) are then re-sorted by that.
+// Its work items are tiny, so the probe has 64 queue words of its own (path_machine.h, ST_FETCH): on the frame's single queue word
+// the same launch took 27 ms.  It leaves the frame's queue words used: the caller zeroes `ctrl` behind its last probe, and, where probes follow each
+// other, before each (zero_ctrl_first).
+static int probe_tiles(DsrtContext* ctx, const RenderPlan& p, RenderArgs pa, size_t at, bool zero_ctrl_first, hipStream_t stream) {
+    pa.frame.spp = p.probe_spp;
+    pa.out_f32 = nullptr; pa.accum_fixed = nullptr; pa.counters = nullptr;
+    pa.sched = p.sched + at;
+    pa.frame.tile_order = ctx->tile_order.p + at;
+    pa.tile_work = ctx->tile_work.p;
+    pa.probe_queue = ctx->probe_queue.p;
+    HIP_TRY(hipMemsetAsync(ctx->probe_queue.p, 0, 1024 * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(ctx->tile_work.p, 0, (size_t)p.t.mine * sizeof(uint32_t), stream));
+    if (zero_ctrl_first) HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
+    HIP_TRY(p.rl->launch_probe(pa, p.blocks, p.variant.lean, stream));
+    HIP_TRY(launch_tile_reorder(ctx->tile_work.p, ctx->tile_order.p + at, ctx->tile_tmp.p, p.sched + at, stream));
+    return DSRT_OK;
+}
+
+// Batch: every frame's pre-pass (exact culling + coverage order), its results left pre_stride apart; then one small kernel turns the counts into the
+// table the render kernel looks work items up in.  Slices stay at the host's 8 (resident_lanes = 0: the pool is never short of heavy pixels).
+static int prepass_batch(DsrtContext* ctx, RenderPlan& p, const BatchInput& batch, hipStream_t stream) {
+    RenderArgs& a = p.a;
+    const size_t frames = (size_t)p.frames;
+    HIP_TRY(hipMemsetAsync(a.out_rgb8, 0, p.out_pixels * 3, stream));                          // culled pixels are never written
+    if (a.out_f32) HIP_TRY(hipMemsetAsync(a.out_f32, 0, p.out_pixels * 3 * sizeof(float), stream));
+    ctx->batch_host.assign(2 * frames, BatchFrame{});
+    for (size_t i = 0; i < frames; ++i) {
+        BatchFrame& e = ctx->batch_host[i];
+        pack_camera(batch.cameras[i], e.cam);
+        e.sun_dir[0] = batch.sun_dirs[i].x; e.sun_dir[1] = batch.sun_dirs[i].y; e.sun_dir[2] = batch.sun_dirs[i].z;
+        e.order_base = (uint32_t)(p.pre_stride * i);
+        e.image_slot = (uint32_t)i;
+        ctx->batch_host[frames + i] = e;                                                  // the frame's second entry (device_layout.h, BatchFrame)
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->batch_table.p, ctx->batch_host.data(), 2 * frames * sizeof(BatchFrame), hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, p.sched, (uint32_t)p.chunks, 0u, p.cull, stream,
+                              ctx->batch_table.p, (uint32_t)frames, (uint32_t)p.pre_stride));
+    // rng_mode 0 at enough samples for a pixel to be a long chain: every frame's heavy tiles re-sorted by measured cost, as for a single
+    // frame -- one probe per frame, 6 ms each at 1080p, against a frame of a second
+    if (p.probe) {
+        for (size_t i = 0; i < frames; ++i) {
+            RenderArgs pa = a;
+            std::memcpy(pa.frame.cam, ctx->batch_host[i].cam, sizeof pa.frame.cam);
+            std::memcpy(pa.frame.sun_dir, ctx->batch_host[i].sun_dir, 3 * sizeof(float));
+            if (int rc = probe_tiles(ctx, p, pa, p.pre_stride * i, true, stream)) return rc;
         }
-        stats->visits_depth_lt6 = cnt[C_VISITS_LT6]; stats->visits_depth_lt9 = cnt[C_VISITS_LT9]; stats->visits_depth_lt12 = cnt[C_VISITS_LT12];
-        uint32_t live = 0;
-        HIP_TRY(hipMemcpy(&live, sched + 1, sizeof live, hipMemcpyDeviceToHost));
-        stats->tiles_total = (uint64_t)t.mine; stats->tiles_culled = (uint64_t)t.mine - live;
-        if (stats->device_flags) {
-            char buf[96];
-            std::snprintf(buf, sizeof buf, "render kernel raised status flags 0x%x", stats->device_flags);
-            set_error(buf);
-            return DSRT_ERR_DEVICE_FLAG;
-        }
+        HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
+    }
+    HIP_TRY(launch_batch_table(ctx->batch_table.p, p.sched, (uint32_t)p.pre_stride, (uint32_t)frames, (uint32_t)(p.t.tile * p.t.tile), p.variant.rng_mode, a.frame.spp,
+                               a.frame.light_chunk_len, ctx->ctrl.p + 2, stream));
+    a.batch = ctx->batch_table.p; a.batch_order = ctx->tile_order.p; a.batch_frames = 2u * (uint32_t)frames;
+    a.batch_frame_pixels = (uint32_t)(p.out_pixels / frames);        // whole images, or the padded compact shard buffers, one after another
+    return DSRT_OK;
+}
+
+// One frame, costliest tiles first.
+static int prepass_ordered(DsrtContext* ctx, RenderPlan& p, hipStream_t stream) {
+    RenderArgs& a = p.a;
+    if (p.cull && a.out_rgb8) {                                 // culled pixels are never written: they are the zeros put here (an accumulate launch adds nothing for them)
+        HIP_TRY(hipMemsetAsync(a.out_rgb8, 0, p.out_pixels * 3, stream));
+        if (a.out_f32) HIP_TRY(hipMemsetAsync(a.out_f32, 0, p.out_pixels * 3 * sizeof(float), stream));
+    }
+    HIP_TRY(launch_tile_order(a.scene, a.frame, ctx->tile_cost.p, ctx->tile_order.p, p.sched, (uint32_t)p.chunks,
+                              (uint32_t)p.blocks * (uint32_t)kThreadsPerBlock, p.cull, stream));
+    a.frame.tile_order = ctx->tile_order.p;
+    if (p.probe) {
+        if (int rc = probe_tiles(ctx, p, a, 0, false, stream)) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->ctrl.p, 0, kCtrlWords * sizeof(uint32_t), stream));
     }
     return DSRT_OK;
 }
 
+// One frame, every tile in the heavy queue, natural order.
+static int prepass_natural(const RenderPlan& p, hipStream_t stream) {
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p.sched, p.t.mine, 2, stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(p.sched + 2), 64, 1, stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(p.sched + 3), p.chunks, 1, stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(p.sched + 4), p.chunk_len, 1, stream));
+    return DSRT_OK;
+}
+
+static int launch_and_resolve(const RenderPlan& p, hipStream_t stream) {
+    const RenderArgs& a = p.a;
+    if (p.pre == PrePass::Batch) HIP_TRY(p.rl->launch_render_batch(a, p.variant.rng_mode, p.blocks, p.variant.lean, stream));
+    else HIP_TRY(p.rl->launch_render(a, p.variant, p.blocks, stream));
+    if (p.own_sums) HIP_TRY(p.rl->launch_resolve(a.accum_fixed, a.frame.spp, a.frame.inv_gamma, p.out_pixels, a.out_rgb8, a.out_f32, nullptr, nullptr, stream));
+    return DSRT_OK;
+}
+
+// The counters of a finished launch (launch_finish has waited for it), as DsrtStats.
+static int read_render_stats(DsrtContext* ctx, const RenderPlan& p, DsrtStats* stats) {
+    uint32_t ctrl[kCtrlWords];
+    HIP_TRY(hipMemcpy(ctrl, ctx->ctrl.p, sizeof ctrl, hipMemcpyDeviceToHost));
+    stats->device_flags = ctrl[1];
+    stats->waves_launched = p.blocks * kWavesPerBlock;
+    stats->lds_stack_entries = kLdsStackEntries;
+    uint64_t cnt[kNumCounters];
+    std::memcpy(cnt, &ctrl[4], sizeof cnt);
+    stats->samples = cnt[C_SAMPLES]; stats->rays = cnt[C_RAYS]; stats->primary_hits = cnt[C_PRIMARY_HITS];
+    stats->box_fetches = cnt[C_BOX_FETCHES]; stats->nodes_entered = cnt[C_NODES_ENTERED]; stats->internal_entered = cnt[C_INTERNAL_ENTERED];
+    stats->tri_tests = cnt[C_TRI_TESTS]; stats->hit_updates = cnt[C_HIT_UPDATES]; stats->sphere_tests = cnt[C_SPHERE_TESTS];
+    stats->shaded_hits = cnt[C_SHADED_HITS]; stats->tex_fetches = cnt[C_TEX_FETCHES]; stats->stack_spills = cnt[C_STACK_SPILLS];
+    stats->max_stack = cnt[C_MAX_STACK];
+    stats->node_slots = cnt[C_NODE_SLOTS]; stats->tri_slots = cnt[C_TRI_SLOTS]; stats->adv_slots = cnt[C_ADV_SLOTS]; stats->adv_active = cnt[C_ADV_ACTIVE];
+    stats->idle_at_leaf = cnt[C_IDLE_AT_LEAF]; stats->idle_waiting = cnt[C_IDLE_WAITING]; stats->idle_done = cnt[C_IDLE_DONE];
+    stats->wave_ticks = cnt[C_WAVE_TICKS];
+    stats->certificate_fallbacks = cnt[C_CERT_FALLBACKS];
+    stats->certificate_audited = cnt[C_AUDITED]; stats->certificate_audit_mismatches = cnt[C_AUDIT_MISMATCHES];
+    stats->certified_tree_used = p.a.accel;
+    {   // time marks relative to the first wave's start, in ms (0 when the mark was never passed)
+        const double t0 = (double)~cnt[C_T_FIRST];
+        stats->heavy_queue_empty_ms = cnt[C_T_HEAVY_EMPTY] ? (float)(((double)~cnt[C_T_HEAVY_EMPTY] - t0) * 1e-5) : 0.0f;
+        stats->light_queue_empty_ms = cnt[C_T_LIGHT_EMPTY] ? (float)(((double)~cnt[C_T_LIGHT_EMPTY] - t0) * 1e-5) : 0.0f;
+        stats->last_wave_exit_ms = cnt[C_T_LAST] ? (float)(((double)cnt[C_T_LAST] - t0) * 1e-5) : 0.0f;
+    }
+    stats->visits_depth_lt6 = cnt[C_VISITS_LT6]; stats->visits_depth_lt9 = cnt[C_VISITS_LT9]; stats->visits_depth_lt12 = cnt[C_VISITS_LT12];
+    uint32_t live = 0;
+    HIP_TRY(hipMemcpy(&live, p.sched + 1, sizeof live, hipMemcpyDeviceToHost));
+    stats->tiles_total = (uint64_t)p.t.mine; stats->tiles_culled = (uint64_t)p.t.mine - live;
+    return DSRT_OK;
+}
+
+static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, void* stream_v, DsrtStats* stats, const BatchInput* batch,
+                       const AccumInput* acc = nullptr) {
+    RenderPlan p;
+    int rc = plan_render(ctx, desc, d_rgb8, d_f32, batch, acc, p);          // every refusal: nothing has been enqueued
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    if ((rc = grow_render_buffers(ctx, p))) return rc;
+    // a context's working buffers serve one render at a time; its own sums (24 bytes per pixel) and its queue, flag and counter words start at zero
+    if ((rc = launch_begin(ctx, stream, {{p.own_sums ? p.a.accum_fixed : nullptr, p.out_pixels * 3 * sizeof(unsigned long long)}, {ctx->ctrl.p, kCtrlWords * sizeof(uint32_t)}}))) return rc;
+    switch (p.pre) {
+        case PrePass::Batch: rc = prepass_batch(ctx, p, *batch, stream); break;
+        case PrePass::Ordered: rc = prepass_ordered(ctx, p, stream); break;
+        case PrePass::Natural: rc = prepass_natural(p, stream); break;
+    }
+    if (rc || (rc = launch_clock(ctx, stream, stats)) || (rc = launch_and_resolve(p, stream)) || (rc = launch_finish(ctx, stream, stats)) || !stats) return rc;
+    if ((rc = read_render_stats(ctx, p, stats))) return rc;
+    return flags_result("render", stats->device_flags);
+}
+
 int dsrt_ctx_scene_bounds(const DsrtContext* ctx, float lo[3], float hi[3]) {
     if (!ctx || !lo || !hi) { set_error("dsrt_ctx_scene_bounds: null argument"); return DSRT_ERR_INVALID; }
-    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_ctx_scene_bounds: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
-    for (int a = 0; a < 3; ++a) { lo[a] = ctx->scene->view.root_lo[a]; hi[a] = ctx->scene->view.root_hi[a]; }
+    const PackedScene* sc = resident_scene(ctx, "dsrt_ctx_scene_bounds");
+    if (!sc) return DSRT_ERR_NO_SCENE;
+    for (int a = 0; a < 3; ++a) { lo[a] = sc->view.root_lo[a]; hi[a] = sc->view.root_hi[a]; }
     return DSRT_OK;
 }
 
@@ -947,15 +1085,9 @@ int dsrt_render_batch_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int 
     return dsrt::guarded("dsrt_render_batch_to_host", [&]() -> int {
     if (!ctx || !desc || !h_rgb8 || frames < 1) { set_error("dsrt_render_batch_to_host: null argument"); return DSRT_ERR_INVALID; }
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)desc->width * desc->height * 3 * (size_t)frames;
-    DevBuf<uint8_t> d8;
-    int rc = d8.alloc(bytes);
-    if (rc) return rc;
+    const Staged s[1] = {{h_rgb8, (size_t)desc->width * desc->height * 3 * (size_t)frames, Dir::Out}};
     DsrtStats local;
-    rc = dsrt_render_batch(ctx, desc, frames, cameras, sun_dirs_xyz, d8.p, nullptr, nullptr, stats ? stats : &local);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(h_rgb8, d8.p, bytes, hipMemcpyDeviceToHost));
-    return DSRT_OK;
+    return staged_call(s, [&](void* const* d) { return dsrt_render_batch(ctx, desc, frames, cameras, sun_dirs_xyz, (uint8_t*)d[0], nullptr, nullptr, stats ? stats : &local); });
     });
 }
 
@@ -965,22 +1097,12 @@ int dsrt_render_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* h
     if (desc->shard_count > 1) { set_error("dsrt_render_to_host renders whole images only"); return DSRT_ERR_INVALID; }
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)desc->width * desc->height;
-    DevBuf<uint8_t> d8;
-    DevBuf<float> d32;
-    int rc = d8.alloc(px * 3);
-    if (rc) return rc;
-    if (h_f32 && (rc = d32.alloc(px * 3))) return rc;
+    const Staged s[2] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}};
     DsrtStats local;
-    rc = dsrt_render(ctx, desc, d8.p, d32.p, nullptr, stats ? stats : &local);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(h_rgb8, d8.p, px * 3, hipMemcpyDeviceToHost));
-    if (h_f32) HIP_TRY(hipMemcpy(h_f32, d32.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return DSRT_OK;
+    return staged_call(s, [&](void* const* d) { return dsrt_render(ctx, desc, (uint8_t*)d[0], (float*)d[1], nullptr, stats ? stats : &local); });
     });
 }
 
-// The G-buffer pass (gbuffer_kernel.hip): the context's camera and sun, the reference tree, one launch.  It reads the resident scene and writes the
-// caller's buffers and one status word of its own; the context's working buffers, camera and sun are not touched.
 // ---- Sample sets (include/dsrt.h, dsrt_render_accumulate): rng_mode 1 sums of any set of a pixel's samples, added into caller-owned buffers ----
 namespace {
 int accum_fail(const char* fn, const char* why) { set_error(std::string(fn) + ": " + why); return DSRT_ERR_INVALID; }
@@ -989,7 +1111,7 @@ int accum_fail(const char* fn, const char* why) { set_error(std::string(fn) + ":
 int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc) {
     if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
     if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL (it is required; sum_sq is the optional one)");
-    if (!ctx->scene || !ctx->scene->valid) { set_error(std::string(fn) + ": no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (!resident_scene(ctx, fn)) return DSRT_ERR_NO_SCENE;
     if (desc->rng_mode != 1) return accum_fail(fn, "sample sets need rng_mode 1 (rng_mode 0 draws a pixel's samples from one serial stream)");
     if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
     if (first < 0) return accum_fail(fn, "first < 0");
@@ -1026,32 +1148,26 @@ int dsrt_render_accumulate(DsrtContext* ctx, const DsrtRenderDesc* desc, int fir
 
 int dsrt_render_accumulate_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_accumulate_to_host", [&]() -> int {
-    int rc = check_accumulate("dsrt_render_accumulate_to_host", ctx, desc, first, count, stride, h_acc);
-    if (rc) return rc;
+    if (int rc = check_accumulate("dsrt_render_accumulate_to_host", ctx, desc, first, count, stride, h_acc)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t words = (size_t)desc->width * desc->height * 3;
-    DevBuf<uint64_t> dsum, dsq;
-    if ((rc = dsum.alloc(words))) return rc;
-    if (h_acc->sum_sq && (rc = dsq.alloc(words))) return rc;
-    HIP_TRY(hipMemcpy(dsum.p, h_acc->sum, words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (h_acc->sum_sq) HIP_TRY(hipMemcpy(dsq.p, h_acc->sum_sq, words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    const DsrtAccum d{dsum.p, dsq.p};
+    const size_t bytes = (size_t)desc->width * desc->height * 3 * sizeof(uint64_t);
+    const Staged s[2] = {{h_acc->sum, bytes, Dir::InOut}, {h_acc->sum_sq, bytes, Dir::InOut}};
     DsrtStats local;
-    if ((rc = dsrt_render_accumulate(ctx, desc, first, count, stride, &d, nullptr, stats ? stats : &local))) return rc;
-    HIP_TRY(hipMemcpy(h_acc->sum, dsum.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (h_acc->sum_sq) HIP_TRY(hipMemcpy(h_acc->sum_sq, dsq.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return DSRT_OK;
+    return staged_call(s, [&](void* const* d) {
+        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
+        return dsrt_render_accumulate(ctx, desc, first, count, stride, &acc, nullptr, stats ? stats : &local);
+    });
     });
 }
 
 int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, uint8_t* d_rgb8, float* d_f32,
                              float* d_var_of_mean, void* stream_v) {
     return dsrt::guarded("dsrt_resolve_accumulated", [&]() -> int {
-    const int rc = check_resolve("dsrt_resolve_accumulated", ctx, desc, acc, samples_done, d_rgb8, d_f32, d_var_of_mean);
+    int rc = check_resolve("dsrt_resolve_accumulated", ctx, desc, acc, samples_done, d_rgb8, d_f32, d_var_of_mean);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
-    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // the context's last launch (an accumulate into these sums, maybe) comes first
+    if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, maybe) comes first
     const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
     const size_t px = (size_t)desc->width * desc->height;
     const unsigned long long* sum = (const unsigned long long*)acc->sum;
@@ -1064,77 +1180,46 @@ int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const
 int dsrt_resolve_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, uint8_t* h_rgb8, float* h_f32,
                                      float* h_var_of_mean) {
     return dsrt::guarded("dsrt_resolve_accumulated_to_host", [&]() -> int {
-    int rc = check_resolve("dsrt_resolve_accumulated_to_host", ctx, desc, h_acc, samples_done, h_rgb8, h_f32, h_var_of_mean);
-    if (rc) return rc;
+    if (int rc = check_resolve("dsrt_resolve_accumulated_to_host", ctx, desc, h_acc, samples_done, h_rgb8, h_f32, h_var_of_mean)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)desc->width * desc->height;
-    DevBuf<uint64_t> dsum, dsq;
-    DevBuf<uint8_t> d8;
-    DevBuf<float> d32, dvar;
-    if ((rc = dsum.alloc(px * 3))) return rc;
-    HIP_TRY(hipMemcpy(dsum.p, h_acc->sum, px * 3 * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (h_var_of_mean) {
-        if ((rc = dsq.alloc(px * 3)) || (rc = dvar.alloc(px * 3))) return rc;
-        HIP_TRY(hipMemcpy(dsq.p, h_acc->sum_sq, px * 3 * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    if (h_rgb8 && (rc = d8.alloc(px * 3))) return rc;
-    if (h_f32 && (rc = d32.alloc(px * 3))) return rc;
-    const DsrtAccum d{dsum.p, dsq.p};
-    if ((rc = dsrt_resolve_accumulated(ctx, desc, &d, samples_done, d8.p, d32.p, dvar.p, nullptr))) return rc;
-    if (h_rgb8) HIP_TRY(hipMemcpy(h_rgb8, d8.p, px * 3, hipMemcpyDeviceToHost));
-    if (h_f32) HIP_TRY(hipMemcpy(h_f32, d32.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (h_var_of_mean) HIP_TRY(hipMemcpy(h_var_of_mean, dvar.p, px * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return DSRT_OK;
+    const Staged s[5] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {h_var_of_mean ? h_acc->sum_sq : nullptr, px * 3 * sizeof(uint64_t), Dir::In},   // (the second
+                         {h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_var_of_mean, px * 3 * sizeof(float), Dir::Out}};              //  moment serves the variance only)
+    return staged_call(s, [&](void* const* d) {
+        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
+        return dsrt_resolve_accumulated(ctx, desc, &acc, samples_done, (uint8_t*)d[2], (float*)d[3], (float*)d[4], nullptr);
+    });
     });
 }
 
+// The G-buffer pass (gbuffer_kernel.hip): the context's camera and sun, the reference tree, one launch.  It reads the resident scene and writes the
+// caller's buffers and one status word of its own; the context's working buffers, camera and sun are not touched.
 int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, void* stream_v, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_gbuffer", [&]() -> int {
     if (!ctx || !desc || !gb) { set_error("dsrt_render_gbuffer: null argument"); return DSRT_ERR_INVALID; }
     if (desc->width < 2 || desc->height < 2) { set_error("dsrt_render_gbuffer: width and height must be at least 2 (the camera divides by W-1 and H-1)"); return DSRT_ERR_INVALID; }
     if (desc->shard_count > 1) { set_error("dsrt_render_gbuffer renders whole images only (shard_count <= 1)"); return DSRT_ERR_INVALID; }
     if ((unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) { set_error("dsrt_render_gbuffer: image too large (2^31 pixels)"); return DSRT_ERR_INVALID; }
-    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render_gbuffer: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    const PackedScene* sc = resident_scene(ctx, "dsrt_render_gbuffer");
+    if (!sc) return DSRT_ERR_NO_SCENE;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const PackedScene& sc = *ctx->scene;
     GBufferArgs a;
     std::memset(&a, 0, sizeof a);
-    a.scene = sc.view;
-    const GPUCamera& c = ctx->camera;
+    a.scene = sc->view;
+    const GPUCamera& c = ctx->frame.camera;
     pack_camera(c, a.cam);
     a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
-    a.sun_dir[0] = ctx->sun_dir.x; a.sun_dir[1] = ctx->sun_dir.y; a.sun_dir[2] = ctx->sun_dir.z;
-    a.sun_enabled = ctx->sun_enabled;
+    a.sun_dir[0] = ctx->frame.sun_dir.x; a.sun_dir[1] = ctx->frame.sun_dir.y; a.sun_dir[2] = ctx->frame.sun_dir.z;
+    a.sun_enabled = ctx->frame.sun_enabled;
     a.width = desc->width; a.height = desc->height;
     a.tiles_x = (desc->width + 7) / 8;
     const int tiles = a.tiles_x * ((desc->height + 7) / 8);
-    a.stack_entries = std::max(1, std::min(64, sc.view.stack_need));       // upload refuses trees that need more than 64
+    a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
     a.t = gb->t; a.range = gb->range; a.depth = gb->depth; a.position = gb->position; a.normal = gb->normal; a.uv = gb->uv; a.albedo = gb->albedo;
     a.prim_id = gb->prim_id; a.material_id = gb->material_id; a.sun_cos = gb->sun_cos; a.flags = gb->flags;
-    if (ctx->gb_status.n < 1) { int rc = ctx->gb_status.alloc(1); if (rc) return rc; }
+    if (int rc = ctx->gb_status.grow(1)) return rc;
     a.status = ctx->gb_status.p;
-    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // one launch at a time per context, as for a render
-    HIP_TRY(hipMemsetAsync(ctx->gb_status.p, 0, sizeof(uint32_t), stream));
-    if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(launch_gbuffer(a, tiles, stream));
-    HIP_TRY(hipEventRecord(ctx->done, stream));
-    ctx->done_valid = true;
-    if (stats) {
-        HIP_TRY(hipEventRecord(ctx->ev1, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        std::memset(stats, 0, sizeof *stats);
-        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, ctx->ev0, ctx->ev1));
-        HIP_TRY(hipMemcpy(&stats->device_flags, ctx->gb_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        stats->waves_launched = tiles;
-        if (stats->device_flags) {
-            char buf[96];
-            std::snprintf(buf, sizeof buf, "G-buffer kernel raised status flags 0x%x", stats->device_flags);
-            set_error(buf);
-            return DSRT_ERR_DEVICE_FLAG;
-        }
-    }
-    return DSRT_OK;
+    return launch_enveloped(ctx, (hipStream_t)stream_v, a.status, stats, "G-buffer", tiles, [&](hipStream_t s) { return launch_gbuffer(a, tiles, s); });
     });
 }
 
@@ -1144,108 +1229,63 @@ int dsrt_render_gbuffer_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, co
     if (desc->width < 2 || desc->height < 2 || desc->shard_count > 1 || (unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) {
         set_error("dsrt_render_gbuffer_to_host: bad size or shard"); return DSRT_ERR_INVALID;
     }
-    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_render_gbuffer_to_host: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (!resident_scene(ctx, "dsrt_render_gbuffer_to_host")) return DSRT_ERR_NO_SCENE;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t px = (size_t)desc->width * desc->height;
-    // one device buffer per channel asked for: {host pointer, bytes per pixel}, in DsrtGBuffer's order
-    void* const host[11] = {gb->t, gb->range, gb->depth, gb->position, gb->normal, gb->uv, gb->albedo, gb->prim_id, gb->material_id, gb->sun_cos, gb->flags};
-    const size_t bpp[11] = {4, 4, 4, 12, 12, 8, 12, 4, 4, 4, 1};
-    DevBuf<uint8_t> dev[11];
-    void* d[11] = {nullptr};
-    for (int i = 0; i < 11; ++i)
-        if (host[i]) { int rc = dev[i].alloc(px * bpp[i]); if (rc) return rc; d[i] = dev[i].p; }
-    DsrtGBuffer dg;
-    dg.t = (float*)d[0]; dg.range = (float*)d[1]; dg.depth = (float*)d[2]; dg.position = (float*)d[3]; dg.normal = (float*)d[4]; dg.uv = (float*)d[5];
-    dg.albedo = (float*)d[6]; dg.prim_id = (int32_t*)d[7]; dg.material_id = (int32_t*)d[8]; dg.sun_cos = (float*)d[9]; dg.flags = (uint8_t*)d[10];
+    Staged s[11];
+    channels(*gb, kGBufferBytes, (size_t)desc->width * desc->height, Dir::Out, s);
     DsrtStats local;
-    int rc = dsrt_render_gbuffer(ctx, desc, &dg, nullptr, stats ? stats : &local);
-    if (rc) return rc;
-    for (int i = 0; i < 11; ++i)
-        if (host[i]) HIP_TRY(hipMemcpy(host[i], d[i], px * bpp[i], hipMemcpyDeviceToHost));
-    return DSRT_OK;
+    return staged_call(s, [&](void* const* d) {
+        const DsrtGBuffer dg = pointers_as<DsrtGBuffer>(d);
+        return dsrt_render_gbuffer(ctx, desc, &dg, nullptr, stats ? stats : &local);
+    });
     });
 }
 
 int dsrt_trace_rays(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, void* stream_v, DsrtStats* stats) {
     return dsrt::guarded("dsrt_trace_rays", [&]() -> int {
     if (int rc = check_trace_args("dsrt_trace_rays", ctx, count, rays, mode, hits)) return rc;
-    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_trace_rays: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    const PackedScene* sc = resident_scene(ctx, "dsrt_trace_rays");
+    if (!sc) return DSRT_ERR_NO_SCENE;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (count == 0) return DSRT_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const PackedScene& sc = *ctx->scene;
     const bool any_hit = mode == DSRT_TRACE_ANY;
     RaycastArgs a;
     std::memset(&a, 0, sizeof a);
-    a.scene = sc.view;
+    a.scene = sc->view;
     a.origins = rays->origins; a.dirs = rays->dirs; a.t_min = rays->t_min; a.t_max = rays->t_max;
     a.count = count;
-    a.stack_entries = std::max(1, std::min(64, sc.view.stack_need));       // upload refuses trees that need more than 64
+    a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
     a.t = hits->t; a.range = hits->range; a.position = hits->position; a.normal = hits->normal; a.uv = hits->uv; a.albedo = hits->albedo;
     a.prim_id = hits->prim_id; a.material_id = hits->material_id; a.flags = hits->flags;
-    if (ctx->rc_status.n < 1) { int rc = ctx->rc_status.alloc(1); if (rc) return rc; }
+    if (int rc = ctx->rc_status.grow(1)) return rc;
     a.status = ctx->rc_status.p;
     const int blocks = (int)(((size_t)count + 63) / 64);                   // one lane per ray
-    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));     // one launch at a time per context, as for a render
-    HIP_TRY(hipMemsetAsync(ctx->rc_status.p, 0, sizeof(uint32_t), stream));
-    if (stats) HIP_TRY(hipEventRecord(ctx->ev0, stream));
-    HIP_TRY(launch_raycast(a, any_hit, blocks, stream));
-    HIP_TRY(hipEventRecord(ctx->done, stream));
-    ctx->done_valid = true;
-    if (stats) {
-        HIP_TRY(hipEventRecord(ctx->ev1, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, ctx->ev0, ctx->ev1));
-        HIP_TRY(hipMemcpy(&stats->device_flags, ctx->rc_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        stats->waves_launched = blocks;
-        if (stats->device_flags) {
-            char buf[96];
-            std::snprintf(buf, sizeof buf, "ray query kernel raised status flags 0x%x", stats->device_flags);
-            set_error(buf);
-            return DSRT_ERR_DEVICE_FLAG;
-        }
-    }
-    return DSRT_OK;
+    return launch_enveloped(ctx, (hipStream_t)stream_v, a.status, stats, "ray query", blocks, [&](hipStream_t s) { return launch_raycast(a, any_hit, blocks, s); });
     });
 }
 
 int dsrt_trace_rays_to_host(DsrtContext* ctx, int count, const DsrtRays* rays, int mode, const DsrtRayHits* hits, DsrtStats* stats) {
     return dsrt::guarded("dsrt_trace_rays_to_host", [&]() -> int {
     if (int rc = check_trace_args("dsrt_trace_rays_to_host", ctx, count, rays, mode, hits)) return rc;
-    if (!ctx->scene || !ctx->scene->valid) { set_error("dsrt_trace_rays_to_host: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (!resident_scene(ctx, "dsrt_trace_rays_to_host")) return DSRT_ERR_NO_SCENE;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (count == 0) return DSRT_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = (size_t)count;
-    // inputs {host pointer, bytes}, then the channels in DsrtRayHits' order
-    const void* const hin[4] = {rays->origins, rays->dirs, rays->t_min, rays->t_max};
-    const size_t bin[4] = {n * 12, n * 12, n * 4, n * 4};
-    void* const hout[9] = {hits->t, hits->range, hits->position, hits->normal, hits->uv, hits->albedo, hits->prim_id, hits->material_id, hits->flags};
-    const size_t bout[9] = {n * 4, n * 4, n * 12, n * 12, n * 8, n * 12, n * 4, n * 4, n};
-    DevBuf<uint8_t> din[4], dout[9];
-    void* di[4] = {nullptr};
-    void* dd[9] = {nullptr};
-    for (int i = 0; i < 4; ++i)
-        if (hin[i]) { int rc = din[i].alloc(bin[i]); if (rc) return rc; di[i] = din[i].p; HIP_TRY(hipMemcpy(di[i], hin[i], bin[i], hipMemcpyHostToDevice)); }
-    for (int i = 0; i < 9; ++i)
-        if (hout[i]) { int rc = dout[i].alloc(bout[i]); if (rc) return rc; dd[i] = dout[i].p; }
-    DsrtRays dr;
-    dr.origins = (const float*)di[0]; dr.dirs = (const float*)di[1]; dr.t_min = (const float*)di[2]; dr.t_max = (const float*)di[3];
-    DsrtRayHits dh;
-    dh.t = (float*)dd[0]; dh.range = (float*)dd[1]; dh.position = (float*)dd[2]; dh.normal = (float*)dd[3]; dh.uv = (float*)dd[4]; dh.albedo = (float*)dd[5];
-    dh.prim_id = (int32_t*)dd[6]; dh.material_id = (int32_t*)dd[7]; dh.flags = (uint8_t*)dd[8];
+    Staged s[4 + 9];
+    channels(*rays, kRayBytes, (size_t)count, Dir::In, s);
+    channels(*hits, kRayHitBytes, (size_t)count, Dir::Out, s + 4);
     DsrtStats local;
-    int rc = dsrt_trace_rays(ctx, count, &dr, mode, &dh, nullptr, stats ? stats : &local);
-    if (rc) return rc;
-    for (int i = 0; i < 9; ++i)
-        if (hout[i]) HIP_TRY(hipMemcpy(hout[i], dd[i], bout[i], hipMemcpyDeviceToHost));
-    return DSRT_OK;
+    return staged_call(s, [&](void* const* d) {
+        const DsrtRays dr = pointers_as<DsrtRays>(d);
+        const DsrtRayHits dh = pointers_as<DsrtRayHits>(d + 4);
+        return dsrt_trace_rays(ctx, count, &dr, mode, &dh, nullptr, stats ? stats : &local);
+    });
     });
 }
 
 int dsrt_selftest_poke_node_word(DsrtContext* ctx, size_t word_index, uint32_t value, uint32_t* old_value) {
-    if (!ctx || !ctx->scene || !ctx->scene->valid) { set_error("dsrt_selftest_poke_node_word: no scene uploaded"); return DSRT_ERR_NO_SCENE; }
+    if (!resident_scene(ctx, "dsrt_selftest_poke_node_word")) return DSRT_ERR_NO_SCENE;
     if (word_index >= ctx->scene->pairs.n * 4) { set_error("dsrt_selftest_poke_node_word: word index beyond the node records"); return DSRT_ERR_INVALID; }
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -1327,13 +1367,13 @@ int fingerprint_device_scene(const GPUScene& d, SceneFingerprint& fp) {
     for (int c : counts) if (c < 0) { set_error("scene has a negative count"); return DSRT_ERR_INVALID; }
     if (!g_dropin_hash) HIP_TRY(hipMalloc((void**)&g_dropin_hash, 2 * sizeof(uint64_t)));
     HIP_TRY(hipMemsetAsync(g_dropin_hash, 0, 2 * sizeof(uint64_t), nullptr));
-    struct Arr { const void* p; size_t bytes; } arrs[7] = {
-        {d.triangles, (size_t)d.num_triangles * sizeof(GPUTriangle)}, {d.spheres, (size_t)d.num_spheres * sizeof(GPUSphere)},
-        {d.materials, (size_t)d.num_materials * sizeof(GPUMaterial)}, {d.bvh_nodes, (size_t)d.num_bvh_nodes * sizeof(GPUBVHNode)},
-        {d.textures, (size_t)d.num_textures * sizeof(GPUTextureHeader)}, {d.texture_pool, (size_t)d.texture_pool_floats * sizeof(float)},
-        {d.tri_indices, d.tri_indices ? (size_t)d.num_triangles * sizeof(int) : 0}};
-    for (int a = 0; a < 7; ++a)
-        if (arrs[a].p && arrs[a].bytes) HIP_TRY(launch_content_hash((const uint32_t*)arrs[a].p, arrs[a].bytes / 4, 0x9E3779B97F4A7C15ull * (uint64_t)(a + 1), g_dropin_hash, nullptr));
+    int k = 0;                                                             // every array's salt: its place in the walk
+    const int rc = for_each_scene_array(d, [&](const auto* p, size_t n) -> int {
+        ++k;
+        if (n) HIP_TRY(launch_content_hash((const uint32_t*)p, n * sizeof(*p) / 4, 0x9E3779B97F4A7C15ull * (uint64_t)k, g_dropin_hash, nullptr));
+        return DSRT_OK;
+    });
+    if (rc) return rc;
     HIP_TRY(hipMemcpy(fp.h, g_dropin_hash, sizeof fp.h, hipMemcpyDeviceToHost));
     fp.valid = true;
     return DSRT_OK;
@@ -1351,7 +1391,7 @@ DsrtContext* dropin_context() {
 
 int dsrt_dropin_has_certified_tree(void) {
     std::lock_guard<std::mutex> lock(g_dropin_mutex);
-    return g_dropin_ctx && g_dropin_ctx->scene && g_dropin_ctx->scene->valid && g_dropin_ctx->scene->has_second_tree ? 1 : 0;
+    return dsrt_ctx_has_certified_tree(g_dropin_ctx);
 }
 
 int dsrt_build_gpu_scene(const DsrtHostScene* hs, const GPUCamera* cam, const float sun_dir_model[3], GPUScene* out) {
@@ -1361,23 +1401,22 @@ int dsrt_build_gpu_scene(const DsrtHostScene* hs, const GPUCamera* cam, const fl
     int rc = dsrt_host_scene_view(hs, &h);
     if (rc) return rc;
     dsrt_scene_set_frame(&h, cam, sun_dir_model);
-    // The returned header carries DEVICE arrays in the reference layouts, like the reference's own builder.
+    // The returned header carries DEVICE arrays in the reference layouts, like the reference's own builder.  A failure frees what was pushed before it
+    // and leaves *out as it was.
     GPUScene d = h;
-    auto push = [&](const void* src, size_t bytes, void** dst) -> int {
-        *dst = nullptr;
-        if (!bytes) return DSRT_OK;
-        HIP_TRY(hipMalloc(dst, bytes));
-        HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    void* pushed[kSceneArrays];
+    size_t n_pushed = 0;
+    rc = for_each_scene_array(d, [&](auto*& p, size_t n) -> int {
+        const void* src = p;
+        p = nullptr;
+        if (!n) return DSRT_OK;
+        HIP_TRY(hipMalloc((void**)&p, n * sizeof(*p)));
+        assert(n_pushed < kSceneArrays);
+        pushed[n_pushed++] = (void*)p;
+        HIP_TRY(hipMemcpy((void*)p, src, n * sizeof(*p), hipMemcpyHostToDevice));
         return DSRT_OK;
-    };
-    void* p = nullptr;
-    if ((rc = push(h.triangles, (size_t)h.num_triangles * sizeof(GPUTriangle), &p))) return rc; d.triangles = (const GPUTriangle*)p;
-    if ((rc = push(h.spheres, (size_t)h.num_spheres * sizeof(GPUSphere), &p))) return rc; d.spheres = (const GPUSphere*)p;
-    if ((rc = push(h.materials, (size_t)h.num_materials * sizeof(GPUMaterial), &p))) return rc; d.materials = (const GPUMaterial*)p;
-    if ((rc = push(h.tri_indices, (size_t)(h.tri_indices ? h.num_triangles : 0) * sizeof(int), &p))) return rc; d.tri_indices = (const int*)p; d.bvh_tri_indices = (int*)p;
-    if ((rc = push(h.bvh_nodes, (size_t)h.num_bvh_nodes * sizeof(GPUBVHNode), &p))) return rc; d.bvh_nodes = (GPUBVHNode*)p;
-    if ((rc = push(h.textures, (size_t)h.num_textures * sizeof(GPUTextureHeader), &p))) return rc; d.textures = (const GPUTextureHeader*)p;
-    if ((rc = push(h.texture_pool, (size_t)h.texture_pool_floats * sizeof(float), &p))) return rc; d.texture_pool = (const float*)p;
+    });
+    if (rc) { while (n_pushed) (void)hipFree(pushed[--n_pushed]); return rc; }
     *out = d;
     return DSRT_OK;
     });
@@ -1385,20 +1424,8 @@ int dsrt_build_gpu_scene(const DsrtHostScene* hs, const GPUCamera* cam, const fl
 
 void dsrt_free_gpu_scene(GPUScene* s) {                                  // src/gpu_scene_builder.cpp:603-626
     if (!s) return;
-    if (s->triangles) (void)hipFree((void*)s->triangles);
-    if (s->spheres) (void)hipFree((void*)s->spheres);
-    if (s->materials) (void)hipFree((void*)s->materials);
-    if (s->bvh_nodes) (void)hipFree((void*)s->bvh_nodes);
-    if (s->tri_indices) (void)hipFree((void*)s->tri_indices);
-    if (s->textures) (void)hipFree((void*)s->textures);
-    if (s->texture_pool) (void)hipFree((void*)s->texture_pool);
-    s->triangles = nullptr; s->num_triangles = 0;
-    s->spheres = nullptr; s->num_spheres = 0;
-    s->materials = nullptr; s->num_materials = 0;
-    s->bvh_nodes = nullptr; s->num_bvh_nodes = 0;
-    s->tri_indices = nullptr; s->bvh_tri_indices = nullptr;
-    s->textures = nullptr; s->num_textures = 0;
-    s->texture_pool = nullptr; s->texture_pool_floats = 0;
+    for_each_scene_array(*s, [](auto*& p, size_t) -> int { if (p) (void)hipFree((void*)p); p = nullptr; return DSRT_OK; });
+    s->num_triangles = s->num_spheres = s->num_materials = s->num_bvh_nodes = s->num_textures = s->texture_pool_floats = 0;
 }
 
 void gpu_render_scene(const GPUScene* scene, int width, int height) {
@@ -1415,10 +1442,9 @@ static void gpu_render_scene_body(const GPUScene* scene, int width, int height) 
     // The reference's entry point has nowhere to ask for the certified second tree either: DSRT_CERTIFIED_TREE=1, looked at on every call here (the one context of the
     // drop-in lives as long as the process); a change of the variable re-converts the scene.
     { const char* e = std::getenv("DSRT_CERTIFIED_TREE"); ctx->want_second_tree = e && e[0] == '1'; }
-    if (ctx->scene && ctx->scene->valid && fp == g_dropin_fp && ctx->scene->has_second_tree == (ctx->want_second_tree && ctx->scene->view.root_ref != kRefNone)) {
+    if (scene_of(ctx) && fp == g_dropin_fp && ctx->scene->has_second_tree == (ctx->want_second_tree && ctx->scene->view.root_ref != kRefNone)) {
         // same geometry, materials and textures as the previous call: only the per-frame part of the header is taken over
-        ctx->camera = scene->camera;
-        ctx->sun_dir = scene->sun_dir; ctx->sun_radiance = scene->sun_radiance; ctx->sun_enabled = scene->sun_enabled ? 1 : 0;
+        ctx->frame = frame_of(*scene);
     } else {
         g_dropin_fp.valid = false;
         if (dsrt_scene_upload_device(ctx, scene) != DSRT_OK) { std::fprintf(stderr, "gpu_render_scene: scene upload failed: %s\n", dsrt_last_error()); return; }

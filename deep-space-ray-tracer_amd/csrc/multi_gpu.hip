@@ -32,22 +32,18 @@
 
 #include "../../include/dsrt.h"
 #include "../host/host_internal.hpp"
+#include "hip_check.h"
 
+using dsrt::hip_ok;
 using dsrt::set_error;
 
 namespace {
 
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return false;
-}
 bool nccl_ok(ncclResult_t r, const char* what) {
     if (r == ncclSuccess) return true;
     set_error(std::string(what) + ": " + ncclGetErrorString(r));
     return false;
 }
-#define HIP_TRY(expr) do { if (!hip_ok((expr), #expr)) return DSRT_ERR_HIP; } while (0)
 #define NCCL_TRY(expr) do { if (!nccl_ok((expr), #expr)) return DSRT_ERR_COMM; } while (0)
 
 struct Slot {                       // one frame in flight on one rank
