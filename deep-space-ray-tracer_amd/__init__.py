@@ -503,6 +503,83 @@ class Context:
                                             C.c_void_p(self._raw_stream(stream))), "dsrt_resolve_accumulated")
         return rgb, f32, var
 
+    # ---- adaptive sampling (include/dsrt.h, ADAPTIVE SAMPLING): masked sample sets, the convergence test, the per-pixel resolve, the driver ----
+    def _pixel_tensor(self, desc, x, dtype, what, required=True):
+        if x is None:
+            if required:
+                raise ValueError(f"{what} is required")
+            return None
+        if _torch is None or not isinstance(x, _torch.Tensor):
+            raise TypeError(f"{what} must be a torch tensor")
+        if x.dtype != dtype:
+            raise TypeError(f"{what} must be {dtype}, not {x.dtype}")
+        if x.device.type != "cuda" or x.device.index != self.device:
+            raise ValueError(f"{what} is on {x.device}, the context is on cuda:{self.device}")
+        if not x.is_contiguous() or x.numel() != desc.width * desc.height:
+            raise ValueError(f"{what} must be contiguous with width*height = {desc.width * desc.height} elements")
+        return x
+
+    def render_accumulate_masked(self, desc, first, count, stride=1, sums=None, sum_sq=None, mask=None, n=None, stream=None, want_stats=False):
+        """dsrt_render_accumulate_masked: render_accumulate for the pixels whose byte of `mask` (uint8 device tensor, width*height, image order) is nonzero;
+        `n` (optional int32 device tensor, width*height: the pixels' sample counts) gets `count` added where the mask is set."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=False)
+        mask = self._pixel_tensor(desc, mask, _torch.uint8, "mask")
+        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
+        acc = DsrtAccum(C.c_void_p(sums.data_ptr()), C.c_void_p(sum_sq.data_ptr()) if sum_sq is not None else None)
+        st = DsrtStats() if want_stats else None
+        _check(lib.dsrt_render_accumulate_masked(self._h, C.byref(desc), int(first), int(count), int(stride), C.byref(acc), C.c_void_p(mask.data_ptr()),
+                                                 C.c_void_p(n.data_ptr()) if n is not None else None, C.c_void_p(self._raw_stream(stream)),
+                                                 C.byref(st) if st is not None else None), "dsrt_render_accumulate_masked")
+        return st
+
+    def select_unconverged(self, desc, sums, sum_sq, n, rel_tol, floor=0.0, n_min=0, n_max=0xFFFFFFFF, mask=None, want_active=True, stream=None):
+        """dsrt_select_unconverged: (mask, active) -- the uint8 device tensor (height, width) of the pixels that still need samples (written into `mask` if one is
+        given) and how many they are (None without want_active: then the call does not synchronise)."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq")
+        n = self._pixel_tensor(desc, n, _torch.int32, "n")
+        mask = _torch.empty((desc.height, desc.width), dtype=_torch.uint8, device=sums.device) if mask is None else self._pixel_tensor(desc, mask, _torch.uint8, "mask")
+        acc = DsrtAccum(C.c_void_p(sums.data_ptr()), C.c_void_p(sum_sq.data_ptr()))
+        active = C.c_uint32(0)
+        _check(lib.dsrt_select_unconverged(self._h, C.byref(desc), C.byref(acc), C.c_void_p(n.data_ptr()), float(rel_tol), float(floor), int(n_min), int(n_max),
+                                           C.c_void_p(mask.data_ptr()), C.byref(active) if want_active else None, C.c_void_p(self._raw_stream(stream))),
+               "dsrt_select_unconverged")
+        return mask, (active.value if want_active else None)
+
+    def resolve_accumulated_counts(self, desc, sums, n, sum_sq=None, want_rgb8=True, want_f32=False, want_var=False, stream=None):
+        """dsrt_resolve_accumulated_counts: resolve_accumulated with every pixel's own sample count `n` (int32 device tensor) in place of samples_done."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=want_var)
+        n = self._pixel_tensor(desc, n, _torch.int32, "n")
+        shape, dev = (desc.height, desc.width, 3), sums.device
+        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
+        f32 = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_f32 else None
+        var = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_var else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
+        _check(lib.dsrt_resolve_accumulated_counts(self._h, C.byref(desc), C.byref(acc), ptr(n), ptr(rgb), ptr(f32), ptr(var),
+                                                   C.c_void_p(self._raw_stream(stream))), "dsrt_resolve_accumulated_counts")
+        return rgb, f32, var
+
+    def render_adaptive(self, desc, rel_tol, passes=8, min_passes=2, floor=0.0, want_rgb8=True, want_f32=False, want_var=False, stream=None):
+        """dsrt_render_adaptive: the frame in up to `passes` interleaved passes, each pass from min_passes on over the pixels that have not converged to rel_tol.
+        Returns (acc, (rgb8, f32, var), stats): the Accumulator holding the sums and the per-pixel counts `acc.n`, the images asked for, and a dict with
+        passes_run, samples_total and active (pixels rendered by each pass that ran)."""
+        acc = Accumulator(self, desc, moments=True, counts=True)
+        shape, dev = (desc.height, desc.width, 3), acc.sum.device
+        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
+        f32 = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_f32 else None
+        var = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_var else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+        a = DsrtAccum(ptr(acc.sum), ptr(acc.sum_sq))
+        ad = capi.DsrtAdaptive(int(passes), int(min_passes), float(rel_tol), float(floor))
+        st = capi.DsrtAdaptiveStats()
+        _check(lib.dsrt_render_adaptive(self._h, C.byref(desc), C.byref(ad), C.byref(a), ptr(acc.n), ptr(rgb), ptr(f32), ptr(var),
+                                        C.c_void_p(self._raw_stream(stream)), C.byref(st)), "dsrt_render_adaptive")
+        acc.samples_done = None                    # the counts are per pixel now: acc.resolve_counts(), not acc.resolve()
+        return acc, (rgb, f32, var), {"passes_run": st.passes_run, "samples_total": st.samples_total, "active": list(st.active[:st.passes_run])}
+
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""
         old = C.c_uint32()
@@ -539,13 +616,15 @@ class Accumulator:
             rgb, _, var = acc.resolve(want_var=True)
     """
 
-    def __init__(self, ctx, desc, moments=False):
+    def __init__(self, ctx, desc, moments=False, counts=False):
         if desc.rng_mode != 1:
             raise ValueError("sample sets are rng_mode 1's")
         self.ctx, self.desc = ctx, desc
         n = desc.width * desc.height * 3
         self.sum = _torch.zeros(n, dtype=_torch.int64, device=f"cuda:{ctx.device}")
         self.sum_sq = _torch.zeros(n, dtype=_torch.int64, device=f"cuda:{ctx.device}") if moments else None
+        # per-pixel sample counts (adaptive sampling: masked sets give pixels different counts), int32 (height, width); None = every pixel has samples_done
+        self.n = _torch.zeros((desc.height, desc.width), dtype=_torch.int32, device=f"cuda:{ctx.device}") if counts else None
         self.samples_done = 0
 
     @staticmethod
@@ -553,12 +632,25 @@ class Accumulator:
         """Samples in the set {first, first + stride, ...} below spp."""
         return len(range(first, spp, stride))
 
-    def render(self, first, count=None, stride=1, ctx=None, stream=None, want_stats=False):
-        """Add the set {first + j*stride : 0 <= j < count} (count: all of them below spp by default) and count its samples."""
+    def render(self, first, count=None, stride=1, ctx=None, stream=None, want_stats=False, mask=None):
+        """Add the set {first + j*stride : 0 <= j < count} (count: all of them below spp by default) and count its samples.  With `mask` (uint8 device
+        tensor, nonzero = active) only for the active pixels: the accumulator then keeps per-pixel counts (`n`) and is resolved with resolve_counts()."""
         count = self.pass_count(self.desc.spp, first, stride) if count is None else count
-        st = (ctx or self.ctx).render_accumulate(self.desc, first, count, stride, self.sum, self.sum_sq, stream=stream, want_stats=want_stats)
-        self.samples_done += count
-        return st
+        if mask is None:
+            st = (ctx or self.ctx).render_accumulate(self.desc, first, count, stride, self.sum, self.sum_sq, stream=stream, want_stats=want_stats)
+            if self.n is not None:                  # behind the launch, on its stream (torch's current one unless another was given)
+                if not stream:
+                    self.n += count
+                else:
+                    with _torch.cuda.stream(stream if isinstance(stream, _torch.cuda.Stream) else _torch.cuda.ExternalStream(int(stream))):
+                        self.n += count
+            if self.samples_done is not None:
+                self.samples_done += count
+            return st
+        if self.n is None:                          # the first masked set: until now every pixel had samples_done samples
+            self.n = _torch.full((self.desc.height, self.desc.width), self.samples_done, dtype=_torch.int32, device=self.sum.device)
+        self.samples_done = None
+        return (ctx or self.ctx).render_accumulate_masked(self.desc, first, count, stride, self.sum, self.sum_sq, mask, self.n, stream=stream, want_stats=want_stats)
 
     def __iadd__(self, other):
         d, o = self.desc, other.desc
@@ -566,6 +658,8 @@ class Accumulator:
             raise ValueError("accumulators of different frames (width, height, spp or seed differ)")
         if self.sum_sq is not None and other.sum_sq is None:
             raise ValueError("this accumulator sums squared samples and the other does not")
+        if self.n is not None or other.n is not None or self.samples_done is None or other.samples_done is None:
+            raise ValueError("accumulators with per-pixel counts are not added (add their sum and n tensors)")
         self.sum += other.sum.to(self.sum.device)
         if self.sum_sq is not None:
             self.sum_sq += other.sum_sq.to(self.sum_sq.device)
@@ -574,7 +668,15 @@ class Accumulator:
 
     def resolve(self, want_rgb8=True, want_f32=False, want_var=False, stream=None):
         """(rgb8, f32, var) device tensors of the current sums (Context.resolve_accumulated)."""
+        if self.samples_done is None:
+            raise ValueError("this accumulator holds masked sets (per-pixel counts): resolve_counts()")
         return self.ctx.resolve_accumulated(self.desc, self.sum, self.samples_done, self.sum_sq if want_var else None, want_rgb8, want_f32, want_var, stream)
+
+    def resolve_counts(self, want_rgb8=True, want_f32=False, want_var=False, stream=None):
+        """(rgb8, f32, var) of the current sums with every pixel's own count `n` (Context.resolve_accumulated_counts)."""
+        if self.n is None:
+            raise ValueError("this accumulator has no per-pixel counts (counts=True, or a masked render)")
+        return self.ctx.resolve_accumulated_counts(self.desc, self.sum, self.n, self.sum_sq if want_var else None, want_rgb8, want_f32, want_var, stream)
 
 
 class Multi:

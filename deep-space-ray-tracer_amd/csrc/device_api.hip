@@ -340,6 +340,9 @@ struct DsrtContext {
     DevBuf<BatchFrame> batch_table;  // dsrt_render_batch: one entry per frame
     std::vector<BatchFrame> batch_host;
     DevBuf<unsigned long long> accum_fixed;
+    DevBuf<uint32_t> pixel_list;    // dsrt_render_accumulate_masked: the lists of active pixels (one entry per pixel of the shard's tiles)
+    DevBuf<uint32_t> active_count;  // dsrt_select_unconverged: the word h_active is read from
+    DevBuf<uint8_t> adaptive_mask;  // dsrt_render_adaptive: the mask between its passes
     DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
     DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -363,6 +366,8 @@ int install_scene(DsrtContext* ctx, const GPUScene& host_layout) {
 
 constexpr size_t kQueueLightWord = 96;                       // the light queue's counter: its own cache line, past the counters
 constexpr size_t kCtrlWords = kQueueLightWord + 16;
+constexpr size_t kListLenSched = 8;                          // masked accumulate launches: the lengths of the heavy and the light list (path_machine.h, LISTED) are words 8 and 9 of
+                                                             // the pre-pass's sched block, next to the words every fetch reads anyway and away from the queue words' atomics
 static_assert(4 + 2 * (size_t)kNumCounters <= kQueueLightWord, "counters overlap the second queue word");
 
 struct Tiling { int tile, tiles_x, tiles_y, total, mine, padded; };
@@ -681,7 +686,8 @@ int dsrt_shard_layout(const DsrtRenderDesc* desc, int* tiles_total, int* tiles_t
 struct BatchInput { int frames; const GPUCamera* cameras; const DsrtF3* sun_dirs; };
 // What an accumulate launch changes (dsrt_render_accumulate, checked there): the samples rendered -- {first + j*stride : 0 <= j < count} of a frame
 // planned at desc->spp -- and where their sums go (the caller's buffers, added to, never cleared; no resolve).
-struct AccumInput { int first, count, stride; unsigned long long* sum; unsigned long long* sum_sq; };
+// mask (dsrt_render_accumulate_masked; null = every pixel): only the pixels whose byte is set; n (optional): their sample counts, `count` added.
+struct AccumInput { int first, count, stride; unsigned long long* sum; unsigned long long* sum_sq; const uint8_t* mask; uint32_t* n; };
 
 // ---- A render launch (dsrt_render, dsrt_render_batch, dsrt_render_accumulate), in stages: plan_render refuses or decides everything, without a HIP call;
 // grow_render_buffers sizes the context's working buffers; one of the three pre-passes orders the tiles; launch_and_resolve; read_render_stats. ----
@@ -867,7 +873,7 @@ static int plan_render(const DsrtContext* ctx, const DsrtRenderDesc* desc, uint8
     v = RenderVariant{};
     v.rng_mode = desc->rng_mode;
     v.count = count; v.checked = count || desc->checked != 0; v.anyhit = desc->collect_counters != 2;
-    v.lean = lean; v.sets = acc != nullptr; v.moments = acc && acc->sum_sq;
+    v.lean = lean; v.sets = acc != nullptr; v.moments = acc && acc->sum_sq; v.listed = acc && acc->mask;
     return DSRT_OK;
 }
 
@@ -885,8 +891,14 @@ static int grow_render_buffers(DsrtContext* ctx, RenderPlan& p) {
         (rc = ctx->tile_work.grow(p.pre_stride)) || (rc = ctx->tile_tmp.grow(p.pre_stride))) return rc;
     if (p.pre == PrePass::Batch && (rc = ctx->batch_table.grow(2 * (size_t)p.frames))) return rc;
     if (p.probe && (rc = ctx->probe_queue.grow(1024))) return rc;
+    if (p.variant.listed) {
+        const size_t tile_pixels = (size_t)p.t.mine * (size_t)(p.t.tile * p.t.tile);     // the two lists, and a word per 8x8 block behind them (launch_pixel_list)
+        if ((rc = ctx->pixel_list.grow(tile_pixels + tile_pixels / 64))) return rc;
+        a.list = ctx->pixel_list.p;
+    }
     p.sched = ctx->tile_cost.p + p.t.mine + 32;
     a.sched = p.sched;
+    if (p.variant.listed) a.list_len = p.sched + kListLenSched;
     return DSRT_OK;
 }
 
@@ -1029,6 +1041,9 @@ static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_
         case PrePass::Ordered: rc = prepass_ordered(ctx, p, stream); break;
         case PrePass::Natural: rc = prepass_natural(p, stream); break;
     }
+    // a masked launch: the lists of active pixels, from the mask and the order the pre-pass has just left (and the sample counts of those pixels)
+    if (!rc && p.variant.listed)
+        HIP_TRY(launch_pixel_list(p.a.frame, p.a.frame.tile_order, p.sched, acc->mask, ctx->pixel_list.p, p.sched + kListLenSched, acc->n, (uint32_t)acc->count, stream));
     if (rc || (rc = launch_clock(ctx, stream, stats)) || (rc = launch_and_resolve(p, stream)) || (rc = launch_finish(ctx, stream, stats)) || !stats) return rc;
     if ((rc = read_render_stats(ctx, p, stats))) return rc;
     return flags_result("render", stats->device_flags);
@@ -1107,10 +1122,8 @@ int dsrt_render_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* h
 namespace {
 int accum_fail(const char* fn, const char* why) { set_error(std::string(fn) + ": " + why); return DSRT_ERR_INVALID; }
 
-// Everything dsrt_render_accumulate refuses, checked before anything is launched or written.
-int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc) {
-    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
-    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL (it is required; sum_sq is the optional one)");
+// Everything dsrt_render_accumulate refuses, checked before anything is launched or written: of the context, the frame and the set (ctx and desc are given) ...
+int check_sample_set(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride) {
     if (!resident_scene(ctx, fn)) return DSRT_ERR_NO_SCENE;
     if (desc->rng_mode != 1) return accum_fail(fn, "sample sets need rng_mode 1 (rng_mode 0 draws a pixel's samples from one serial stream)");
     if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
@@ -1120,6 +1133,13 @@ int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDes
     const long long spp = desc->spp < 1 ? 1 : desc->spp;
     if ((long long)first + (long long)(count - 1) * (long long)stride >= spp) return accum_fail(fn, "the set reaches past the frame's planned samples (first + (count - 1) * stride >= spp)");
     return DSRT_OK;
+}
+
+// ... and of the sums.
+int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc) {
+    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
+    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL (it is required; sum_sq is the optional one)");
+    return check_sample_set(fn, ctx, desc, first, count, stride);
 }
 
 int check_resolve(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const void* rgb8, const void* f32, const void* var) {
@@ -1141,7 +1161,7 @@ int dsrt_render_accumulate(DsrtContext* ctx, const DsrtRenderDesc* desc, int fir
     return dsrt::guarded("dsrt_render_accumulate", [&]() -> int {
     const int rc = check_accumulate("dsrt_render_accumulate", ctx, desc, first, count, stride, acc);
     if (rc) return rc;
-    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq};
+    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq, nullptr, nullptr};
     return render_impl(ctx, desc, nullptr, nullptr, stream, stats, nullptr, &in);
     });
 }
@@ -1189,6 +1209,175 @@ int dsrt_resolve_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* des
         const DsrtAccum acc = pointers_as<DsrtAccum>(d);
         return dsrt_resolve_accumulated(ctx, desc, &acc, samples_done, (uint8_t*)d[2], (float*)d[3], (float*)d[4], nullptr);
     });
+    });
+}
+
+// ---- Adaptive sampling (include/dsrt.h, ADAPTIVE SAMPLING): masked sample sets, the convergence test that makes the masks, the per-pixel resolve, the driver ----
+namespace {
+int check_masked_desc(const char* fn, const DsrtRenderDesc* desc) {
+    if (desc->collect_counters != 0) return accum_fail(fn, "masked launches use the production and checked kernels only (collect_counters must be 0)");
+    return DSRT_OK;
+}
+
+int check_accumulate_masked(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, bool have_mask) {
+    if (int rc = check_accumulate(fn, ctx, desc, first, count, stride, acc)) return rc;
+    if (!have_mask) return accum_fail(fn, "the mask is NULL (dsrt_render_accumulate renders every pixel)");
+    return check_masked_desc(fn, desc);
+}
+
+// What dsrt_select_unconverged and dsrt_resolve_accumulated_counts refuse (`outputs`: the resolve's three; null for the test, whose output is the mask).
+// The checks ask whether a buffer is given, never what it holds: have_sum, have_sq, have_n say so (the _to_host driver checks before it has allocated any).
+int check_counts(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, bool have_sum, bool have_sq, bool have_n, bool need_sq, const void* const* outputs) {
+    if (!ctx || !desc || !have_n) return accum_fail(fn, "null argument");
+    if (!have_sum) return accum_fail(fn, "DsrtAccum.sum is NULL");
+    if (desc->rng_mode != 1) return accum_fail(fn, "accumulated sums are rng_mode 1's");
+    if (desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
+    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
+    if (desc->width < 2 || desc->height < 2) return accum_fail(fn, "width and height must be >= 2");
+    if (need_sq && !have_sq) return accum_fail(fn, "the variance needs DsrtAccum.sum_sq");
+    if (outputs && !outputs[0] && !outputs[1] && !outputs[2]) return accum_fail(fn, "no output");
+    return DSRT_OK;
+}
+
+int check_adaptive(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* ad, bool have_sum, bool have_sq, bool have_n, const void* rgb8,
+                   const void* f32, const void* var) {
+    if (!ad) return accum_fail(fn, "null argument");
+    const void* outputs[3] = {rgb8, f32, var};
+    if (int rc = check_counts(fn, ctx, desc, have_sum, have_sq, have_n, true, outputs)) return rc;
+    if (int rc = check_sample_set(fn, ctx, desc, 0, 1, 1)) return rc;                         // whatever a masked launch refuses of ctx and desc
+    if (int rc = check_masked_desc(fn, desc)) return rc;
+    const int spp = desc->spp < 1 ? 1 : desc->spp;
+    if (ad->passes < 1 || ad->passes > spp || ad->passes > 64) return accum_fail(fn, "passes must be between 1 and min(spp, 64)");
+    if (ad->min_passes < 1 || ad->min_passes > ad->passes) return accum_fail(fn, "min_passes must be between 1 and passes");
+    if (!(ad->rel_tol >= 0.0f) || !(ad->floor >= 0.0f)) return accum_fail(fn, "rel_tol and floor must be >= 0");
+    return DSRT_OK;
+}
+}  // namespace
+
+int dsrt_render_accumulate_masked(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, const uint8_t* d_mask,
+                                  uint32_t* d_n, void* stream, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_accumulate_masked", [&]() -> int {
+    const int rc = check_accumulate_masked("dsrt_render_accumulate_masked", ctx, desc, first, count, stride, acc, d_mask != nullptr);
+    if (rc) return rc;
+    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq, d_mask, d_n};
+    return render_impl(ctx, desc, nullptr, nullptr, stream, stats, nullptr, &in);
+    });
+}
+
+int dsrt_render_accumulate_masked_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, const uint8_t* h_mask,
+                                          uint32_t* h_n, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_accumulate_masked_to_host", [&]() -> int {
+    if (int rc = check_accumulate_masked("dsrt_render_accumulate_masked_to_host", ctx, desc, first, count, stride, h_acc, h_mask != nullptr)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * desc->height;
+    const Staged s[4] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::InOut}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::InOut}, {h_mask, px, Dir::In},
+                         {h_n, px * sizeof(uint32_t), Dir::InOut}};
+    DsrtStats local;
+    return staged_call(s, [&](void* const* d) {
+        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
+        return dsrt_render_accumulate_masked(ctx, desc, first, count, stride, &acc, (const uint8_t*)d[2], (uint32_t*)d[3], nullptr, stats ? stats : &local);
+    });
+    });
+}
+
+int dsrt_select_unconverged(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, const uint32_t* d_n, float rel_tol, float floor, uint32_t n_min,
+                            uint32_t n_max, uint8_t* d_mask, uint32_t* h_active, void* stream_v) {
+    return dsrt::guarded("dsrt_select_unconverged", [&]() -> int {
+    int rc = check_counts("dsrt_select_unconverged", ctx, desc, acc && acc->sum, acc && acc->sum_sq, acc && d_n, true, nullptr);
+    if (rc) return rc;
+    if (!d_mask) return accum_fail("dsrt_select_unconverged", "the mask is NULL");
+    if (!(rel_tol >= 0.0f) || !(floor >= 0.0f)) return accum_fail("dsrt_select_unconverged", "rel_tol and floor must be >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (h_active && (rc = ctx->active_count.grow(1))) return rc;
+    if ((rc = launch_begin(ctx, stream, {{h_active ? ctx->active_count.p : nullptr, sizeof(uint32_t)}}))) return rc;      // behind the context's last launch (into these sums, maybe)
+    HIP_TRY(launch_select_unconverged((const unsigned long long*)acc->sum, (const unsigned long long*)acc->sum_sq, d_n, (size_t)desc->width * desc->height, rel_tol, floor,
+                                      n_min, n_max, d_mask, h_active ? ctx->active_count.p : nullptr, stream));
+    if ((rc = launch_finish(ctx, stream, nullptr)) || !h_active) return rc;       // (the next launch reads the mask: it comes behind this one on any stream)
+    HIP_TRY(hipMemcpyAsync(h_active, ctx->active_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DSRT_OK;
+    });
+}
+
+int dsrt_resolve_accumulated_counts(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, const uint32_t* d_n, uint8_t* d_rgb8, float* d_f32,
+                                    float* d_var_of_mean, void* stream_v) {
+    return dsrt::guarded("dsrt_resolve_accumulated_counts", [&]() -> int {
+    const void* outputs[3] = {d_rgb8, d_f32, d_var_of_mean};
+    int rc = check_counts("dsrt_resolve_accumulated_counts", ctx, desc, acc && acc->sum, acc && acc->sum_sq, acc && d_n, d_var_of_mean != nullptr, outputs);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    if ((rc = launch_begin(ctx, stream, {}))) return rc;
+    const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
+    const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;
+    HIP_TRY(render_launchers(desc->math_mode == 1).launch_resolve_counts((const unsigned long long*)acc->sum, d_n, inv_gamma, (size_t)desc->width * desc->height, d_rgb8,
+                                                                         d_f32, sq, d_var_of_mean, stream));
+    return DSRT_OK;
+    });
+}
+
+// The driver: passes of one interleaved sample set each; the first min_passes over every pixel, each later one over the pixels the convergence test left
+// active behind the pass before it (one 4-byte readback per pass); then the per-pixel resolve.
+int dsrt_render_adaptive(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* ad, const DsrtAccum* acc, uint32_t* d_n, uint8_t* d_rgb8, float* d_f32,
+                         float* d_var_of_mean, void* stream_v, DsrtAdaptiveStats* stats) {
+    return dsrt::guarded("dsrt_render_adaptive", [&]() -> int {
+    int rc = check_adaptive("dsrt_render_adaptive", ctx, desc, ad, acc && acc->sum, acc && acc->sum_sq, acc && d_n, d_rgb8, d_f32, d_var_of_mean);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const size_t px = (size_t)desc->width * desc->height;
+    if ((rc = ctx->adaptive_mask.grow(px))) return rc;
+    const int spp = desc->spp < 1 ? 1 : desc->spp, P = ad->passes;
+    DsrtAdaptiveStats local;
+    std::memset(&local, 0, sizeof local);
+    // a `checked` frame reads every pass's status flags (a synchronisation per pass, as a checked launch with stats has): the first flagged pass ends the
+    // frame with DSRT_ERR_DEVICE_FLAG, as the primitive would
+    DsrtStats pass_stats;
+    DsrtStats* const flags = desc->checked != 0 ? &pass_stats : nullptr;
+    uint32_t active = (uint32_t)px;
+    for (int p = 0; p < P && active; ++p) {
+        const int count = (spp - p + P - 1) / P;                                     // len(range(p, spp, P))
+        if (p < ad->min_passes) {
+            if ((rc = dsrt_render_accumulate(ctx, desc, p, count, P, acc, stream, flags))) return rc;
+            HIP_TRY(launch_add_count(d_n, (uint32_t)count, px, stream));
+        } else if ((rc = dsrt_render_accumulate_masked(ctx, desc, p, count, P, acc, ctx->adaptive_mask.p, d_n, stream, flags))) return rc;
+        local.active[p] = active;
+        local.samples_total += (uint64_t)active * (uint64_t)count;
+        local.passes_run = p + 1;
+        if (p + 1 >= ad->min_passes && p + 1 < P &&
+            (rc = dsrt_select_unconverged(ctx, desc, acc, d_n, ad->rel_tol, ad->floor, 0u, 0xFFFFFFFFu, ctx->adaptive_mask.p, &active, stream))) return rc;
+    }
+    if ((rc = dsrt_resolve_accumulated_counts(ctx, desc, acc, d_n, d_rgb8, d_f32, d_var_of_mean, stream))) return rc;
+    if (stats) *stats = local;
+    return DSRT_OK;
+    });
+}
+
+int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* ad, uint32_t* h_n, uint8_t* h_rgb8, float* h_f32, float* h_var_of_mean,
+                                 DsrtAdaptiveStats* stats) {
+    return dsrt::guarded("dsrt_render_adaptive_to_host", [&]() -> int {
+    if (!ctx || !desc) return accum_fail("dsrt_render_adaptive_to_host", "null argument");
+    const size_t px = (size_t)desc->width * (size_t)desc->height;
+    DevBuf<unsigned long long> sum, sq;                     // the frame's sums live on the device for the call; the counts come back only if asked for
+    DevBuf<uint32_t> n;
+    if (int rc = check_adaptive("dsrt_render_adaptive_to_host", ctx, desc, ad, true, true, true, h_rgb8, h_f32, h_var_of_mean)) return rc;   // (the call owns sums and counts)
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (rc = n.alloc(px))) return rc;
+    HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(n.p, 0, px * sizeof(uint32_t)));
+    const DsrtAccum acc{(uint64_t*)sum.p, (uint64_t*)sq.p};
+    const Staged s[3] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_var_of_mean, px * 3 * sizeof(float), Dir::Out}};
+    if ((rc = staged_call(s, [&](void* const* d) -> int {
+            const int r = dsrt_render_adaptive(ctx, desc, ad, &acc, n.p, (uint8_t*)d[0], (float*)d[1], (float*)d[2], nullptr, stats);
+            if (r) return r;
+            HIP_TRY(hipStreamSynchronize(nullptr));
+            return DSRT_OK;
+        }))) return rc;
+    if (h_n) HIP_TRY(hipMemcpy(h_n, n.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DSRT_OK;
     });
 }
 

@@ -136,8 +136,19 @@ struct RenderArgs {
                                //   [2] spread   lanes per wave (1..64) that serve the heavy queue first; the others start on the light one
     uint32_t* probe_queue;     // probe launch only: 64 queue words, 64 bytes apart (path_machine.h, ST_FETCH)
     int       hot;             // rng_mode 0: 1 = a wave that holds a pixel of a heavy tile raises its issue priority (render_body)
-    const BatchFrame* batch;   // batch launch only: the table, batch_frames entries (two per frame)
-    const uint32_t* batch_order; //   the frames' tile orders, BatchFrame::order_base apart
+    union {
+        const BatchFrame* batch;   // batch launch only: the table, batch_frames entries (two per frame)
+        const uint32_t* list;      // LISTED launches only (dsrt_render_accumulate_masked): the active pixels, x | row << 16 (row 0 = top), written by
+                               //   dsrt_pixel_list_kernel behind the pre-pass in the tile order itself: the heavy list from entry 0, the light list from
+                               //   entry n_heavy * tile * tile
+    };
+    union {
+        const uint32_t* batch_order; //   the frames' tile orders, BatchFrame::order_base apart
+        const uint32_t* list_len;  // LISTED launches only: [0] entries of the heavy list, [1] of the light list; two words of the sched block, read-only during
+                               //   the render -- NOT on a queue word's line: every fetch reads them, and beside the light queue's counter a masked pass took
+                               //   38 % longer.  (Both share a batch launch's slots, as accum_sq shares the probe's below: a launch is one kind
+                               //   or the other, and the block keeps its layout)
+    };
     uint32_t  batch_frames, batch_frame_pixels;   // table entries in the launch; output pixels per frame (W*H, or a shard's padded tile buffer)
     union {
         uint32_t* tile_work;   // probe launch only (null otherwise): rays traced per local tile, the measured cost the order is refined by

@@ -9,16 +9,19 @@ namespace dsrt {
 // Which instantiation of dsrt_render_kernel a launch wants (render_kernel.hip: launch_render picks it and refuses what is not built).
 //   count, checked: the counting / checked builds (never LEAN)      anyhit: shadow rays stop at the first accepted triangle
 //   lean: a scene of Lambertian triangles only (path_machine.h)     sets, moments: the rng_mode 1 launches of dsrt_render_accumulate
-struct RenderVariant { int rng_mode; bool count, checked, anyhit, lean, sets, moments; };
+//   listed: dsrt_render_listed_kernel -- a sets launch over the lists of active pixels (dsrt_render_accumulate_masked); never count
+struct RenderVariant { int rng_mode; bool count, checked, anyhit, lean, sets, moments, listed; };
 
 // The launchers of render_kernel.hip.  That file is compiled twice -- with the deterministic sin / cos / pow shared with the CPU oracle, and against the device
-// math library's (DsrtRenderDesc.math_mode 1, namespace devlibm) -- and each compilation exports its four launchers as one table.
+// math library's (DsrtRenderDesc.math_mode 1, namespace devlibm) -- and each compilation exports its launchers as one table.
 struct RenderLaunchers {
     hipError_t (*launch_render)(const RenderArgs& a, const RenderVariant& v, int blocks, hipStream_t stream);
     hipError_t (*launch_render_batch)(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
     hipError_t (*launch_probe)(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
     hipError_t (*launch_resolve)(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
                                  const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
+    hipError_t (*launch_resolve_counts)(const unsigned long long* sums, const uint32_t* counts, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                                        const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
 };
 const RenderLaunchers& compiled_render_launchers();
 namespace devlibm { const RenderLaunchers& compiled_render_launchers(); }
@@ -30,6 +33,13 @@ hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_
 hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream);
 hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
                               uint32_t* total_items, hipStream_t stream);
+
+// ... adaptive sampling: the lists of a masked accumulate launch (with its update of the sample counts), the counts of an unmasked pass, the convergence test
+hipError_t launch_pixel_list(const FrameParams& P, const uint32_t* order, const uint32_t* sched, const uint8_t* mask, uint32_t* list, uint32_t* list_len,
+                             uint32_t* n, uint32_t count, hipStream_t stream);
+hipError_t launch_add_count(uint32_t* n, uint32_t count, size_t n_pixels, hipStream_t stream);
+hipError_t launch_select_unconverged(const unsigned long long* sums, const unsigned long long* sums_sq, const uint32_t* counts, size_t n_pixels, float rel_tol, float floor_,
+                                     uint32_t n_min, uint32_t n_max, uint8_t* mask, uint32_t* n_active, hipStream_t stream);
 
 // ... tile de-interleave, the drop-in layer's content hash and the self-test hooks
 hipError_t launch_deinterleave(const uint8_t* gathered, uint8_t* image, int W, int H, int tile, int tiles_x, int shard_count,

@@ -134,8 +134,9 @@ __device__ __forceinline__ typename RngOf<RNGMODE>::type make_rng(Lane& ln, cons
 // never takes) and ~20 scalar registers the advance pass no longer keeps alive.
 // SETS (rng_mode 1 only; dsrt_render_accumulate): the lane's sample j is the frame's sample first + j*stride (FrameParams::sample_first); dsrt_render's
 // kernels are built without it and do not pay for the arithmetic.  MOMENTS (with SETS; sum_sq given): every sample also adds its squared quantised
-// value to a second set of sums.
-template <bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false, bool SETS = false, bool MOMENTS = false>
+// value to a second set of sums.  LISTED (with SETS; dsrt_render_accumulate_masked): the work items are the pixels of two compact lists (RenderArgs::list), not of
+// whole tiles; only ST_FETCH differs.
+template <bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false, bool SETS = false, bool MOMENTS = false, bool LISTED = false>
 __device__ __forceinline__ void advance_step(LaneOf<MOMENTS>& ln, const RenderArgs& args, uint32_t* c, uint32_t& flags) {
     const DeviceScene& S = args.scene;
     const int num_spheres = LEAN ? 0 : S.num_spheres;
@@ -562,7 +563,10 @@ __device__ __forceinline__ void advance_step(LaneOf<MOMENTS>& ln, const RenderAr
         // a 1000-sample item of cheap samples is a longer job than a 125-sample item of dear ones, so the biggest jobs came last.
         const int light_len = RNGMODE == 1 ? P.light_chunk_len : spp;
         const uint32_t per_pixel_light = RNGMODE == 1 ? (uint32_t)((spp + light_len - 1) / light_len) : 1u;
-        const uint32_t heavy_items = n_heavy * tt * per_pixel, light_items = (n_live - n_heavy) * tt * per_pixel_light;
+        uint32_t heavy_items = n_heavy * tt * per_pixel, light_items = (n_live - n_heavy) * tt * per_pixel_light;
+        // LISTED: the queues run over the active pixels of the heavy and of the light tiles instead of over all of them (the lists' lengths come from the device
+        // words the list-building kernel left); slices, spread and everything behind the fetch are as for whole tiles.
+        if constexpr (LISTED) { heavy_items = args.list_len[0] * per_pixel; light_items = args.list_len[1] * per_pixel_light; }
         bool heavy = PROBE || (ln.aux & 63u) < spread;
         uint32_t item;
         if constexpr (PROBE) {
@@ -592,9 +596,22 @@ __device__ __forceinline__ void advance_step(LaneOf<MOMENTS>& ln, const RenderAr
             if (args.hot && heavy && !none) ln.aux |= kHot;
         }
         if (sliced) { ln.chunk = item % pp; item /= pp; }
-        if (!heavy) item += n_heavy * tt;                     // position in tile_order x pixels per tile
+        if (!heavy) item += n_heavy * tt;                     // position in tile_order x pixels per tile (LISTED: in the list, whose light part starts there)
         if (none) {
             state = ST_DONE;
+        } else if constexpr (LISTED) {
+            // the pixel comes from the list (x | row << 16, row 0 = top: device_layout.h), not from the tile order: the only read of the list, nothing of it lives on
+            const uint32_t e = args.list[item];
+            px = (int)(e & 0xFFFFu);
+            ky = H - 1 - (int)(e >> 16);
+            out_index = (e >> 16) * (uint32_t)W + (e & 0xFFFFu);
+            accum = mk(0, 0, 0);
+            if constexpr (MOMENTS) ln.accum_sq = mk(0, 0, 0);
+            const int len = heavy ? chunk_len : light_len;
+            sample = sliced ? (int)ln.chunk * len : 0;
+            ln.sample_end = sliced ? min(spp, sample + len) : spp;
+            restream();
+            state = ST_GEN;
         } else {
             const uint32_t within = item % tt;
             const uint32_t* order = BATCH ? args.batch_order + bf->order_base : P.tile_order;

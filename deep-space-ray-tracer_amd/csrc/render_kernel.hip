@@ -71,7 +71,7 @@ __device__ __forceinline__ bool apply_pair(Lane& ln, uint32_t* c, int slot_a, v2
 // Node-loop iterations per look at the loop's votes (1: +1.4 % time, 3: no better than 2; profiles/r03/ab_node_loop_unroll.jsonl).
 constexpr int kNodeUnroll = 2;
 
-template <int K, bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false, bool SETS = false, bool MOMENTS = false>
+template <int K, bool COUNT, bool CHECKED, bool ANYHIT, int RNGMODE, bool PROBE, bool BATCH = false, bool LEAN = false, bool SETS = false, bool MOMENTS = false, bool LISTED = false>
 __device__ __forceinline__ void render_body(const RenderArgs& args) {
     const DeviceScene& S = args.scene;
     __shared__ uint2 lds_stack[kWavesPerBlock][K + 1][64];       // entry K is a dump slot, see the node visit
@@ -119,7 +119,7 @@ __device__ __forceinline__ void render_body(const RenderArgs& args) {
                 typedef const RenderArgs __attribute__((address_space(4)))* KernargPtr;
                 KernargPtr kp = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(kp));
-                advance_step<COUNT, CHECKED, ANYHIT, RNGMODE, PROBE, BATCH, LEAN, SETS, MOMENTS>(ln, *(const RenderArgs*)kp, c, flags);
+                advance_step<COUNT, CHECKED, ANYHIT, RNGMODE, PROBE, BATCH, LEAN, SETS, MOMENTS, LISTED>(ln, *(const RenderArgs*)kp, c, flags);
             }
         }
 
@@ -352,6 +352,14 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) DSRT_WAVES_ATTR dsrt_rend
     static_assert(!SETS || RNGMODE == 1, "sample sets are rng_mode 1's");
     static_assert(!MOMENTS || SETS, "second moments are summed by accumulate launches only");
     render_body<K, COUNT, CHECKED, ANYHIT, RNGMODE, false, false, LEAN, SETS, MOMENTS>(args);
+}
+
+// Masked accumulate launch (dsrt_render_accumulate_masked): the SETS kernel of rng_mode 1 with its work items fetched from the lists of active pixels
+// (path_machine.h, LISTED).  Production (LEAN or general) and checked builds only.  A kernel symbol of its own: dsrt_render_kernel's instantiations keep their names.
+template <bool CHECKED, bool LEAN, bool MOMENTS>
+__global__ void __launch_bounds__(64 * kWavesPerBlock) DSRT_WAVES_ATTR dsrt_render_listed_kernel(const RenderArgs args) {
+    static_assert(!(CHECKED && LEAN), "the checked build is the general code");
+    render_body<8, false, CHECKED, true, 1, false, false, LEAN, true, MOMENTS, true>(args);
 }
 
 // Batch launch: many frames of one scene as one pool of work (path_machine.h, ST_FETCH).
@@ -594,6 +602,149 @@ __global__ void __launch_bounds__(1024) dsrt_tile_reorder_kernel(const uint32_t*
     }
 }
 
+// The lists of a masked accumulate launch (path_machine.h, LISTED), built behind the pre-pass on its stream in three small kernels: one wave per 8x8 block of every
+// tile in the order, heavy part and light part, counts its active pixels (mask byte != 0) with a ballot; one workgroup turns the counts into offsets (a prefix sum
+// along the order) and writes the two lengths, which ST_FETCH reads afterwards -- no readback; the waves of the first kernel's shape then write their pixels at
+// offset + rank in the ballot.  So a list is in the tile order itself, block by block and pixel by pixel as the tile FETCH walks a tile: with every pixel active an
+// item number means the pixel it means in an unmasked launch, and the costliest tiles' pixels come first whatever order the waves ran in.  (A first form appended
+// with one atomicAdd per wave on the length word: the blocks then arrive in the order the atomics were served.)  The heavy list has room for every pixel of the
+// heavy tiles, the light list starts right behind that, and the per-wave counts lie behind both.  The counting threads, one per pixel of the image (culled tiles
+// included: the rule does not depend on culling), also add `count` to n[] where the mask is set.
+struct ListWave { uint32_t pos, x, row; bool live, active; unsigned long long votes; };
+__device__ __forceinline__ ListWave list_wave(uint32_t wave_id, uint32_t lane, int W, int H, int tile, int tiles_x, const uint32_t* __restrict__ order,
+                                              const uint32_t* __restrict__ sched, const uint8_t* __restrict__ mask) {
+    const uint32_t per_row = (uint32_t)tile >> 3, blocks_per_tile = per_row * per_row;
+    ListWave w;
+    w.pos = wave_id / blocks_per_tile;                                                    // place in the tile order
+    const uint32_t sub = wave_id % blocks_per_tile;                                       // 8x8 block of that tile
+    w.live = w.pos < sched[1];                                                            // (wave-uniform)
+    w.x = w.row = 0; w.active = false;
+    if (w.live) {
+        const uint32_t k = order ? order[w.pos] : w.pos;
+        w.x = (k % (uint32_t)tiles_x) * (uint32_t)tile + (sub % per_row) * 8u + (lane & 7u);
+        w.row = (k / (uint32_t)tiles_x) * (uint32_t)tile + (sub / per_row) * 8u + (lane >> 3);
+        w.active = w.x < (uint32_t)W && w.row < (uint32_t)H && mask[(size_t)w.row * (uint32_t)W + w.x] != 0;
+    }
+    w.votes = wave_ballot(w.active);
+    return w;
+}
+
+__global__ void __launch_bounds__(256) dsrt_pixel_count_kernel(int W, int H, int tile, int tiles_x, const uint32_t* __restrict__ order, const uint32_t* __restrict__ sched,
+                                                               const uint8_t* __restrict__ mask, uint32_t* __restrict__ offs, uint32_t* __restrict__ n, uint32_t count) {
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n && gid < (uint32_t)W * (uint32_t)H && mask[gid]) n[gid] += count;
+    const ListWave w = list_wave(gid >> 6, threadIdx.x & 63u, W, H, tile, tiles_x, order, sched, mask);
+    if (w.live && (threadIdx.x & 63u) == 0u) offs[gid >> 6] = (uint32_t)__popcll(w.votes);
+}
+
+// offs[0 .. n_live * blocks_per_tile): counts in, their exclusive prefix sums out; list_len = the sum over the heavy tiles' blocks, the sum over the rest.
+__global__ void __launch_bounds__(1024) dsrt_pixel_scan_kernel(int tile, const uint32_t* __restrict__ sched, uint32_t* __restrict__ offs, uint32_t* __restrict__ list_len) {
+    __shared__ uint32_t part[1024], heavy_total;
+    const uint32_t blocks_per_tile = (uint32_t)((tile >> 3) * (tile >> 3));
+    const uint32_t total = sched[1] * blocks_per_tile, boundary = sched[0] * blocks_per_tile;
+    const uint32_t each = (total + 1023u) / 1024u, lo = min(total, threadIdx.x * each), hi = min(total, lo + each);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; ++i) sum += offs[i];
+    part[threadIdx.x] = sum;
+    if (threadIdx.x == 0) heavy_total = 0;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {                                            // inclusive scan of the 1024 partial sums
+        const uint32_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[threadIdx.x] - sum;
+    for (uint32_t i = lo; i < hi; ++i) {
+        if (i == boundary) heavy_total = run;
+        const uint32_t c = offs[i];
+        offs[i] = run;
+        run += c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t all = part[1023], h = boundary >= total ? all : heavy_total;
+        list_len[0] = h;
+        list_len[1] = all - h;
+    }
+}
+
+__global__ void __launch_bounds__(256) dsrt_pixel_list_kernel(int W, int H, int tile, int tiles_x, const uint32_t* __restrict__ order, const uint32_t* __restrict__ sched,
+                                                              const uint8_t* __restrict__ mask, const uint32_t* __restrict__ offs, uint32_t* __restrict__ list,
+                                                              const uint32_t* __restrict__ list_len) {
+    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const ListWave w = list_wave(gid >> 6, threadIdx.x & 63u, W, H, tile, tiles_x, order, sched, mask);
+    if (w.votes == 0ull) return;                                                          // (a wave past the live tiles has none)
+    const uint32_t n_heavy = sched[0], tt = (uint32_t)(tile * tile);
+    // offsets run on through both parts: the light list's own start is the heavy list's length, and its place is behind the heavy tiles' pixels
+    const uint32_t base = w.pos < n_heavy ? offs[gid >> 6] : n_heavy * tt + (offs[gid >> 6] - list_len[0]);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(w.votes >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)w.votes, 0u));
+    if (w.active) list[base + rank] = w.x | (w.row << 16);
+}
+
+// `list`: local_tiles * tile^2 entries for the two lists and, behind them, one word per 8x8 block of every tile for the counts and offsets.
+hipError_t launch_pixel_list(const FrameParams& P, const uint32_t* order, const uint32_t* sched, const uint8_t* mask, uint32_t* list, uint32_t* list_len,
+                             uint32_t* n, uint32_t count, hipStream_t stream) {
+    const size_t threads = (size_t)P.local_tiles * (size_t)(P.tile * P.tile);            // one per pixel of every tile: at least width * height
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    uint32_t* offs = list + threads;
+    hipLaunchKernelGGL(dsrt_pixel_count_kernel, grid, dim3(256), 0, stream, P.width, P.height, P.tile, P.tiles_x, order, sched, mask, offs, n, count);
+    hipLaunchKernelGGL(dsrt_pixel_scan_kernel, dim3(1), dim3(1024), 0, stream, P.tile, sched, offs, list_len);
+    hipLaunchKernelGGL(dsrt_pixel_list_kernel, grid, dim3(256), 0, stream, P.width, P.height, P.tile, P.tiles_x, order, (const uint32_t*)sched, mask,
+                       (const uint32_t*)offs, list, (const uint32_t*)list_len);
+    return hipGetLastError();
+}
+
+// n[] += count for every pixel: what an unmasked pass of dsrt_render_adaptive adds to the sample counts.
+__global__ void dsrt_add_count_kernel(uint32_t* __restrict__ n, uint32_t count, size_t n_pixels) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_pixels) n[i] += count;
+}
+
+hipError_t launch_add_count(uint32_t* n, uint32_t count, size_t n_pixels, hipStream_t stream) {
+    hipLaunchKernelGGL(dsrt_add_count_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, n, count, n_pixels);
+    return hipGetLastError();
+}
+
+// The convergence test of adaptive sampling (include/dsrt.h, ADAPTIVE SAMPLING): in double, in exactly the order the header writes down -- conversions, one
+// multiplication by a power of two, and correctly rounded + - * / only (no fused operations: -ffp-contract=off; no sqrt) -- so that a CPU reproduces every byte.
+__global__ void __launch_bounds__(256) dsrt_select_unconverged_kernel(const unsigned long long* __restrict__ sums, const unsigned long long* __restrict__ sums_sq,
+                                                                      const uint32_t* __restrict__ counts, size_t n_pixels, float rel_tol, float floor_, uint32_t n_min,
+                                                                      uint32_t n_max, uint8_t* __restrict__ mask, uint32_t* __restrict__ n_active) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool active = false;
+    if (i < n_pixels) {
+        const uint32_t cnt = counts[i];
+        bool converged = cnt >= 2u;
+        if (converged) {
+            const double n = (double)cnt;
+            for (int ch = 0; ch < 3; ++ch) {
+                const double s = (double)sums[i * 3 + ch] * (1.0 / 1048576.0), s2 = (double)sums_sq[i * 3 + ch] * (1.0 / 1048576.0);
+                double v = (s2 - s * s / n) / (n - 1.0);
+                v = v > 0.0 ? v : 0.0;
+                const double vm = v / n, m = s / n;
+                const double r = m > (double)floor_ ? m : (double)floor_;
+                const double lim = (double)rel_tol * r;
+                converged = converged && vm <= lim * lim;
+            }
+        }
+        active = cnt < n_max && (cnt < n_min || !converged);
+        mask[i] = active ? 1 : 0;
+    }
+    if (n_active) {
+        const unsigned long long votes = wave_ballot(active);
+        if ((threadIdx.x & 63u) == 0u && votes != 0ull) atomicAdd(n_active, (uint32_t)__popcll(votes));
+    }
+}
+
+hipError_t launch_select_unconverged(const unsigned long long* sums, const unsigned long long* sums_sq, const uint32_t* counts, size_t n_pixels, float rel_tol, float floor_,
+                                     uint32_t n_min, uint32_t n_max, uint8_t* mask, uint32_t* n_active, hipStream_t stream) {
+    if (!n_pixels) return hipSuccess;
+    hipLaunchKernelGGL(dsrt_select_unconverged_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, sums_sq, counts, n_pixels, rel_tol, floor_,
+                       n_min, n_max, mask, n_active);
+    return hipGetLastError();
+}
+
 hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream) {
     hipLaunchKernelGGL(dsrt_tile_reorder_kernel, dim3(1), dim3(1024), 0, stream, work, order, tmp, sched);
     return hipGetLastError();
@@ -694,6 +845,45 @@ __global__ void dsrt_resolve_kernel(const unsigned long long* __restrict__ sums,
     if (out_f32) { out_f32[i * 3 + 0] = col.x; out_f32[i * 3 + 1] = col.y; out_f32[i * 3 + 2] = col.z; }
 }
 
+// dsrt_resolve_accumulated_counts: the same arithmetic with every pixel's own sample count (adaptive sampling, include/dsrt.h) in place of samples_done.  A pixel
+// nobody sampled (n == 0) is zero bytes and +0.0f; a pixel with one sample has no variance estimate: +0.0f.
+__global__ void dsrt_resolve_counts_kernel(const unsigned long long* __restrict__ sums, const uint32_t* __restrict__ counts, float inv_gamma, size_t n_pixels,
+                                           uint8_t* __restrict__ out_rgb8, float* __restrict__ out_f32,
+                                           const unsigned long long* __restrict__ sums_sq, float* __restrict__ out_var) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const uint32_t cnt = counts[i];
+    if (out_var) {
+        const double n = (double)cnt;
+        for (int ch = 0; ch < 3; ++ch) {
+            float var = 0.0f;
+            if (cnt >= 2u) {
+                const double s = (double)sums[i * 3 + ch] * (1.0 / 1048576.0), s2 = (double)sums_sq[i * 3 + ch] * (1.0 / 1048576.0);
+                double v = (s2 - s * s / n) / (n - 1.0);
+                v = v > 0.0 ? v : 0.0;
+                var = (float)(v / n);
+            }
+            out_var[i * 3 + ch] = var;
+        }
+    }
+    if (!out_rgb8 && !out_f32) return;
+    F3 col = mk(0, 0, 0);
+    if (cnt) {
+        const double unit = 1.0 / 1048576.0 / (double)cnt;
+        col = mk((float)((double)sums[i * 3 + 0] * unit), (float)((double)sums[i * 3 + 1] * unit), (float)((double)sums[i * 3 + 2] * unit));
+        col = mk(fmaxf(col.x, 0.0f), fmaxf(col.y, 0.0f), fmaxf(col.z, 0.0f));
+        col = mk(fminf(col.x, 10.0f), fminf(col.y, 10.0f), fminf(col.z, 10.0f));
+        col = mk(dsrt_powf(col.x, inv_gamma), dsrt_powf(col.y, inv_gamma), dsrt_powf(col.z, inv_gamma));
+        col = clamp01(col);
+    }
+    if (out_rgb8) {
+        out_rgb8[i * 3 + 0] = (unsigned char)(255.99f * col.x);
+        out_rgb8[i * 3 + 1] = (unsigned char)(255.99f * col.y);
+        out_rgb8[i * 3 + 2] = (unsigned char)(255.99f * col.z);
+    }
+    if (out_f32) { out_f32[i * 3 + 0] = col.x; out_f32[i * 3 + 1] = col.y; out_f32[i * 3 + 2] = col.z; }
+}
+
 // ---- launchers (declared in launchers.h; the four of the twice-compiled kernels go out as this compilation's table) -----
 template <int K, int RNGMODE, bool SETS = false, bool MOMENTS = false>
 static hipError_t launch_k(const RenderArgs& a, int blocks, bool count, bool checked, bool anyhit, bool lean, hipStream_t stream) {
@@ -734,9 +924,22 @@ static hipError_t launch_probe(const RenderArgs& a, int blocks, bool lean, hipSt
     return hipGetLastError();
 }
 
-// sets: the SETS instantiations (rng_mode 1, dsrt_render_accumulate); moments: with MOMENTS as well (a.accum_sq is set)
+template <bool MOMENTS>
+static hipError_t launch_listed(const RenderArgs& a, int blocks, bool checked, bool lean, hipStream_t stream) {
+    const dim3 grid(blocks), block(64 * kWavesPerBlock);
+    if (checked) hipLaunchKernelGGL((dsrt_render_listed_kernel<true, false, MOMENTS>), grid, block, 0, stream, a);
+    else if (lean) hipLaunchKernelGGL((dsrt_render_listed_kernel<false, true, MOMENTS>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((dsrt_render_listed_kernel<false, false, MOMENTS>), grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+// sets: the SETS instantiations (rng_mode 1, dsrt_render_accumulate); moments: with MOMENTS as well (a.accum_sq is set); listed: the masked form of a SETS launch
 // (K = 8 is the only short-stack size built)
 static hipError_t launch_render(const RenderArgs& a, const RenderVariant& v, int blocks, hipStream_t stream) {
+    if (v.listed) {
+        if (v.rng_mode != 1 || !v.sets || v.count || !v.anyhit) return hipErrorInvalidValue;
+        return v.moments ? launch_listed<true>(a, blocks, v.checked, v.lean, stream) : launch_listed<false>(a, blocks, v.checked, v.lean, stream);
+    }
     if (v.rng_mode == 0 && !v.sets && !v.moments) return launch_k<8, 0>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
     if (v.rng_mode == 1 && !v.sets && !v.moments) return launch_k<8, 1>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
     if (v.rng_mode == 1 && v.sets && !v.moments) return launch_k<8, 1, true>(a, blocks, v.count, v.checked, v.anyhit, v.lean, stream);
@@ -752,8 +955,16 @@ static hipError_t launch_resolve(const unsigned long long* sums, int samples_don
     return hipGetLastError();
 }
 
+static hipError_t launch_resolve_counts(const unsigned long long* sums, const uint32_t* counts, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                                        const unsigned long long* sums_sq, float* out_var, hipStream_t stream) {
+    if (!n_pixels) return hipSuccess;
+    hipLaunchKernelGGL(dsrt_resolve_counts_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, counts, inv_gamma, n_pixels, out_rgb8, out_f32,
+                       sums_sq, out_var);
+    return hipGetLastError();
+}
+
 const RenderLaunchers& compiled_render_launchers() {
-    static const RenderLaunchers table = {launch_render, launch_render_batch, launch_probe, launch_resolve};
+    static const RenderLaunchers table = {launch_render, launch_render_batch, launch_probe, launch_resolve, launch_resolve_counts};
     return table;
 }
 

@@ -155,6 +155,8 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_RAYS: return sizeof(DsrtRays);
         case DSRT_SIZEOF_RAY_HITS: return sizeof(DsrtRayHits);
         case DSRT_SIZEOF_ACCUM: return sizeof(DsrtAccum);
+        case DSRT_SIZEOF_ADAPTIVE: return sizeof(DsrtAdaptive);
+        case DSRT_SIZEOF_ADAPTIVE_STATS: return sizeof(DsrtAdaptiveStats);
         default: return 0;
     }
 }

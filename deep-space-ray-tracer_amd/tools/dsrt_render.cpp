@@ -14,6 +14,10 @@
 //   * rng_mode 1 only: --passes P renders each frame as P interleaved sample sets and writes <frame>_pass<p>of<P> after each (a preview that
 //     sharpens), then <frame> itself -- the last pass's image, byte for byte the one-launch image; --variance also writes the variance of every
 //     pixel's mean as <frame>_var.pfm (include/dsrt.h, SAMPLE SETS).
+//   * rng_mode 1 only: --adaptive TOL renders each frame with adaptive sampling (include/dsrt.h, ADAPTIVE SAMPLING: dsrt_render_adaptive) -- up to
+//     --adaptive-passes P (8) interleaved passes, the first --adaptive-min-passes M (2) over every pixel, the later ones over the pixels whose standard error
+//     still exceeds TOL times their mean (or times --adaptive-floor F, for dark pixels) -- and writes <frame> and <frame>_spp.pfm, every pixel's sample count
+//     (with --variance also <frame>_var.pfm).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,6 +45,9 @@ static int fail(const char* what) {
 int main(int argc, char** argv) {
     std::string pose_file, out_dir = "output", obj;
     int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0, passes = 0;
+    int adaptive_passes = 8, adaptive_min = 2;
+    float adaptive_tol = 0.0f, adaptive_floor = 0.0f;
+    bool adaptive = false, adaptive_detail = false;
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -67,10 +74,20 @@ int main(int argc, char** argv) {
         else if (a == "--png") png = true;                          // frames as PNG instead of PPM (the reference converts with ImageMagick)
         else if (a == "--passes") passes = std::atoi(next("--passes"));   // rng_mode 1: each frame as P interleaved sample sets, an image after each (include/dsrt.h, SAMPLE SETS)
         else if (a == "--variance") variance = true;                // rng_mode 1: also the variance of each pixel's mean, <frame>_var.pfm
+        else if (a == "--adaptive") { adaptive = true; adaptive_tol = (float)std::atof(next("--adaptive")); }   // rng_mode 1: adaptive sampling to this relative standard error
+        else if (a == "--adaptive-passes") { adaptive_detail = true; adaptive_passes = std::atoi(next("--adaptive-passes")); }
+        else if (a == "--adaptive-min-passes") { adaptive_detail = true; adaptive_min = std::atoi(next("--adaptive-min-passes")); }
+        else if (a == "--adaptive-floor") { adaptive_detail = true; adaptive_floor = (float)std::atof(next("--adaptive-floor")); }
         else if (a == "--upscale") std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
+    if (adaptive_detail && !adaptive) { std::fprintf(stderr, "dsrt_render: --adaptive-passes, --adaptive-min-passes and --adaptive-floor need --adaptive TOL\n"); return 2; }
+    if (adaptive && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --adaptive needs --rng-mode 1 (or --fast)\n"); return 2; }
+    if (adaptive && (passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --adaptive does not combine with --passes / --gbuffer\n"); return 2; }
+    if (adaptive && !(adaptive_tol >= 0.0f && adaptive_floor >= 0.0f)) { std::fprintf(stderr, "dsrt_render: --adaptive and --adaptive-floor must be >= 0\n"); return 2; }
+    if (adaptive && (adaptive_passes < 1 || adaptive_passes > std::min(std::max(spp, 1), 64))) { std::fprintf(stderr, "dsrt_render: --adaptive-passes must be between 1 and min(--spp, 64)\n"); return 2; }
+    if (adaptive && (adaptive_min < 1 || adaptive_min > adaptive_passes)) { std::fprintf(stderr, "dsrt_render: --adaptive-min-passes must be between 1 and --adaptive-passes\n"); return 2; }
     if ((passes != 0 || variance) && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --passes and --variance need --rng-mode 1 (or --fast)\n"); return 2; }
     if (passes < 0 || passes > std::max(spp, 1)) { std::fprintf(stderr, "dsrt_render: --passes must be between 1 and --spp\n"); return 2; }
     if (variance && spp < 2) { std::fprintf(stderr, "dsrt_render: --variance needs --spp 2 or more\n"); return 2; }
@@ -145,6 +162,33 @@ int main(int argc, char** argv) {
     std::memset(&d, 0, sizeof d);
     d.width = width; d.height = height; d.spp = spp; d.max_depth = depth; d.gamma = 2.0f; d.seed = 1337; d.rng_mode = rng_mode; d.math_mode = math_mode;
     const size_t image_bytes = (size_t)width * height * 3;
+    if (adaptive) {
+        const size_t px = (size_t)width * height;
+        std::vector<uint8_t> img(image_bytes);
+        std::vector<uint32_t> n(px);
+        std::vector<float> spp_map(px), var(variance ? image_bytes : 0);
+        const DsrtAdaptive ad{adaptive_passes, adaptive_min, adaptive_tol, adaptive_floor};
+        for (size_t q = 0; q < ids.size(); ++q) {
+            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
+            DsrtAdaptiveStats st;
+            if (dsrt_render_adaptive_to_host(ctx, &d, &ad, n.data(), img.data(), nullptr, variance ? var.data() : nullptr, &st) != DSRT_OK) return fail("rendering adaptively");
+            char stem[64];
+            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
+            const std::string base = out_dir + stem, path = base + (png ? ".png" : ".ppm");
+            if ((png ? dsrt_write_png(path.c_str(), img.data(), width, height) : dsrt_write_ppm(path.c_str(), img.data(), width, height)) != DSRT_OK) return fail("writing the frame");
+            for (size_t i = 0; i < px; ++i) spp_map[i] = (float)n[i];
+            if (dsrt_write_pfm((base + "_spp.pfm").c_str(), spp_map.data(), width, height, 1) != DSRT_OK) return fail("writing the sample counts");
+            if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
+            std::printf("adaptive: %d of %d passes, %.1f %% of the frame's %d samples per pixel; pixels per pass:", st.passes_run, adaptive_passes,
+                        100.0 * (double)st.samples_total / ((double)px * spp), spp);
+            for (int p = 0; p < st.passes_run; ++p) std::printf(" %u", st.active[p]);
+            std::printf("\nSaved %s, %s_spp.pfm%s\n", path.c_str(), base.c_str(), variance ? " and _var.pfm" : "");
+        }
+        dsrt_ctx_destroy(ctx);
+        dsrt_host_scene_destroy(hs);
+        std::printf("Done.\n");
+        return 0;
+    }
     if (passes != 0 || variance) {
         // Each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
         // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).

@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -51,6 +51,8 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_RAYS        7
 #define DSRT_SIZEOF_RAY_HITS    8
 #define DSRT_SIZEOF_ACCUM       9
+#define DSRT_SIZEOF_ADAPTIVE    10
+#define DSRT_SIZEOF_ADAPTIVE_STATS 11
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -499,6 +501,55 @@ int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const
                              float* d_var_of_mean, void* stream);
 int dsrt_resolve_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, uint8_t* h_rgb8, float* h_f32,
                                      float* h_var_of_mean);
+
+/*
+ * ADAPTIVE SAMPLING (rng_mode 1, on top of SAMPLE SETS): stop sampling the pixels whose mean has converged and spend the launches on the others.  Three primitives
+ * and a driver; every pixel's value stays defined by the set of its samples that were rendered, whichever launches rendered them.
+ *   dsrt_render_accumulate_masked: dsrt_render_accumulate for a subset of the pixels.  d_mask: width*height bytes, image order (top row first), nonzero = active.
+ *     For every active pixel the launch adds exactly what dsrt_render_accumulate(first, count, stride) adds to acc->sum (and acc->sum_sq when given); for every
+ *     other pixel it adds nothing and writes nothing.  d_n (optional): width*height uint32, image order, the pixels' sample counts: `count` is added to d_n[p] of
+ *     every active pixel -- pixels of culled tiles included: their samples are black, their sums get no addition, and the count does not depend on culling.
+ *     An all-zero mask is a valid launch that changes nothing.  The mask is read on the device, in stream order.
+ *     DSRT_ERR_INVALID: everything dsrt_render_accumulate refuses; a NULL mask; collect_counters != 0 (masked launches use the production and checked kernels only).
+ *     DSRT_ERR_NO_SCENE before an upload.  A refused call touches no buffer.
+ *   dsrt_select_unconverged: the mask of the pixels that still need samples.  Per pixel with n = d_n[p], per channel with the sums S = acc->sum, S2 = acc->sum_sq,
+ *     in double, in exactly this order, every operation correctly rounded (no fused operations, no sqrt):
+ *         s = (double)S * 2^-20;  s2 = (double)S2 * 2^-20;  v = (s2 - s*s/n) / (n - 1);  v = v > 0 ? v : 0;  vm = v / n;  m = s / n;
+ *         r = m > (double)floor ? m : (double)floor;  lim = (double)rel_tol * r;  ok = vm <= lim*lim
+ *     i.e. the standard error of the mean is at most rel_tol times the mean (or times `floor`, for dark pixels).  A pixel with n < 2 is never converged;
+ *     converged = ok_r && ok_g && ok_b;  mask[p] = n < n_max && (n < n_min || !converged) ? 1 : 0.  h_active (optional, HOST): the number of bytes set; the call
+ *     synchronises `stream` when it is given.  Waits for the context's last launch.  Needs no scene.
+ *     DSRT_ERR_INVALID: a NULL ctx, desc, acc, acc->sum, acc->sum_sq, d_n or d_mask; rng_mode != 1; shard_count > 1; rel_tol or floor negative or NaN.
+ *     Stopping on a pixel's own estimate is slightly biased, as with every adaptive sampler: a pixel whose first n_min samples are all alike has v = 0 and stops
+ *     at n_min although later samples might have differed (an edge the first samples missed).  n_min is the guard against that: choose it with the scene in mind.
+ *   dsrt_resolve_accumulated_counts: dsrt_resolve_accumulated's arithmetic with the pixel's own n = d_n[p] in place of samples_done.  A pixel with n == 0 resolves
+ *     to zero bytes, +0.0f and variance +0.0f; a pixel with n == 1 has variance +0.0f.  Refusals as dsrt_resolve_accumulated's (the variance needs acc->sum_sq), and a NULL d_n.
+ *   dsrt_render_adaptive: the frame `desc` plans (desc->spp samples) in up to P = passes passes, 1 <= P <= min(spp, 64).  Pass p is the interleaved set
+ *     (first p, count len(range(p, spp, P)), stride P), which keeps every pixel's samples spread over its area.  Passes < min_passes (1 <= min_passes <= P) cover every
+ *     pixel; from pass min_passes - 1 on, each pass but the last is followed by dsrt_select_unconverged(rel_tol, floor, n_min 0, n_max UINT32_MAX) -- one 4-byte
+ *     readback -- and the next pass is a masked launch over that mask.  The loop ends when no pixel is active or the passes run out; then
+ *     dsrt_resolve_accumulated_counts writes the outputs (at least one of d_rgb8, d_f32, d_var_of_mean).  acc (with sum_sq) and d_n are the caller's, zeroed by the
+ *     caller: afterwards they hold the frame's sums and every pixel's sample count.  stats (optional): passes_run, active[p] = pixels pass p rendered,
+ *     samples_total = the sum over the passes of active[p] * count_p.  Synchronises `stream` after every test.  With desc->checked the status word of every pass
+ *     is read behind it (one more synchronisation per pass) and the first pass that raised it ends the call with DSRT_ERR_DEVICE_FLAG, as the primitives with
+ *     `stats` do; sums and counts then hold the passes up to and including that one, and no output is written.
+ *     DSRT_ERR_INVALID: what the three calls refuse; passes < 1, > spp or > 64; min_passes < 1 or > passes.
+ * The _to_host forms take HOST buffers and are synchronous; dsrt_render_adaptive_to_host keeps the sums on the device and returns the counts in h_n (optional).
+ */
+typedef struct DsrtAdaptive { int passes; int min_passes; float rel_tol; float floor; } DsrtAdaptive;
+typedef struct DsrtAdaptiveStats { int passes_run; uint64_t samples_total; uint32_t active[64]; } DsrtAdaptiveStats;
+int dsrt_render_accumulate_masked(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, const uint8_t* d_mask,
+                                  uint32_t* d_n, void* stream, DsrtStats* stats);
+int dsrt_render_accumulate_masked_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, const uint8_t* h_mask,
+                                          uint32_t* h_n, DsrtStats* stats);
+int dsrt_select_unconverged(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, const uint32_t* d_n, float rel_tol, float floor, uint32_t n_min,
+                            uint32_t n_max, uint8_t* d_mask, uint32_t* h_active, void* stream);
+int dsrt_resolve_accumulated_counts(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, const uint32_t* d_n, uint8_t* d_rgb8, float* d_f32,
+                                    float* d_var_of_mean, void* stream);
+int dsrt_render_adaptive(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* adaptive, const DsrtAccum* acc, uint32_t* d_n, uint8_t* d_rgb8, float* d_f32,
+                         float* d_var_of_mean, void* stream, DsrtAdaptiveStats* stats);
+int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* adaptive, uint32_t* h_n, uint8_t* h_rgb8, float* h_f32,
+                                 float* h_var_of_mean, DsrtAdaptiveStats* stats);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
