@@ -217,6 +217,20 @@ def make_desc(width, height, spp, max_depth=50, gamma=2.0, seed=1337, tile_size=
     return d
 
 
+DENOISE_GUIDES = ("normal", "position", "albedo", "range")            # DsrtDenoiseGuides' channels: G-buffer channels of those names (capi.GBUFFER_CHANNELS)
+
+
+def denoise_defaults(**changes):
+    """dsrt_denoise_defaults: the DsrtDenoise the library fills (iterations, normal_power_log2, sigma_l, sigma_z, sigma_a), with `changes` applied."""
+    p = capi.DsrtDenoise()
+    lib.dsrt_denoise_defaults(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(capi.DsrtDenoise._fields_):
+            raise ValueError(f"DsrtDenoise has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def shard_layout(desc):
     total, mine, padded, nbytes = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
     _check(lib.dsrt_shard_layout(C.byref(desc), C.byref(total), C.byref(mine), C.byref(padded), C.byref(nbytes)), "dsrt_shard_layout")
@@ -580,6 +594,75 @@ class Context:
         acc.samples_done = None                    # the counts are per pixel now: acc.resolve_counts(), not acc.resolve()
         return acc, (rgb, f32, var), {"passes_run": st.passes_run, "samples_total": st.samples_total, "active": list(st.active[:st.passes_run])}
 
+    # ---- the denoiser (include/dsrt.h, DENOISER): the variance-guided a-trous filter over sums and G-buffer guides ----
+    def _guide_tensors(self, desc, guides):
+        if set(guides) != set(DENOISE_GUIDES):
+            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
+        out = {}
+        for k in DENOISE_GUIDES:
+            x, comps = guides[k], capi.GBUFFER_CHANNELS[k][1]
+            if _torch is None or not isinstance(x, _torch.Tensor) or x.dtype != _torch.float32:
+                raise TypeError(f"guide {k} must be a float32 torch tensor")
+            if x.device.type != "cuda" or x.device.index != self.device:
+                raise ValueError(f"guide {k} is on {x.device}, the context is on cuda:{self.device}")
+            if not x.is_contiguous() or x.numel() != desc.width * desc.height * comps:
+                raise ValueError(f"guide {k} must be contiguous with width*height*{comps} elements")
+            out[k] = x
+        return out
+
+    def denoise_accumulated(self, desc, sums, sum_sq, guides, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
+                            want_var=False, stream=None):
+        """dsrt_denoise_accumulated: the filtered image of `sums` / `sum_sq` (int64 device tensors, as render_accumulate's) after `samples_done` samples per pixel
+        or the per-pixel counts `n` (int32 device tensor), guided by `guides` = {"normal", "position", "albedo", "range": float32 device tensors, G-buffer
+        channels}.  params: a DsrtDenoise (denoise_defaults()).  Returns (rgb8, f32, linear, var) device tensors of shape (height, width, 3), None where not asked for."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq")
+        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
+        if n is None and samples_done is None:
+            raise ValueError("denoise_accumulated needs samples_done or per-pixel counts n")
+        g = self._guide_tensors(desc, guides)
+        params = denoise_defaults() if params is None else params
+        shape, dev = (desc.height, desc.width, 3), sums.device
+        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
+        f32, lin, var = (_torch.empty(shape, dtype=_torch.float32, device=dev) if w else None for w in (want_f32, want_linear, want_var))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
+        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
+        _check(lib.dsrt_denoise_accumulated(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(n), C.byref(gd), C.byref(params), ptr(rgb), ptr(f32),
+                                            ptr(lin), ptr(var), C.c_void_p(self._raw_stream(stream))), "dsrt_denoise_accumulated")
+        return rgb, f32, lin, var
+
+    def denoise_accumulated_to_host(self, desc, sums, sum_sq, guides, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
+                                    want_var=False):
+        """dsrt_denoise_accumulated_to_host: the same from numpy arrays (uint64 sums (H, W, 3), uint32 counts (H, W), float32 guides) into numpy arrays."""
+        H, W = desc.height, desc.width
+        S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
+        S2 = np.ascontiguousarray(sum_sq, np.uint64).reshape(H, W, 3)
+        cnt = np.ascontiguousarray(n, np.uint32).reshape(H, W) if n is not None else None
+        if set(guides) != set(DENOISE_GUIDES):
+            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
+        g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
+        params = denoise_defaults() if params is None else params
+        rgb = np.zeros((H, W, 3), np.uint8) if want_rgb8 else None
+        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
+        acc = DsrtAccum(ptr(S), ptr(S2))
+        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
+        _check(lib.dsrt_denoise_accumulated_to_host(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(cnt), C.byref(gd), C.byref(params), ptr(rgb),
+                                                    ptr(f32), ptr(lin), ptr(var)), "dsrt_denoise_accumulated_to_host")
+        return rgb, f32, lin, var
+
+    def render_denoised_to_host(self, desc, params=None, want_f32=False, want_linear=True, want_var=False):
+        """dsrt_render_denoised_to_host: desc.spp samples, the G-buffer of the current camera and the filter, into numpy arrays: (rgb8, f32, linear, var, DsrtStats)."""
+        H, W = desc.height, desc.width
+        params = denoise_defaults() if params is None else params
+        rgb = np.zeros((H, W, 3), np.uint8)
+        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
+        st = DsrtStats()
+        _check(lib.dsrt_render_denoised_to_host(self._h, C.byref(desc), C.byref(params), ptr(rgb), ptr(f32), ptr(lin), ptr(var), C.byref(st)), "dsrt_render_denoised_to_host")
+        return rgb, f32, lin, var, st
+
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""
         old = C.c_uint32()
@@ -677,6 +760,23 @@ class Accumulator:
         if self.n is None:
             raise ValueError("this accumulator has no per-pixel counts (counts=True, or a masked render)")
         return self.ctx.resolve_accumulated_counts(self.desc, self.sum, self.n, self.sum_sq if want_var else None, want_rgb8, want_f32, want_var, stream)
+
+    def guides(self, ctx=None, stream=None):
+        """The denoiser's guides of the context's current camera: {"normal", "position", "albedo", "range"} float32 device tensors (Context.render_gbuffer)."""
+        ctx = ctx or self.ctx
+        H, W, dev = self.desc.height, self.desc.width, self.sum.device
+        g = {k: _torch.empty((H, W, 3) if capi.GBUFFER_CHANNELS[k][1] == 3 else (H, W), dtype=_torch.float32, device=dev) for k in DENOISE_GUIDES}
+        ctx.render_gbuffer(self.desc, {k: x.data_ptr() for k, x in g.items()}, stream=ctx._raw_stream(stream))
+        return g
+
+    def denoise(self, params=None, guides=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, stream=None):
+        """(rgb8, f32, linear, var) of the current sums through the variance-guided filter (Context.denoise_accumulated); needs moments=True.  Without
+        `guides` the G-buffer of the context's current camera is rendered first."""
+        if self.sum_sq is None:
+            raise ValueError("the denoiser is guided by the variance: Accumulator(..., moments=True)")
+        guides = self.guides(stream=stream) if guides is None else guides
+        return self.ctx.denoise_accumulated(self.desc, self.sum, self.sum_sq, guides, samples_done=self.samples_done, n=self.n if self.samples_done is None else None,
+                                            params=params, want_rgb8=want_rgb8, want_f32=want_f32, want_linear=want_linear, want_var=want_var, stream=stream)
 
 
 class Multi:

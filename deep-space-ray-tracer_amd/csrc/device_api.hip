@@ -345,6 +345,7 @@ struct DsrtContext {
     DevBuf<uint8_t> adaptive_mask;  // dsrt_render_adaptive: the mask between its passes
     DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
     DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
+    DevBuf<float4> dn_cl[2], dn_vl[2], dn_nr, dn_xf, dn_al;   // dsrt_denoise_accumulated: 7 records of 16 bytes per pixel (launchers.h, DenoiseBuffers)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t done = nullptr;      // recorded behind every render: the next render on ANY stream waits for it (queue words, spill strip,
     bool done_valid = false;        // pre-pass arrays and partial sums are per context, so a context has one render in flight)
@@ -1378,6 +1379,138 @@ int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, c
         }))) return rc;
     if (h_n) HIP_TRY(hipMemcpy(h_n, n.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return DSRT_OK;
+    });
+}
+
+// ---- The denoiser (include/dsrt.h, DENOISER; denoise_kernel.hip): prepare, one a-trous launch per iteration, output.  It reads the caller's sums, counts and guides
+// and writes the caller's outputs and the context's own seven records per pixel; the render buffers, camera and sun are not touched. ----
+namespace {
+constexpr size_t kDenoiseGuideBytes[4] = {12, 12, 12, 4};                       // DsrtDenoiseGuides: normal, position, albedo, range
+static_assert(sizeof(DsrtDenoiseGuides) == 4 * sizeof(void*), "kDenoiseGuideBytes has one entry per pointer of DsrtDenoiseGuides");
+
+int check_denoise_params(const char* fn, const DsrtDenoise* dn) {
+    if (!dn) return accum_fail(fn, "null argument");
+    if (dn->iterations < 0 || dn->iterations > 6) return accum_fail(fn, "iterations must be between 0 and 6");
+    if (dn->normal_power_log2 < 0 || dn->normal_power_log2 > 8) return accum_fail(fn, "normal_power_log2 must be between 0 and 8");
+    if (!(dn->sigma_l > 0.0f) || !(dn->sigma_z > 0.0f) || !(dn->sigma_a > 0.0f)) return accum_fail(fn, "sigma_l, sigma_z and sigma_a must be > 0");
+    return DSRT_OK;
+}
+
+// Everything dsrt_denoise_accumulated refuses, before anything is launched or written; the same for the host form's host pointers.
+int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* n, const DsrtDenoiseGuides* guides,
+                  const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
+    if (!ctx || !desc || !acc || !guides || !dn) return accum_fail(fn, "null argument");
+    if (!acc->sum || !acc->sum_sq) return accum_fail(fn, "DsrtAccum.sum or sum_sq is NULL (the filter is guided by the variance: both are required)");
+    if (!guides->normal || !guides->position || !guides->albedo || !guides->range) return accum_fail(fn, "a guide channel is NULL (normal, position, albedo and range are required)");
+    if (desc->rng_mode != 1) return accum_fail(fn, "accumulated sums are rng_mode 1's");
+    if (desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
+    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
+    if (desc->width < 2 || desc->height < 2) return accum_fail(fn, "width and height must be >= 2");
+    if ((unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) return accum_fail(fn, "image too large (2^31 pixels)");
+    if (!n && samples_done < 2) return accum_fail(fn, "samples_done < 2 (the variance needs two samples; pass per-pixel counts otherwise)");
+    if (int rc = check_denoise_params(fn, dn)) return rc;
+    if (!rgb8 && !f32 && !linear && !var) return accum_fail(fn, "no output");
+    const size_t px = (size_t)desc->width * desc->height;
+    Staged in[7] = {{acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {n, px * sizeof(uint32_t), Dir::In}};
+    channels(*guides, kDenoiseGuideBytes, px, Dir::In, in + 3);
+    const Staged out[4] = {{rgb8, px * 3, Dir::Out}, {f32, px * 3 * sizeof(float), Dir::Out}, {linear, px * 3 * sizeof(float), Dir::Out}, {var, px * 3 * sizeof(float), Dir::Out}};
+    if (((uintptr_t)acc->sum | (uintptr_t)acc->sum_sq) & 7u) return accum_fail(fn, "a sum pointer is not 8-byte aligned");
+    for (int k = 2; k < 7; ++k) if ((uintptr_t)in[k].host & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
+    for (int k = 1; k < 4; ++k) if ((uintptr_t)out[k].host & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
+    for (int a = 0; a < 4; ++a) {
+        for (const Staged& i : in) if (ranges_overlap(out[a], i)) return accum_fail(fn, "an output range overlaps an input range");
+        for (int b = a + 1; b < 4; ++b) if (ranges_overlap(out[a], out[b])) return accum_fail(fn, "two output ranges overlap");
+    }
+    return DSRT_OK;
+}
+}  // namespace
+
+void dsrt_denoise_defaults(DsrtDenoise* out) {
+    if (!out) return;
+    out->iterations = 5; out->normal_power_log2 = 5;
+    out->sigma_l = 1.0f; out->sigma_z = 0.01f; out->sigma_a = 0.1f;          // sigma_l: 1, not SVGF's 4 (include/dsrt.h says why)
+}
+
+int dsrt_denoise_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                             const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, void* stream_v) {
+    return dsrt::guarded("dsrt_denoise_accumulated", [&]() -> int {
+    int rc = check_denoise("dsrt_denoise_accumulated", ctx, desc, acc, samples_done, d_n, guides, dn, d_rgb8, d_f32, d_linear, d_var);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const size_t px = (size_t)desc->width * desc->height;
+    // (growing frees the old records: the launch that may still read them has to be over first)
+    if (ctx->dn_al.n < px && ctx->done_valid) HIP_TRY(hipEventSynchronize(ctx->done));
+    for (int k = 0; k < 2; ++k) if ((rc = ctx->dn_cl[k].grow(px)) || (rc = ctx->dn_vl[k].grow(px))) return rc;
+    if ((rc = ctx->dn_nr.grow(px)) || (rc = ctx->dn_xf.grow(px)) || (rc = ctx->dn_al.grow(px))) return rc;
+    const DenoiseBuffers b{{ctx->dn_cl[0].p, ctx->dn_cl[1].p}, {ctx->dn_vl[0].p, ctx->dn_vl[1].p}, ctx->dn_nr.p, ctx->dn_xf.p, ctx->dn_al.p};
+    if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, the G-buffer) comes first
+    HIP_TRY(launch_denoise_prepare((const unsigned long long*)acc->sum, (const unsigned long long*)acc->sum_sq, samples_done, d_n, guides->normal, guides->position,
+                                   guides->albedo, guides->range, px, b, stream));
+    for (int i = 0; i < dn->iterations; ++i)
+        HIP_TRY(launch_denoise_atrous(b, i & 1, desc->width, desc->height, 1 << i, dn->normal_power_log2, dn->sigma_l, dn->sigma_z, dn->sigma_a, stream));
+    const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
+    HIP_TRY(launch_denoise_output(b, dn->iterations & 1, px, inv_gamma, desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
+    return launch_finish(ctx, stream, nullptr);                                      // the records are the context's: its next launch on any stream comes behind
+    });
+}
+
+int dsrt_denoise_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n, const DsrtDenoiseGuides* h_guides,
+                                     const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var) {
+    return dsrt::guarded("dsrt_denoise_accumulated_to_host", [&]() -> int {
+    if (int rc = check_denoise("dsrt_denoise_accumulated_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, dn, h_rgb8, h_f32, h_linear, h_var)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * desc->height;
+    Staged s[11] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {h_n, px * sizeof(uint32_t), Dir::In}};
+    channels(*h_guides, kDenoiseGuideBytes, px, Dir::In, s + 3);
+    s[7] = Staged{h_rgb8, px * 3, Dir::Out};
+    s[8] = Staged{h_f32, px * 3 * sizeof(float), Dir::Out};
+    s[9] = Staged{h_linear, px * 3 * sizeof(float), Dir::Out};
+    s[10] = Staged{h_var, px * 3 * sizeof(float), Dir::Out};
+    return staged_call(s, [&](void* const* d) -> int {
+        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
+        const DsrtDenoiseGuides g = pointers_as<DsrtDenoiseGuides>(d + 3);
+        const int r = dsrt_denoise_accumulated(ctx, desc, &acc, samples_done, (const uint32_t*)d[2], &g, dn, (uint8_t*)d[7], (float*)d[8], (float*)d[9], (float*)d[10], nullptr);
+        if (r) return r;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return DSRT_OK;
+    });
+    });
+}
+
+// The convenience form: desc->spp samples with second moments, the G-buffer of the current camera, the filter; sums and guides live on the device for the call.
+int dsrt_render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_denoised_to_host", [&]() -> int {
+    const char* fn = "dsrt_render_denoised_to_host";
+    if (!ctx || !desc) return accum_fail(fn, "null argument");
+    if (int rc = check_denoise_params(fn, dn)) return rc;
+    if (!h_rgb8 && !h_f32 && !h_linear && !h_var) return accum_fail(fn, "no output");
+    const int spp = desc->spp < 1 ? 1 : desc->spp;
+    if (int rc = check_sample_set(fn, ctx, desc, 0, spp, 1)) return rc;               // DSRT_ERR_NO_SCENE before an upload; rng_mode 1, no shards
+    if (spp < 2) return accum_fail(fn, "spp < 2 (the variance needs two samples)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * (size_t)desc->height;
+    DevBuf<unsigned long long> sum, sq;
+    DevBuf<float> normal, position, albedo, range;
+    int rc;
+    if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px))) return rc;
+    HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
+    const DsrtAccum acc{(uint64_t*)sum.p, (uint64_t*)sq.p};
+    const DsrtDenoiseGuides guides{normal.p, position.p, albedo.p, range.p};
+    DsrtGBuffer gb;
+    std::memset(&gb, 0, sizeof gb);
+    gb.normal = normal.p; gb.position = position.p; gb.albedo = albedo.p; gb.range = range.p;
+    const Staged s[4] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_linear, px * 3 * sizeof(float), Dir::Out}, {h_var, px * 3 * sizeof(float), Dir::Out}};
+    DsrtStats local;
+    return staged_call(s, [&](void* const* d) -> int {
+        int r;
+        if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &acc, nullptr, stats ? stats : &local))) return r;
+        if ((r = dsrt_render_gbuffer(ctx, desc, &gb, nullptr, nullptr))) return r;
+        if ((r = dsrt_denoise_accumulated(ctx, desc, &acc, spp, nullptr, &guides, dn, (uint8_t*)d[0], (float*)d[1], (float*)d[2], (float*)d[3], nullptr))) return r;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return DSRT_OK;
+    });
     });
 }
 

@@ -52,4 +52,15 @@ hipError_t launch_philox(unsigned long long seed, unsigned long long sub, int n,
 hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream);                                  // gbuffer_kernel.hip
 hipError_t launch_raycast(const RaycastArgs& a, bool any_hit, int blocks, hipStream_t stream);                   // raycast_kernel.hip
 
+// denoise_kernel.hip (include/dsrt.h, DENOISER).  The filter's working memory, one 16-byte record per pixel each: {c.rgb, L(c)} and {v.rgb, L(v)} twice (the
+// iterations ping-pong between [0] and [1]), and the guides {N, range}, {X, filterable}, {A, 0}.  prepare fills cl[0], vl[0] and the guides; an a-trous launch
+// reads cl / vl[src] and writes [src ^ 1]; output reads [src].
+struct DenoiseBuffers { float4* cl[2]; float4* vl[2]; float4* nr; float4* xf; float4* al; };
+hipError_t launch_denoise_prepare(const unsigned long long* sums, const unsigned long long* sums_sq, int samples_done, const uint32_t* counts, const float* normal,
+                                  const float* position, const float* albedo, const float* range, size_t n_pixels, const DenoiseBuffers& b, hipStream_t stream);
+hipError_t launch_denoise_atrous(const DenoiseBuffers& b, int src, int W, int H, int step, int normal_power_log2, float sigma_l, float sigma_z, float sigma_a,
+                                 hipStream_t stream);
+hipError_t launch_denoise_output(const DenoiseBuffers& b, int src, size_t n_pixels, float inv_gamma, bool device_libm, uint8_t* out_rgb8, float* out_f32, float* out_linear,
+                                 float* out_var, hipStream_t stream);
+
 }  // namespace dsrt

@@ -157,6 +157,8 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_ACCUM: return sizeof(DsrtAccum);
         case DSRT_SIZEOF_ADAPTIVE: return sizeof(DsrtAdaptive);
         case DSRT_SIZEOF_ADAPTIVE_STATS: return sizeof(DsrtAdaptiveStats);
+        case DSRT_SIZEOF_DENOISE_GUIDES: return sizeof(DsrtDenoiseGuides);
+        case DSRT_SIZEOF_DENOISE: return sizeof(DsrtDenoise);
         default: return 0;
     }
 }

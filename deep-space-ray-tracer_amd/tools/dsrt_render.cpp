@@ -18,6 +18,10 @@
 //     --adaptive-passes P (8) interleaved passes, the first --adaptive-min-passes M (2) over every pixel, the later ones over the pixels whose standard error
 //     still exceeds TOL times their mean (or times --adaptive-floor F, for dark pixels) -- and writes <frame> and <frame>_spp.pfm, every pixel's sample count
 //     (with --variance also <frame>_var.pfm).
+//   * rng_mode 1 only: --denoise [ITER] reconstructs each frame from its samples with the variance-guided a-trous filter (include/dsrt.h, DENOISER: the
+//     library's default parameters, ITER iterations if given) -- the reference's reconstruction step runs outside its renderer (scripts/upsample.py) -- and
+//     writes <frame> denoised and <frame>_raw undenoised, byte for byte the frame without the flag (with --variance also <frame>_var.pfm, the
+//     filtered image's propagated variance).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,7 +51,8 @@ int main(int argc, char** argv) {
     int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0, passes = 0;
     int adaptive_passes = 8, adaptive_min = 2;
     float adaptive_tol = 0.0f, adaptive_floor = 0.0f;
-    bool adaptive = false, adaptive_detail = false;
+    bool adaptive = false, adaptive_detail = false, denoise = false;
+    int denoise_iterations = -1;                                    // -1: the library's default
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -78,8 +83,12 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive-passes") { adaptive_detail = true; adaptive_passes = std::atoi(next("--adaptive-passes")); }
         else if (a == "--adaptive-min-passes") { adaptive_detail = true; adaptive_min = std::atoi(next("--adaptive-min-passes")); }
         else if (a == "--adaptive-floor") { adaptive_detail = true; adaptive_floor = (float)std::atof(next("--adaptive-floor")); }
+        else if (a == "--denoise") {                                // rng_mode 1: the variance-guided filter over each frame; the value (iterations) is optional
+            denoise = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_iterations = std::atoi(argv[++i]);
+        }
         else if (a == "--upscale") std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (adaptive_detail && !adaptive) { std::fprintf(stderr, "dsrt_render: --adaptive-passes, --adaptive-min-passes and --adaptive-floor need --adaptive TOL\n"); return 2; }
@@ -88,6 +97,10 @@ int main(int argc, char** argv) {
     if (adaptive && !(adaptive_tol >= 0.0f && adaptive_floor >= 0.0f)) { std::fprintf(stderr, "dsrt_render: --adaptive and --adaptive-floor must be >= 0\n"); return 2; }
     if (adaptive && (adaptive_passes < 1 || adaptive_passes > std::min(std::max(spp, 1), 64))) { std::fprintf(stderr, "dsrt_render: --adaptive-passes must be between 1 and min(--spp, 64)\n"); return 2; }
     if (adaptive && (adaptive_min < 1 || adaptive_min > adaptive_passes)) { std::fprintf(stderr, "dsrt_render: --adaptive-min-passes must be between 1 and --adaptive-passes\n"); return 2; }
+    if (denoise && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --denoise needs --rng-mode 1 (or --fast)\n"); return 2; }
+    if (denoise && (passes != 0 || adaptive || gbuffer)) { std::fprintf(stderr, "dsrt_render: --denoise does not combine with --passes / --adaptive / --gbuffer\n"); return 2; }
+    if (denoise && denoise_iterations > 6) { std::fprintf(stderr, "dsrt_render: --denoise ITER must be between 0 and 6\n"); return 2; }
+    if (denoise && spp < 2) { std::fprintf(stderr, "dsrt_render: --denoise needs --spp 2 or more\n"); return 2; }
     if ((passes != 0 || variance) && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --passes and --variance need --rng-mode 1 (or --fast)\n"); return 2; }
     if (passes < 0 || passes > std::max(spp, 1)) { std::fprintf(stderr, "dsrt_render: --passes must be between 1 and --spp\n"); return 2; }
     if (variance && spp < 2) { std::fprintf(stderr, "dsrt_render: --variance needs --spp 2 or more\n"); return 2; }
@@ -183,6 +196,45 @@ int main(int argc, char** argv) {
                         100.0 * (double)st.samples_total / ((double)px * spp), spp);
             for (int p = 0; p < st.passes_run; ++p) std::printf(" %u", st.active[p]);
             std::printf("\nSaved %s, %s_spp.pfm%s\n", path.c_str(), base.c_str(), variance ? " and _var.pfm" : "");
+        }
+        dsrt_ctx_destroy(ctx);
+        dsrt_host_scene_destroy(hs);
+        std::printf("Done.\n");
+        return 0;
+    }
+    if (denoise) {
+        // Each frame: its sums with second moments, the raw image they resolve to, the G-buffer of its camera, the filter (include/dsrt.h, DENOISER).
+        const size_t px = (size_t)width * height;
+        std::vector<uint64_t> sum(image_bytes), sq(image_bytes);
+        std::vector<uint8_t> raw(image_bytes), img(image_bytes);
+        std::vector<float> normal(image_bytes), position(image_bytes), albedo(image_bytes), range(px), var(variance ? image_bytes : 0);
+        const DsrtAccum acc{sum.data(), sq.data()};
+        const DsrtDenoiseGuides guides{normal.data(), position.data(), albedo.data(), range.data()};
+        DsrtGBuffer g;
+        std::memset(&g, 0, sizeof g);
+        g.normal = normal.data(); g.position = position.data(); g.albedo = albedo.data(); g.range = range.data();
+        DsrtDenoise dn;
+        dsrt_denoise_defaults(&dn);
+        if (denoise_iterations >= 0) dn.iterations = denoise_iterations;
+        const std::string ext = png ? ".png" : ".ppm";
+        auto write = [&](const std::string& path, const std::vector<uint8_t>& image) {
+            return (png ? dsrt_write_png(path.c_str(), image.data(), width, height) : dsrt_write_ppm(path.c_str(), image.data(), width, height)) == DSRT_OK;
+        };
+        for (size_t q = 0; q < ids.size(); ++q) {
+            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
+            std::fill(sum.begin(), sum.end(), 0);
+            std::fill(sq.begin(), sq.end(), 0);
+            if (dsrt_render_accumulate_to_host(ctx, &d, 0, spp, 1, &acc, nullptr) != DSRT_OK) return fail("rendering the samples");
+            if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, spp, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving the raw image");
+            if (dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK) return fail("rendering the G-buffer");
+            if (dsrt_denoise_accumulated_to_host(ctx, &d, &acc, spp, nullptr, &guides, &dn, img.data(), nullptr, nullptr, variance ? var.data() : nullptr) != DSRT_OK)
+                return fail("denoising");
+            char stem[64];
+            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
+            const std::string base = out_dir + stem;
+            if (!write(base + ext, img) || !write(base + "_raw" + ext, raw)) return fail("writing the frame");
+            if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
+            std::printf("denoise: %d iterations\nSaved %s, %s_raw%s%s\n", dn.iterations, (base + ext).c_str(), base.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
         }
         dsrt_ctx_destroy(ctx);
         dsrt_host_scene_destroy(hs);

@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -53,6 +53,8 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_ACCUM       9
 #define DSRT_SIZEOF_ADAPTIVE    10
 #define DSRT_SIZEOF_ADAPTIVE_STATS 11
+#define DSRT_SIZEOF_DENOISE_GUIDES 12
+#define DSRT_SIZEOF_DENOISE     13
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -550,6 +552,70 @@ int dsrt_render_adaptive(DsrtContext* ctx, const DsrtRenderDesc* desc, const Dsr
                          float* d_var_of_mean, void* stream, DsrtAdaptiveStats* stats);
 int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* adaptive, uint32_t* h_n, uint8_t* h_rgb8, float* h_f32,
                                  float* h_var_of_mean, DsrtAdaptiveStats* stats);
+
+/*
+ * DENOISER (rng_mode 1, on top of SAMPLE SETS and the G-BUFFER): an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) in the variance-guided form of SVGF,
+ * on a single frame.  It reconstructs an image from the samples already taken: the per-pixel mean and its variance come from the sums, the edge-stopping guides
+ * (normal, position, albedo, range of the pixel-centre ray) from dsrt_render_gbuffer.  What it computes is written out here in full; it uses correctly rounded
+ * fp32 operations only, so a CPU reproduces every bit (tests/_denoise_model.py).
+ *
+ * THE ARITHMETIC.  fp32 unless marked double; every operation one correctly rounded IEEE operation, never contracted, in the order written; sqrtf and / are the IEEE
+ * ones; the constants are float literals.
+ *     L(x) = (0.2126f*x.r + 0.7152f*x.g) + 0.0722f*x.b            dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *     h = {1/16, 1/4, 3/8, 1/4, 1/16}  (the B3 spline)            k3 = {1/4, 1/2, 1/4}
+ *   Start, per pixel p with n its sample count (samples_done, or d_n[p]):
+ *     c   = dsrt_resolve_accumulated_counts' mean: (float)((double)sum * (1.0 / 2^20 / n)), in double, converted once; +0 for n = 0
+ *     v   = its variance of the mean, as defined with DsrtRenderDesc.rng_mode; +0 for n < 2
+ *     F_p = (range_p <= FLT_MAX) && n >= 2: "filterable" (a NaN range is not)
+ *   Iteration i = 0 .. iterations-1, step s = 1 << i, takes (c, v) to (c', v'), reading the previous iteration's images only:
+ *     !F_p:  c' = c, v' = v, bit for bit.  Otherwise
+ *     g     = sum over ey = -1..1 (outer, ascending), ex = -1..1 of (k3[ex+1]*k3[ey+1]) * L(v_q), q = p + (ex, ey) CLAMPED to the image, starting from +0;
+ *             every pixel counts, filterable or not
+ *     den_l = sigma_l * sqrtf(g) + 0x1p-20f;   den_z = sigma_z * range_p;   lp = L(c_p)
+ *     taps dy = -2..2 (outer), dx = -2..2, q = p + s*(dx, dy) in buffer coordinates (row 0 the top row); a tap outside the image or with !F_q is skipped; else
+ *         wn = fmaxf(dot(N_p, N_q), 0.0f);  normal_power_log2 times: wn = wn * wn;
+ *         D  = X_q - X_p;   ez = fabsf(dot(N_p, D)) / den_z;
+ *         el = fabsf(L(c_q) - lp) / den_l;
+ *         da = A_q - A_p;   ea2 = dot(da, da) / (sigma_a * sigma_a);
+ *         w  = ((h[dx+2]*h[dy+2]) * wn) / (((1.0f + ez*ez) * (1.0f + el*el)) * (1.0f + ea2));
+ *         sw += w;   sc.k += w * c_q.k;   sv.k += (w*w) * v_q.k;                    (k = r, g, b; all sums start at +0.0f)
+ *     sw > 0:  c'.k = sc.k / sw,  v'.k = sv.k / (sw*sw);  otherwise p is copied through
+ *   Output, after the last iteration: d_linear = c, d_var = v; d_rgb8 and d_f32 are dsrt_resolve_accumulated's tone map and 8-bit store applied to c
+ *   (desc->math_mode chooses powf as it does there).
+ * The Cauchy weights 1/(1+e^2) stand where SVGF has exp(-e): expf is in no correctly rounded set, and the filter does not need it.  The geometry term is the distance
+ * of q's hit point from p's tangent plane relative to p's range: zero along a flat oblique surface, which a depth difference gets wrong.
+ * BACKGROUND AND SILHOUETTE: a pixel whose centre ray misses is never touched and never contributes -- space stays black and the silhouette stays where the renderer
+ * put it; so the partially covered pixels just OUTSIDE the silhouette (centre ray misses, some samples hit) stay unfiltered.
+ * Guides must be finite wherever `range` is finite; the call does not check.
+ *
+ * dsrt_denoise_accumulated: at least one of d_rgb8 (bytes), d_f32, d_linear, d_var (floats), each width*height*3 elements.  Asynchronous on `stream`; like
+ *   dsrt_resolve_accumulated and dsrt_render_gbuffer it waits for the context's previous launch, the next launch waits for it, it needs no scene, and the context's
+ *   camera, sun and render buffers are left as they were.  Sums, counts and guides are read only.  Working memory (112 bytes per pixel: the packed guides and two
+ *   colour / variance pairs to ping-pong) belongs to the context: allocated on first use, grown for a larger frame, freed by dsrt_ctx_destroy.
+ *   DSRT_ERR_INVALID: a NULL ctx, desc, acc, acc->sum, acc->sum_sq, guides, guide channel or params; rng_mode != 1; shard_count > 1; width or height < 2;
+ *   samples_done < 2 when d_n is NULL; iterations outside [0, 6]; normal_power_log2 outside [0, 8]; a sigma that is not > 0 (NaN is refused); no output; a pointer not
+ *   aligned to its element; an output range that overlaps an input range or another output.  A refused call touches no buffer.
+ * dsrt_denoise_accumulated_to_host: the same from HOST buffers into HOST buffers, synchronously.
+ * dsrt_render_denoised_to_host: the convenience form -- desc->spp samples with second moments, the G-buffer of the current camera, and the call above.
+ *   DSRT_ERR_NO_SCENE before an upload.  stats (optional): the accumulate launch's, as dsrt_render_accumulate fills them; spp must be at least 2.
+ * dsrt_denoise_defaults: iterations 5, normal_power_log2 5, sigma_l 1, sigma_z 0.01, sigma_a 0.1.  sigma_l was first set to SVGF's 4; on the parity scenes at 8 and
+ *   16 samples per pixel that blurs the station's sun shadows until the error RISES with the iterations (1.2 times the unfiltered error after five), while with 1 --
+ *   a tap's weight halves at one standard deviation of luminance -- it falls to about half and stays there (tests/test_denoise_host.py).
+ */
+typedef struct DsrtDenoiseGuides {   /* DEVICE (HOST for _to_host) buffers, width*height elements, image order: channels of DsrtGBuffer */
+    const float* normal;             /* x3 */
+    const float* position;           /* x3 */
+    const float* albedo;             /* x3 */
+    const float* range;              /* x1, +inf on a miss */
+} DsrtDenoiseGuides;
+typedef struct DsrtDenoise { int iterations; int normal_power_log2; float sigma_l, sigma_z, sigma_a; } DsrtDenoise;
+void dsrt_denoise_defaults(DsrtDenoise* out);
+int  dsrt_denoise_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n /* NULL = samples_done for every pixel */,
+                              const DsrtDenoiseGuides* guides, const DsrtDenoise* params, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, void* stream);
+int  dsrt_denoise_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n,
+                                      const DsrtDenoiseGuides* h_guides, const DsrtDenoise* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var);
+int  dsrt_render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var,
+                                  DsrtStats* stats);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
