@@ -231,6 +231,24 @@ def denoise_defaults(**changes):
     return p
 
 
+def temporal_defaults(**changes):
+    """dsrt_temporal_defaults: the DsrtTemporal the library fills (alpha_min, normal_cos_min, plane_tol, min_support), with `changes` applied."""
+    p = capi.DsrtTemporal()
+    lib.dsrt_temporal_defaults(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(capi.DsrtTemporal._fields_):
+            raise ValueError(f"DsrtTemporal has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def aligned_zeros(count, dtype=np.float32, align=64):
+    """A zeroed numpy array of `count` elements whose data starts on an `align`-byte boundary (a host history buffer must be 16-byte aligned)."""
+    raw = np.zeros(count * np.dtype(dtype).itemsize + align, np.uint8)
+    off = (-raw.ctypes.data) % align
+    return raw[off:off + count * np.dtype(dtype).itemsize].view(dtype)
+
+
 def shard_layout(desc):
     total, mine, padded, nbytes = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
     _check(lib.dsrt_shard_layout(C.byref(desc), C.byref(total), C.byref(mine), C.byref(padded), C.byref(nbytes)), "dsrt_shard_layout")
@@ -663,6 +681,86 @@ class Context:
         _check(lib.dsrt_render_denoised_to_host(self._h, C.byref(desc), C.byref(params), ptr(rgb), ptr(f32), ptr(lin), ptr(var), C.byref(st)), "dsrt_render_denoised_to_host")
         return rgb, f32, lin, var, st
 
+    # ---- temporal accumulation (include/dsrt.h, TEMPORAL ACCUMULATION): the denoiser with reprojected frame history in front of its iterations ----
+    def denoise_temporal(self, desc, sums, sum_sq, guides, history_next, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None, params=None,
+                         want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False, want_weight=False, stream=None):
+        """dsrt_denoise_temporal: denoise_accumulated with the history stage.  history_prev / history_next: float32 device tensors of width*height*16 elements
+        (the caller ping-pongs two); prev_camera: the GPUCamera history_prev was written under -- both None for the first frame of a sequence.  temporal: a
+        DsrtTemporal (temporal_defaults()).  Returns (rgb8, f32, linear, var, prev_xy, weight) device tensors -- prev_xy (height, width, 2), weight (height, width) --
+        None where not asked for."""
+        sums = self._sum_tensor(desc, sums, "sums")
+        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq")
+        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
+        if n is None and samples_done is None:
+            raise ValueError("denoise_temporal needs samples_done or per-pixel counts n")
+        g = self._guide_tensors(desc, guides)
+        for what, h in (("history_prev", history_prev), ("history_next", history_next)):
+            if h is None:
+                continue
+            if not isinstance(h, _torch.Tensor) or h.dtype != _torch.float32 or h.device.type != "cuda" or h.device.index != self.device:
+                raise TypeError(f"{what} must be a float32 torch tensor on cuda:{self.device}")
+            if not h.is_contiguous() or h.numel() != desc.width * desc.height * capi.HISTORY_FLOATS:
+                raise ValueError(f"{what} must be contiguous with width*height*{capi.HISTORY_FLOATS} elements")
+        params = denoise_defaults() if params is None else params
+        temporal = temporal_defaults() if temporal is None else temporal
+        shape, dev = (desc.height, desc.width, 3), sums.device
+        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
+        f32, lin, var = (_torch.empty(shape, dtype=_torch.float32, device=dev) if w else None for w in (want_f32, want_linear, want_var))
+        pxy = _torch.empty((desc.height, desc.width, 2), dtype=_torch.float32, device=dev) if want_prev_xy else None
+        wgt = _torch.empty((desc.height, desc.width), dtype=_torch.float32, device=dev) if want_weight else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
+        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
+        _check(lib.dsrt_denoise_temporal(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(n), C.byref(gd), C.byref(prev_camera) if prev_camera is not None else None,
+                                         ptr(history_prev), ptr(history_next), C.byref(temporal), C.byref(params), ptr(rgb), ptr(f32), ptr(lin), ptr(var), ptr(pxy), ptr(wgt),
+                                         C.c_void_p(self._raw_stream(stream))), "dsrt_denoise_temporal")
+        return rgb, f32, lin, var, pxy, wgt
+
+    def denoise_temporal_to_host(self, desc, sums, sum_sq, guides, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None, params=None,
+                                 want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=True, want_weight=True):
+        """dsrt_denoise_temporal_to_host: the same from numpy arrays into numpy arrays.  history_prev: float32 (H, W, 16) or None.  Returns
+        (rgb8, f32, linear, var, prev_xy, weight, history_next) -- history_next (H, W, 16), 64-byte aligned."""
+        H, W = desc.height, desc.width
+        S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
+        S2 = np.ascontiguousarray(sum_sq, np.uint64).reshape(H, W, 3)
+        cnt = np.ascontiguousarray(n, np.uint32).reshape(H, W) if n is not None else None
+        if set(guides) != set(DENOISE_GUIDES):
+            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
+        g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
+        prev = None
+        if history_prev is not None:
+            prev = aligned_zeros(H * W * capi.HISTORY_FLOATS)
+            prev[:] = np.asarray(history_prev, np.float32).reshape(-1)
+        nxt = aligned_zeros(H * W * capi.HISTORY_FLOATS)
+        params = denoise_defaults() if params is None else params
+        temporal = temporal_defaults() if temporal is None else temporal
+        rgb = np.zeros((H, W, 3), np.uint8) if want_rgb8 else None
+        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
+        pxy = np.zeros((H, W, 2), np.float32) if want_prev_xy else None
+        wgt = np.zeros((H, W), np.float32) if want_weight else None
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
+        acc = DsrtAccum(ptr(S), ptr(S2))
+        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
+        _check(lib.dsrt_denoise_temporal_to_host(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(cnt), C.byref(gd),
+                                                 C.byref(prev_camera) if prev_camera is not None else None, ptr(prev), ptr(nxt), C.byref(temporal), C.byref(params), ptr(rgb), ptr(f32),
+                                                 ptr(lin), ptr(var), ptr(pxy), ptr(wgt)), "dsrt_denoise_temporal_to_host")
+        return rgb, f32, lin, var, pxy, wgt, nxt.reshape(H, W, capi.HISTORY_FLOATS)
+
+    def render_denoised_temporal_to_host(self, desc, params=None, temporal=None, reset=False, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False):
+        """dsrt_render_denoised_temporal_to_host: render_denoised_to_host with the history the CONTEXT keeps from call to call (reset=True starts a new sequence;
+        change desc.seed from frame to frame).  Returns (rgb8, f32, linear, var, prev_xy, DsrtStats)."""
+        H, W = desc.height, desc.width
+        params = denoise_defaults() if params is None else params
+        temporal = temporal_defaults() if temporal is None else temporal
+        rgb = np.zeros((H, W, 3), np.uint8)
+        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
+        pxy = np.zeros((H, W, 2), np.float32) if want_prev_xy else None
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
+        st = DsrtStats()
+        _check(lib.dsrt_render_denoised_temporal_to_host(self._h, C.byref(desc), C.byref(params), C.byref(temporal), 1 if reset else 0, ptr(rgb), ptr(f32), ptr(lin), ptr(var),
+                                                         ptr(pxy), C.byref(st)), "dsrt_render_denoised_temporal_to_host")
+        return rgb, f32, lin, var, pxy, st
+
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""
         old = C.c_uint32()
@@ -777,6 +875,50 @@ class Accumulator:
         guides = self.guides(stream=stream) if guides is None else guides
         return self.ctx.denoise_accumulated(self.desc, self.sum, self.sum_sq, guides, samples_done=self.samples_done, n=self.n if self.samples_done is None else None,
                                             params=params, want_rgb8=want_rgb8, want_f32=want_f32, want_linear=want_linear, want_var=want_var, stream=stream)
+
+
+class TemporalDenoiser:
+    """A sequence of frames through Context.denoise_temporal: owns the two history tensors and the previous frame's camera.
+
+        td = TemporalDenoiser(ctx, desc)
+        for f, (cam, sun) in enumerate(views):
+            ctx.set_camera_sun(cam, sun)
+            d = make_desc(W, H, spp, seed=seed0 + f, rng_mode=1)           # a different seed per frame: the blend takes the frames as independent
+            acc = Accumulator(ctx, d, moments=True); acc.render(0)
+            rgb, _, linear, var, prev_xy, weight = td.step(acc, cam, want_prev_xy=True)
+    """
+
+    def __init__(self, ctx, desc, temporal=None, params=None):
+        self.ctx, self.width, self.height = ctx, desc.width, desc.height
+        self.temporal = temporal_defaults() if temporal is None else temporal
+        self.params = denoise_defaults() if params is None else params
+        n = desc.width * desc.height * capi.HISTORY_FLOATS
+        self.history = [_torch.zeros(n, dtype=_torch.float32, device=f"cuda:{ctx.device}") for _ in range(2)]
+        self.current = 0                    # history[current] holds the last frame's records once prev_camera is set
+        self.prev_camera = None
+
+    def reset(self):
+        """Start a new sequence: the next step has no history."""
+        self.prev_camera = None
+
+    def step(self, accumulator, camera, guides=None, params=None, temporal=None, stream=None, **wants):
+        """One frame: `accumulator` holds its sums (moments=True), `camera` is the GPUCamera it was rendered with (the context's current one: without `guides`
+        the G-buffer is rendered here).  Returns Context.denoise_temporal's tuple; `wants`: its want_* flags."""
+        d = accumulator.desc
+        if (d.width, d.height) != (self.width, self.height):
+            raise ValueError("the accumulator's frame has another size than this sequence")
+        if accumulator.sum_sq is None:
+            raise ValueError("the denoiser is guided by the variance: Accumulator(..., moments=True)")
+        guides = accumulator.guides(stream=stream) if guides is None else guides
+        first = self.prev_camera is None
+        nxt = self.current if first else self.current ^ 1
+        out = self.ctx.denoise_temporal(d, accumulator.sum, accumulator.sum_sq, guides, self.history[nxt], None if first else self.prev_camera,
+                                        None if first else self.history[self.current], samples_done=accumulator.samples_done,
+                                        n=accumulator.n if accumulator.samples_done is None else None, temporal=temporal or self.temporal, params=params or self.params,
+                                        stream=stream, **wants)
+        self.current = nxt
+        self.prev_camera = GPUCamera.from_buffer_copy(camera)
+        return out
 
 
 class Multi:

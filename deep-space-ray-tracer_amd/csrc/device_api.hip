@@ -346,6 +346,11 @@ struct DsrtContext {
     DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
     DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
     DevBuf<float4> dn_cl[2], dn_vl[2], dn_nr, dn_xf, dn_al;   // dsrt_denoise_accumulated: 7 records of 16 bytes per pixel (launchers.h, DenoiseBuffers)
+    // dsrt_render_denoised_temporal_to_host: the sequence the context keeps -- two histories (tp_hist[tp_cur] holds the last frame's), that frame's camera and size
+    DevBuf<float4> tp_hist[2];
+    GPUCamera tp_camera{};
+    int tp_cur = 0, tp_width = 0, tp_height = 0;
+    bool tp_valid = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t done = nullptr;      // recorded behind every render: the next render on ANY stream waits for it (queue words, spill strip,
     bool done_valid = false;        // pre-pass arrays and partial sums are per context, so a context has one render in flight)
@@ -362,6 +367,7 @@ int install_scene(DsrtContext* ctx, const GPUScene& host_layout) {
     if (rc) return rc;
     ctx->scene = std::move(fresh);
     ctx->frame = ctx->scene->frame;
+    ctx->tp_valid = false;                         // a new scene: the temporal history of the old one is void
     return DSRT_OK;
 }
 
@@ -1431,13 +1437,49 @@ void dsrt_denoise_defaults(DsrtDenoise* out) {
     out->sigma_l = 1.0f; out->sigma_z = 0.01f; out->sigma_a = 0.1f;          // sigma_l: 1, not SVGF's 4 (include/dsrt.h says why)
 }
 
-int dsrt_denoise_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
-                             const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, void* stream_v) {
-    return dsrt::guarded("dsrt_denoise_accumulated", [&]() -> int {
-    int rc = check_denoise("dsrt_denoise_accumulated", ctx, desc, acc, samples_done, d_n, guides, dn, d_rgb8, d_f32, d_linear, d_var);
-    if (rc) return rc;
+// The temporal stage's part of a launch (dsrt_denoise_temporal, checked there): null for the plain denoiser.
+struct TemporalInput { const GPUCamera* prev_camera; const float* prev; float* next; const DsrtTemporal* tp; float* prev_xy; float* weight; };
+
+namespace {
+constexpr size_t kHistoryBytes = 64;                                            // per pixel: include/dsrt.h, TEMPORAL ACCUMULATION
+
+int check_temporal_params(const char* fn, const DsrtTemporal* tp) {
+    if (!tp) return accum_fail(fn, "null argument (DsrtTemporal)");
+    if (!(tp->alpha_min >= 0.0f && tp->alpha_min <= 1.0f)) return accum_fail(fn, "alpha_min must be between 0 and 1");
+    if (!(tp->normal_cos_min >= -1.0f && tp->normal_cos_min <= 1.0f)) return accum_fail(fn, "normal_cos_min must be between -1 and 1");
+    if (!(tp->plane_tol > 0.0f)) return accum_fail(fn, "plane_tol must be > 0");
+    if (!(tp->min_support > 0.0f && tp->min_support <= 1.0f)) return accum_fail(fn, "min_support must be > 0 and <= 1");
+    return DSRT_OK;
+}
+
+// Everything dsrt_denoise_temporal refuses, before anything is launched or written; the same for the host form's host pointers.
+int check_temporal(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* n, const DsrtDenoiseGuides* guides,
+                   const TemporalInput& t, const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
+    if (int rc = check_denoise(fn, ctx, desc, acc, samples_done, n, guides, dn, rgb8, f32, linear, var)) return rc;
+    if ((t.prev_camera != nullptr) != (t.prev != nullptr)) return accum_fail(fn, "the previous camera and the previous history go together: both NULL (first frame) or both given");
+    if (!t.next) return accum_fail(fn, "the next history is NULL (it is required)");
+    if (int rc = check_temporal_params(fn, t.tp)) return rc;
+    if (((uintptr_t)t.prev | (uintptr_t)t.next) & 15u) return accum_fail(fn, "a history buffer is not 16-byte aligned");
+    if (((uintptr_t)t.prev_xy | (uintptr_t)t.weight) & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
+    const size_t px = (size_t)desc->width * desc->height;
+    Staged in[8] = {{acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {n, px * sizeof(uint32_t), Dir::In}};
+    channels(*guides, kDenoiseGuideBytes, px, Dir::In, in + 3);
+    in[7] = Staged{t.prev, px * kHistoryBytes, Dir::In};
+    const Staged out[7] = {{t.next, px * kHistoryBytes, Dir::Out}, {t.prev_xy, px * 2 * sizeof(float), Dir::Out}, {t.weight, px * sizeof(float), Dir::Out},
+                           {rgb8, px * 3, Dir::Out}, {f32, px * 3 * sizeof(float), Dir::Out}, {linear, px * 3 * sizeof(float), Dir::Out}, {var, px * 3 * sizeof(float), Dir::Out}};
+    for (int a = 0; a < 3; ++a) {                                                // (the four image outputs among themselves and against the inputs: check_denoise)
+        for (const Staged& i : in) if (ranges_overlap(out[a], i)) return accum_fail(fn, "the next history, prev_xy or weight overlaps an input or the previous history");
+        for (int b = a + 1; b < 7; ++b) if (ranges_overlap(out[a], out[b])) return accum_fail(fn, "the next history, prev_xy or weight overlaps another output");
+    }
+    for (int a = 3; a < 7; ++a) if (ranges_overlap(out[a], in[7])) return accum_fail(fn, "an output range overlaps the previous history");
+    return DSRT_OK;
+}
+
+// The launches of dsrt_denoise_accumulated and dsrt_denoise_temporal (arguments checked by the caller): prepare, the temporal stage if there is one, the iterations, output.
+int denoise_launches(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                     const TemporalInput* t, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, hipStream_t stream) {
+    int rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
     const size_t px = (size_t)desc->width * desc->height;
     // (growing frees the old records: the launch that may still read them has to be over first)
     if (ctx->dn_al.n < px && ctx->done_valid) HIP_TRY(hipEventSynchronize(ctx->done));
@@ -1447,11 +1489,33 @@ int dsrt_denoise_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const
     if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, the G-buffer) comes first
     HIP_TRY(launch_denoise_prepare((const unsigned long long*)acc->sum, (const unsigned long long*)acc->sum_sq, samples_done, d_n, guides->normal, guides->position,
                                    guides->albedo, guides->range, px, b, stream));
+    if (t) {
+        TemporalArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.cl = b.cl[0]; a.vl = b.vl[0]; a.nr = b.nr; a.xf = b.xf;
+        a.prev = (const float4*)t->prev; a.next = (float4*)t->next; a.prev_xy = t->prev_xy; a.weight = t->weight;
+        a.counts = d_n; a.samples_done = samples_done; a.width = desc->width; a.height = desc->height;
+        if (t->prev_camera) {
+            const GPUCamera& c = *t->prev_camera;
+            const DsrtF3 v[7] = {c.origin, c.lower_left_corner, c.horizontal, c.vertical, c.u, c.v, c.w};
+            for (int k = 0; k < 7; ++k) { a.cam[3 * k] = v[k].x; a.cam[3 * k + 1] = v[k].y; a.cam[3 * k + 2] = v[k].z; }
+        }
+        a.alpha_min = t->tp->alpha_min; a.normal_cos_min = t->tp->normal_cos_min; a.plane_tol = t->tp->plane_tol; a.min_support = t->tp->min_support;
+        HIP_TRY(launch_temporal(a, stream));
+    }
     for (int i = 0; i < dn->iterations; ++i)
         HIP_TRY(launch_denoise_atrous(b, i & 1, desc->width, desc->height, 1 << i, dn->normal_power_log2, dn->sigma_l, dn->sigma_z, dn->sigma_a, stream));
     const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
     HIP_TRY(launch_denoise_output(b, dn->iterations & 1, px, inv_gamma, desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
     return launch_finish(ctx, stream, nullptr);                                      // the records are the context's: its next launch on any stream comes behind
+}
+}  // namespace
+
+int dsrt_denoise_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                             const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, void* stream_v) {
+    return dsrt::guarded("dsrt_denoise_accumulated", [&]() -> int {
+    if (int rc = check_denoise("dsrt_denoise_accumulated", ctx, desc, acc, samples_done, d_n, guides, dn, d_rgb8, d_f32, d_linear, d_var)) return rc;
+    return denoise_launches(ctx, desc, acc, samples_done, d_n, guides, nullptr, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
     });
 }
 
@@ -1511,6 +1575,103 @@ int dsrt_render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, c
         HIP_TRY(hipStreamSynchronize(nullptr));
         return DSRT_OK;
     });
+    });
+}
+
+// ---- Temporal accumulation (include/dsrt.h, TEMPORAL ACCUMULATION; temporal_kernel.hip): the denoiser with the history stage in front of its iterations ----
+void dsrt_temporal_defaults(DsrtTemporal* out) {
+    if (!out) return;
+    out->alpha_min = 0.1f; out->normal_cos_min = 0.9f; out->plane_tol = 0.01f; out->min_support = 0.9f;      // min_support: 0.9, not one tap of four (include/dsrt.h says why)
+}
+
+int dsrt_denoise_temporal(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                          const GPUCamera* prev_camera, const float* d_history_prev, float* d_history_next, const DsrtTemporal* tp, const DsrtDenoise* dn,
+                          uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, float* d_prev_xy, float* d_weight, void* stream_v) {
+    return dsrt::guarded("dsrt_denoise_temporal", [&]() -> int {
+    const TemporalInput t{prev_camera, d_history_prev, d_history_next, tp, d_prev_xy, d_weight};
+    if (int rc = check_temporal("dsrt_denoise_temporal", ctx, desc, acc, samples_done, d_n, guides, t, dn, d_rgb8, d_f32, d_linear, d_var)) return rc;
+    return denoise_launches(ctx, desc, acc, samples_done, d_n, guides, &t, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
+    });
+}
+
+int dsrt_denoise_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n, const DsrtDenoiseGuides* h_guides,
+                                  const GPUCamera* prev_camera, const float* h_history_prev, float* h_history_next, const DsrtTemporal* tp, const DsrtDenoise* dn,
+                                  uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, float* h_weight) {
+    return dsrt::guarded("dsrt_denoise_temporal_to_host", [&]() -> int {
+    const TemporalInput ht{prev_camera, h_history_prev, h_history_next, tp, h_prev_xy, h_weight};
+    if (int rc = check_temporal("dsrt_denoise_temporal_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, ht, dn, h_rgb8, h_f32, h_linear, h_var)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * desc->height;
+    Staged s[15] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {h_n, px * sizeof(uint32_t), Dir::In}};
+    channels(*h_guides, kDenoiseGuideBytes, px, Dir::In, s + 3);
+    s[7] = Staged{h_rgb8, px * 3, Dir::Out};
+    s[8] = Staged{h_f32, px * 3 * sizeof(float), Dir::Out};
+    s[9] = Staged{h_linear, px * 3 * sizeof(float), Dir::Out};
+    s[10] = Staged{h_var, px * 3 * sizeof(float), Dir::Out};
+    s[11] = Staged{h_history_prev, px * kHistoryBytes, Dir::In};
+    s[12] = Staged{h_history_next, px * kHistoryBytes, Dir::Out};
+    s[13] = Staged{h_prev_xy, px * 2 * sizeof(float), Dir::Out};
+    s[14] = Staged{h_weight, px * sizeof(float), Dir::Out};
+    return staged_call(s, [&](void* const* d) -> int {
+        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
+        const DsrtDenoiseGuides g = pointers_as<DsrtDenoiseGuides>(d + 3);
+        const int r = dsrt_denoise_temporal(ctx, desc, &acc, samples_done, (const uint32_t*)d[2], &g, prev_camera, (const float*)d[11], (float*)d[12], tp, dn, (uint8_t*)d[7],
+                                            (float*)d[8], (float*)d[9], (float*)d[10], (float*)d[13], (float*)d[14], nullptr);
+        if (r) return r;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return DSRT_OK;
+    });
+    });
+}
+
+// The convenience form: dsrt_render_denoised_to_host's three steps, with the histories and the previous camera kept by the context from call to call.
+int dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* dn, const DsrtTemporal* tp, int reset, uint8_t* h_rgb8, float* h_f32,
+                                          float* h_linear, float* h_var, float* h_prev_xy, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_denoised_temporal_to_host", [&]() -> int {
+    const char* fn = "dsrt_render_denoised_temporal_to_host";
+    if (!ctx || !desc) return accum_fail(fn, "null argument");
+    if (int rc = check_denoise_params(fn, dn)) return rc;
+    if (int rc = check_temporal_params(fn, tp)) return rc;
+    if (!h_rgb8 && !h_f32 && !h_linear && !h_var) return accum_fail(fn, "no output");
+    const int spp = desc->spp < 1 ? 1 : desc->spp;
+    if (int rc = check_sample_set(fn, ctx, desc, 0, spp, 1)) return rc;               // DSRT_ERR_NO_SCENE before an upload; rng_mode 1, no shards
+    if (spp < 2) return accum_fail(fn, "spp < 2 (the variance needs two samples)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * (size_t)desc->height;
+    const bool fresh = reset != 0 || !ctx->tp_valid || ctx->tp_width != desc->width || ctx->tp_height != desc->height;
+    DevBuf<unsigned long long> sum, sq;
+    DevBuf<float> normal, position, albedo, range;
+    int rc;
+    if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px))) return rc;
+    if (fresh) ctx->tp_valid = false;                                                 // (growing does not keep the contents: a sequence of another size is over either way)
+    for (DevBuf<float4>& h : ctx->tp_hist) if ((rc = h.grow(px * 4))) return rc;      // (only this call, which is synchronous, uses them: nothing in flight reads them)
+    HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
+    const DsrtAccum acc{(uint64_t*)sum.p, (uint64_t*)sq.p};
+    const DsrtDenoiseGuides guides{normal.p, position.p, albedo.p, range.p};
+    DsrtGBuffer gb;
+    std::memset(&gb, 0, sizeof gb);
+    gb.normal = normal.p; gb.position = position.p; gb.albedo = albedo.p; gb.range = range.p;
+    const GPUCamera camera = ctx->frame.camera, prev_camera = ctx->tp_camera;
+    const float* prev = fresh ? nullptr : (const float*)ctx->tp_hist[ctx->tp_cur].p;
+    float* next = (float*)ctx->tp_hist[fresh ? 0 : ctx->tp_cur ^ 1].p;
+    const Staged s[5] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_linear, px * 3 * sizeof(float), Dir::Out}, {h_var, px * 3 * sizeof(float), Dir::Out},
+                         {h_prev_xy, px * 2 * sizeof(float), Dir::Out}};
+    DsrtStats local;
+    rc = staged_call(s, [&](void* const* d) -> int {
+        int r;
+        if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &acc, nullptr, stats ? stats : &local))) return r;
+        if ((r = dsrt_render_gbuffer(ctx, desc, &gb, nullptr, nullptr))) return r;
+        if ((r = dsrt_denoise_temporal(ctx, desc, &acc, spp, nullptr, &guides, fresh ? nullptr : &prev_camera, prev, next, tp, dn, (uint8_t*)d[0], (float*)d[1], (float*)d[2],
+                                       (float*)d[3], (float*)d[4], nullptr, nullptr))) return r;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return DSRT_OK;
+    });
+    if (rc) return rc;
+    ctx->tp_cur = fresh ? 0 : ctx->tp_cur ^ 1;
+    ctx->tp_camera = camera; ctx->tp_width = desc->width; ctx->tp_height = desc->height;
+    ctx->tp_valid = true;
+    return DSRT_OK;
     });
 }
 

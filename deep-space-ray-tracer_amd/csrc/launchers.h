@@ -63,4 +63,16 @@ hipError_t launch_denoise_atrous(const DenoiseBuffers& b, int src, int W, int H,
 hipError_t launch_denoise_output(const DenoiseBuffers& b, int src, size_t n_pixels, float inv_gamma, bool device_libm, uint8_t* out_rgb8, float* out_f32, float* out_linear,
                                  float* out_var, hipStream_t stream);
 
+// temporal_kernel.hip (include/dsrt.h, TEMPORAL ACCUMULATION): between prepare and the first a-trous launch.  cl / vl are DenoiseBuffers' [0], blended in place;
+// prev (null = no previous frame) and next are the caller's histories, four float4 per pixel; cam = the previous GPUCamera's origin, lower_left_corner,
+// horizontal, vertical, u, v, w; counts / samples_done as prepare's.
+struct TemporalArgs {
+    float4* cl; float4* vl; const float4* nr; const float4* xf;
+    const float4* prev; float4* next; float* prev_xy; float* weight;
+    const uint32_t* counts; int samples_done, width, height;
+    float cam[21];
+    float alpha_min, normal_cos_min, plane_tol, min_support;
+};
+hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
+
 }  // namespace dsrt

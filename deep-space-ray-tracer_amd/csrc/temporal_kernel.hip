@@ -1,0 +1,121 @@
+// temporal_kernel.hip -- the temporal accumulation stage of include/dsrt.h (TEMPORAL ACCUMULATION): one kernel, one thread per pixel, between the denoiser's
+// prepare and its first a-trous launch (denoise_kernel.hip).
+//
+//   * It reads the records prepare wrote for its own pixel -- cl = {c, L(c)}, vl = {v, L(v)}, nr = {N, range}, xf = {X, F} -- projects X through the previous
+//     frame's camera, gathers the four history records around the projected point, blends, and writes cl / vl IN PLACE (each thread touches its own pixel's
+//     records only; the history it gathers from is another buffer) with L recomputed for the blended values, as every writer of cl / vl does.
+//   * A history record is 64 bytes = four dwordx4 loads at consecutive addresses; neighbouring pixels project to neighbouring points, so a wave's taps fall into
+//     neighbouring records.  `next` is written as four dwordx4 stores per lane.  Measured against one a-trous iteration: DESIGN.md section 4.
+//   * The occluder guard reads {c, m} and {X} of the up to sixteen records of the 4 x 4 block around the footprint: a surface in front of the pixel's tangent plane
+//     there voids the history, unless an accepted tap of weight >= 0.99 proves the point visible (include/dsrt.h).
+//   * The camera's eight dot products are per-launch constants, but they are part of the header's fp32 arithmetic: every lane computes them, by the operations
+//     written there, rather than have a host compiler's rounding of them enter the contract.
+//   * A tap index is formed only from fx in (-1, W) and fy in (-1, H) -- NaN fails that test -- so x0 is in [-1, W-1], and every tap is bounds-checked before its load.
+//
+// There is no reference counterpart (the reference reconstructs outside its renderer).
+// Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off, no fast-math, as denoise_kernel.hip.
+#include <cfloat>
+
+#include "launchers.h"
+
+namespace dsrt {
+
+namespace {
+__device__ __forceinline__ float t_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+__device__ __forceinline__ float t_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+}  // namespace
+
+__global__ __launch_bounds__(256) void dsrt_temporal_kernel(const TemporalArgs a) {
+    const int x = (int)blockIdx.x * 16 + (int)(threadIdx.x & 15u), y = (int)blockIdx.y * 16 + (int)(threadIdx.x >> 4);
+    const int W = a.width, H = a.height;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * (size_t)W + (size_t)x;
+    const float4 cp = a.cl[p], vp = a.vl[p], np = a.nr[p], xp = a.xf[p];
+    const bool filterable = xp.w != 0.0f;
+    const float nf = (float)(a.counts ? a.counts[p] : (uint32_t)a.samples_done);
+    const float qnan = __uint_as_float(0x7FC00000u);
+
+    // ---- the projection into the previous frame ----
+    float fx = qnan, fy = qnan;
+    bool projected = false;
+    if (a.prev && np.w <= FLT_MAX) {
+        const float* C = a.cam;                                              // origin, lower_left_corner, horizontal, vertical, u, v, w
+        const float Dx = xp.x - C[0], Dy = xp.y - C[1], Dz = xp.z - C[2];
+        const float ex = C[3] - C[0], ey = C[4] - C[1], ez = C[5] - C[2];
+        const float da = t_dot3(Dx, Dy, Dz, C[12], C[13], C[14]), db = t_dot3(Dx, Dy, Dz, C[15], C[16], C[17]), dc = t_dot3(Dx, Dy, Dz, C[18], C[19], C[20]);
+        const float eu = t_dot3(ex, ey, ez, C[12], C[13], C[14]), ev = t_dot3(ex, ey, ez, C[15], C[16], C[17]), ew = t_dot3(ex, ey, ez, C[18], C[19], C[20]);
+        const float hu = t_dot3(C[6], C[7], C[8], C[12], C[13], C[14]), vv = t_dot3(C[9], C[10], C[11], C[15], C[16], C[17]);
+        const float k = ew / dc;
+        if (k > 0.0f) {
+            const float s = (da * k - eu) / hu, t = (db * k - ev) / vv;
+            const float px = s * (float)(W - 1) - 0.5f, py = (float)(H - 1) - (t * (float)(H - 1) - 0.5f);
+            if (px > -1.0f && px < (float)W && py > -1.0f && py < (float)H) { fx = px; fy = py; projected = true; }
+        }
+    }
+
+    // ---- the four taps ----
+    float c0 = cp.x, c1 = cp.y, c2 = cp.z, v0 = vp.x, v1 = vp.y, v2 = vp.z;
+    float m = filterable ? nf : 0.0f;
+    if (projected && filterable) {
+        const float flx = floorf(fx), fly = floorf(fy);
+        const int x0 = (int)flx, y0 = (int)fly;                              // in [-1, W-1] x [-1, H-1]
+        const float wx = fx - flx, wy = fy - fly, ox = 1.0f - wx, oy = 1.0f - wy;
+        const float bw[4] = {ox * oy, wx * oy, ox * wy, wx * wy};
+        const float tol = a.plane_tol * np.w;
+        // the occluder guard: a record of the 4 x 4 block around the footprint that holds a surface in FRONT of this pixel's tangent plane voids the history
+        bool guarded = false;
+        for (int gy = y0 - 1; gy <= y0 + 2; ++gy) {
+            if (gy < 0 || gy >= H) continue;
+            for (int gx = x0 - 1; gx <= x0 + 2; ++gx) {
+                if (gx < 0 || gx >= W) continue;
+                const float4* rec = a.prev + ((size_t)gy * (size_t)W + (size_t)gx) * 4;
+                const float4 cq = rec[0], xq = rec[3];
+                guarded |= cq.w > 0.0f && t_dot3(np.x, np.y, np.z, xq.x - xp.x, xq.y - xp.y, xq.z - xp.z) > tol;
+            }
+        }
+        float sw = 0.0f, sc0 = 0.0f, sc1 = 0.0f, sc2 = 0.0f, sv0 = 0.0f, sv1 = 0.0f, sv2 = 0.0f, sm = 0.0f;
+        bool seen = false;                                                   // an accepted tap whose centre ray all but coincides with the ray to X: proof of visibility
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const float4* rec = a.prev + ((size_t)qy * (size_t)W + (size_t)qx) * 4;
+            const float4 cq = rec[0], vq = rec[1], nq = rec[2], xq = rec[3];
+            if (!(cq.w > 0.0f)) continue;
+            if (!(t_dot3(np.x, np.y, np.z, nq.x, nq.y, nq.z) >= a.normal_cos_min)) continue;
+            if (!(fabsf(t_dot3(np.x, np.y, np.z, xq.x - xp.x, xq.y - xp.y, xq.z - xp.z)) <= tol)) continue;
+            const float b = bw[k];
+            seen |= b >= 0.99f;
+            sw += b;
+            sc0 += b * cq.x; sc1 += b * cq.y; sc2 += b * cq.z;
+            sv0 += b * vq.x; sv1 += b * vq.y; sv2 += b * vq.z;
+            sm += b * cq.w;
+        }
+        if (sw >= a.min_support && (seen || !guarded)) {
+            const float mh = sm / sw;
+            const float alpha = fmaxf(nf / (nf + mh), a.alpha_min), beta = 1.0f - alpha;
+            const float b2 = beta * beta, a2 = alpha * alpha;
+            c0 = beta * (sc0 / sw) + alpha * cp.x; c1 = beta * (sc1 / sw) + alpha * cp.y; c2 = beta * (sc2 / sw) + alpha * cp.z;
+            v0 = b2 * (sv0 / sw) + a2 * vp.x; v1 = b2 * (sv1 / sw) + a2 * vp.y; v2 = b2 * (sv2 / sw) + a2 * vp.z;
+            m = nf / alpha;
+            a.cl[p] = make_float4(c0, c1, c2, t_lum(c0, c1, c2));
+            a.vl[p] = make_float4(v0, v1, v2, t_lum(v0, v1, v2));
+        }
+    }
+
+    float4* out = a.next + p * 4;
+    out[0] = make_float4(c0, c1, c2, m);
+    out[1] = make_float4(v0, v1, v2, 0.0f);
+    out[2] = make_float4(np.x, np.y, np.z, 0.0f);
+    out[3] = make_float4(xp.x, xp.y, xp.z, 0.0f);
+    if (a.prev_xy) { a.prev_xy[p * 2] = fx; a.prev_xy[p * 2 + 1] = fy; }      // (the caller's buffer is 4-byte aligned: two stores)
+    if (a.weight) a.weight[p] = m;
+}
+
+hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.width + 15) / 16), (unsigned)((a.height + 15) / 16));
+    hipLaunchKernelGGL(dsrt_temporal_kernel, grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace dsrt

@@ -159,6 +159,7 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_ADAPTIVE_STATS: return sizeof(DsrtAdaptiveStats);
         case DSRT_SIZEOF_DENOISE_GUIDES: return sizeof(DsrtDenoiseGuides);
         case DSRT_SIZEOF_DENOISE: return sizeof(DsrtDenoise);
+        case DSRT_SIZEOF_TEMPORAL: return sizeof(DsrtTemporal);
         default: return 0;
     }
 }

@@ -22,6 +22,11 @@
 //     library's default parameters, ITER iterations if given) -- the reference's reconstruction step runs outside its renderer (scripts/upsample.py) -- and
 //     writes <frame> denoised and <frame>_raw undenoised, byte for byte the frame without the flag (with --variance also <frame>_var.pfm, the
 //     filtered image's propagated variance).
+//   * with --denoise: --temporal carries every frame's accumulated mean and variance on to the next, reprojected through the previous camera (include/dsrt.h,
+//     TEMPORAL ACCUMULATION: dsrt_render_denoised_temporal_to_host, the library's default parameters).  Frames are rendered in pose order, a skipped frame leaves the
+//     history as it is, and frame i (its index in the pose file) is rendered with seed 1337 + i: the blend takes the frames' noise as independent, which one seed for
+//     all frames would not give.  <frame>_raw is that frame's own samples, undenoised.  --flow also writes <frame>_flow.pfm: per pixel where its surface point was
+//     in the previous frame, as (fx - x, fy - y, 0) in pixels (NaN where it was not in view, and in the first frame) -- optical-flow ground truth.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,7 +56,7 @@ int main(int argc, char** argv) {
     int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0, passes = 0;
     int adaptive_passes = 8, adaptive_min = 2;
     float adaptive_tol = 0.0f, adaptive_floor = 0.0f;
-    bool adaptive = false, adaptive_detail = false, denoise = false;
+    bool adaptive = false, adaptive_detail = false, denoise = false, temporal = false, flow = false;
     int denoise_iterations = -1;                                    // -1: the library's default
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     for (int i = 1; i < argc; ++i) {
@@ -87,8 +92,10 @@ int main(int argc, char** argv) {
             denoise = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_iterations = std::atoi(argv[++i]);
         }
+        else if (a == "--temporal") temporal = true;                // with --denoise: reprojected frame history (include/dsrt.h, TEMPORAL ACCUMULATION)
+        else if (a == "--flow") flow = true;                        // with --temporal: <frame>_flow.pfm, every pixel's displacement from the previous frame
         else if (a == "--upscale") std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (adaptive_detail && !adaptive) { std::fprintf(stderr, "dsrt_render: --adaptive-passes, --adaptive-min-passes and --adaptive-floor need --adaptive TOL\n"); return 2; }
@@ -101,6 +108,8 @@ int main(int argc, char** argv) {
     if (denoise && (passes != 0 || adaptive || gbuffer)) { std::fprintf(stderr, "dsrt_render: --denoise does not combine with --passes / --adaptive / --gbuffer\n"); return 2; }
     if (denoise && denoise_iterations > 6) { std::fprintf(stderr, "dsrt_render: --denoise ITER must be between 0 and 6\n"); return 2; }
     if (denoise && spp < 2) { std::fprintf(stderr, "dsrt_render: --denoise needs --spp 2 or more\n"); return 2; }
+    if (temporal && !denoise) { std::fprintf(stderr, "dsrt_render: --temporal needs --denoise\n"); return 2; }
+    if (flow && !temporal) { std::fprintf(stderr, "dsrt_render: --flow needs --temporal\n"); return 2; }
     if ((passes != 0 || variance) && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --passes and --variance need --rng-mode 1 (or --fast)\n"); return 2; }
     if (passes < 0 || passes > std::max(spp, 1)) { std::fprintf(stderr, "dsrt_render: --passes must be between 1 and --spp\n"); return 2; }
     if (variance && spp < 2) { std::fprintf(stderr, "dsrt_render: --variance needs --spp 2 or more\n"); return 2; }
@@ -196,6 +205,47 @@ int main(int argc, char** argv) {
                         100.0 * (double)st.samples_total / ((double)px * spp), spp);
             for (int p = 0; p < st.passes_run; ++p) std::printf(" %u", st.active[p]);
             std::printf("\nSaved %s, %s_spp.pfm%s\n", path.c_str(), base.c_str(), variance ? " and _var.pfm" : "");
+        }
+        dsrt_ctx_destroy(ctx);
+        dsrt_host_scene_destroy(hs);
+        std::printf("Done.\n");
+        return 0;
+    }
+    if (denoise && temporal) {
+        // Each frame in pose order through the convenience form, the history kept by the context; the raw image is the same samples in one launch.
+        const size_t px = (size_t)width * height;
+        std::vector<uint8_t> raw(image_bytes), img(image_bytes);
+        std::vector<float> var(variance ? image_bytes : 0), prev_xy(flow ? px * 2 : 0), flow_px(flow ? px * 3 : 0);
+        DsrtDenoise dn;
+        dsrt_denoise_defaults(&dn);
+        if (denoise_iterations >= 0) dn.iterations = denoise_iterations;
+        DsrtTemporal tp;
+        dsrt_temporal_defaults(&tp);
+        const std::string ext = png ? ".png" : ".ppm";
+        auto write = [&](const std::string& path, const std::vector<uint8_t>& image) {
+            return (png ? dsrt_write_png(path.c_str(), image.data(), width, height) : dsrt_write_ppm(path.c_str(), image.data(), width, height)) == DSRT_OK;
+        };
+        for (size_t q = 0; q < ids.size(); ++q) {
+            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
+            d.seed = 1337 + (uint64_t)ids[q];
+            if (dsrt_render_denoised_temporal_to_host(ctx, &d, &dn, &tp, q == 0 ? 1 : 0, img.data(), nullptr, nullptr, variance ? var.data() : nullptr,
+                                                      flow ? prev_xy.data() : nullptr, nullptr) != DSRT_OK) return fail("rendering with temporal accumulation");
+            if (dsrt_render_to_host(ctx, &d, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("rendering the raw image");
+            char stem[64];
+            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
+            const std::string base = out_dir + stem;
+            if (!write(base + ext, img) || !write(base + "_raw" + ext, raw)) return fail("writing the frame");
+            if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
+            if (flow) {
+                for (size_t i = 0; i < px; ++i) {
+                    flow_px[3 * i + 0] = prev_xy[2 * i + 0] - (float)(i % (size_t)width);
+                    flow_px[3 * i + 1] = prev_xy[2 * i + 1] - (float)(i / (size_t)width);
+                    flow_px[3 * i + 2] = 0.0f;
+                }
+                if (dsrt_write_pfm((base + "_flow.pfm").c_str(), flow_px.data(), width, height, 3) != DSRT_OK) return fail("writing the flow");
+            }
+            std::printf("denoise: %d iterations, temporal, seed %llu\nSaved %s, %s_raw%s%s%s\n", dn.iterations, (unsigned long long)d.seed, (base + ext).c_str(), base.c_str(),
+                        ext.c_str(), variance ? ", _var.pfm" : "", flow ? ", _flow.pfm" : "");
         }
         dsrt_ctx_destroy(ctx);
         dsrt_host_scene_destroy(hs);
