@@ -303,6 +303,29 @@ def stats_dict(st):
     return {name: getattr(st, name) for name, _ in DsrtStats._fields_}
 
 
+def _tensor_ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _array_ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+_OUTPUTS = {"rgb8": (np.uint8, (3,)), "f32": (np.float32, (3,)), "linear": (np.float32, (3,)), "var": (np.float32, (3,)), "prev_xy": (np.float32, (2,)),
+            "weight": (np.float32, ())}
+
+
+def _outputs(desc, wants, device=None):
+    """The outputs of a sample-set frame that `wants` = {name of _OUTPUTS: asked for?} names, in its order, None for one not asked for: torch tensors on `device`
+    (uninitialised), or zeroed numpy arrays where there is none."""
+    out = []
+    for name, want in wants.items():
+        dt, tail = _OUTPUTS[name]
+        shape = (desc.height, desc.width) + tail
+        out.append(None if not want else np.zeros(shape, dt) if device is None else _torch.empty(shape, dtype=getattr(_torch, np.dtype(dt).name), device=device))
+    return tuple(out)
+
+
 class Context:
     """One GPU: resident scene in traversal layout + render launches (DsrtContext)."""
 
@@ -488,20 +511,33 @@ class Context:
         return (out, st) if want_stats else out
 
     # ---- sample sets (include/dsrt.h, dsrt_render_accumulate): rng_mode 1 sums in caller-owned int64 device tensors ----
-    def _sum_tensor(self, desc, x, what, required=True):
+    def _device_tensor(self, x, dtype, numel, what, required=True):
+        """`x`, if it is a contiguous torch tensor of `dtype` on this context's device with `numel` elements -- numel: (the count, the message's words for it) --
+        or None for an optional one that is not given."""
         if x is None:
             if required:
                 raise ValueError(f"{what} is required")
             return None
         if _torch is None or not isinstance(x, _torch.Tensor):
             raise TypeError(f"{what} must be a torch tensor")
-        if x.dtype != _torch.int64:
-            raise TypeError(f"{what} must be int64, not {x.dtype}")
+        if x.dtype != dtype:
+            raise TypeError(f"{what} must be {'int64' if dtype == _torch.int64 else dtype}, not {x.dtype}")
         if x.device.type != "cuda" or x.device.index != self.device:
             raise ValueError(f"{what} is on {x.device}, the context is on cuda:{self.device}")
-        if not x.is_contiguous() or x.numel() != desc.width * desc.height * 3:
-            raise ValueError(f"{what} must be contiguous with width*height*3 = {desc.width * desc.height * 3} elements")
+        if not x.is_contiguous() or x.numel() != numel[0]:
+            raise ValueError(f"{what} must be contiguous with {numel[1]} elements")
         return x
+
+    def _accum(self, desc, sums, sum_sq, sq_required=True):
+        """DsrtAccum of `sums` and `sum_sq`, int64 device tensors of width*height*3 elements (sum_sq may be None unless sq_required)."""
+        n = desc.width * desc.height * 3
+        numel = (n, f"width*height*3 = {n}")
+        return DsrtAccum(_tensor_ptr(self._device_tensor(sums, _torch.int64, numel, "sums")),
+                         _tensor_ptr(self._device_tensor(sum_sq, _torch.int64, numel, "sum_sq", sq_required)))
+
+    def _pixel_tensor(self, desc, x, dtype, what, required=True):
+        n = desc.width * desc.height
+        return self._device_tensor(x, dtype, (n, f"width*height = {n}"), what, required)
 
     def _raw_stream(self, stream):
         if isinstance(stream, _torch.cuda.Stream):
@@ -512,9 +548,7 @@ class Context:
         """dsrt_render_accumulate: ADD the sums of samples {first + j*stride : 0 <= j < count} of every pixel (a frame planned at desc.spp, rng_mode 1)
         to `sums` (and the squared samples to `sum_sq`, if given): int64 device tensors of width*height*3 elements, zeroed by the caller once.  On
         `stream` (a torch.cuda.Stream or a raw hipStream_t; default: torch's current stream); with want_stats the call synchronises and returns DsrtStats."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=False)
-        acc = DsrtAccum(C.c_void_p(sums.data_ptr()), C.c_void_p(sum_sq.data_ptr()) if sum_sq is not None else None)
+        acc = self._accum(desc, sums, sum_sq, sq_required=False)
         st = DsrtStats() if want_stats else None
         _check(lib.dsrt_render_accumulate(self._h, C.byref(desc), int(first), int(count), int(stride), C.byref(acc), C.c_void_p(self._raw_stream(stream)),
                                           C.byref(st) if st is not None else None), "dsrt_render_accumulate")
@@ -523,96 +557,61 @@ class Context:
     def resolve_accumulated(self, desc, sums, samples_done, sum_sq=None, want_rgb8=True, want_f32=False, want_var=False, stream=None):
         """dsrt_resolve_accumulated: the image of `sums` after `samples_done` samples per pixel.  Returns (rgb8, f32, var) as device tensors of shape
         (height, width, 3) -- uint8, float32, float32 (the variance of the mean; needs sum_sq) -- None for what was not asked for."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=want_var)
-        shape, dev = (desc.height, desc.width, 3), sums.device
-        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
-        f32 = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_f32 else None
-        var = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_var else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
-        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
-        _check(lib.dsrt_resolve_accumulated(self._h, C.byref(desc), C.byref(acc), int(samples_done), ptr(rgb), ptr(f32), ptr(var),
-                                            C.c_void_p(self._raw_stream(stream))), "dsrt_resolve_accumulated")
-        return rgb, f32, var
+        acc = self._accum(desc, sums, sum_sq, sq_required=want_var)
+        out = _outputs(desc, dict(rgb8=want_rgb8, f32=want_f32, var=want_var), sums.device)
+        _check(lib.dsrt_resolve_accumulated(self._h, C.byref(desc), C.byref(acc), int(samples_done), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream))),
+               "dsrt_resolve_accumulated")
+        return out
 
     # ---- adaptive sampling (include/dsrt.h, ADAPTIVE SAMPLING): masked sample sets, the convergence test, the per-pixel resolve, the driver ----
-    def _pixel_tensor(self, desc, x, dtype, what, required=True):
-        if x is None:
-            if required:
-                raise ValueError(f"{what} is required")
-            return None
-        if _torch is None or not isinstance(x, _torch.Tensor):
-            raise TypeError(f"{what} must be a torch tensor")
-        if x.dtype != dtype:
-            raise TypeError(f"{what} must be {dtype}, not {x.dtype}")
-        if x.device.type != "cuda" or x.device.index != self.device:
-            raise ValueError(f"{what} is on {x.device}, the context is on cuda:{self.device}")
-        if not x.is_contiguous() or x.numel() != desc.width * desc.height:
-            raise ValueError(f"{what} must be contiguous with width*height = {desc.width * desc.height} elements")
-        return x
-
     def render_accumulate_masked(self, desc, first, count, stride=1, sums=None, sum_sq=None, mask=None, n=None, stream=None, want_stats=False):
         """dsrt_render_accumulate_masked: render_accumulate for the pixels whose byte of `mask` (uint8 device tensor, width*height, image order) is nonzero;
         `n` (optional int32 device tensor, width*height: the pixels' sample counts) gets `count` added where the mask is set."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=False)
+        acc = self._accum(desc, sums, sum_sq, sq_required=False)
         mask = self._pixel_tensor(desc, mask, _torch.uint8, "mask")
         n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
-        acc = DsrtAccum(C.c_void_p(sums.data_ptr()), C.c_void_p(sum_sq.data_ptr()) if sum_sq is not None else None)
         st = DsrtStats() if want_stats else None
-        _check(lib.dsrt_render_accumulate_masked(self._h, C.byref(desc), int(first), int(count), int(stride), C.byref(acc), C.c_void_p(mask.data_ptr()),
-                                                 C.c_void_p(n.data_ptr()) if n is not None else None, C.c_void_p(self._raw_stream(stream)),
-                                                 C.byref(st) if st is not None else None), "dsrt_render_accumulate_masked")
+        _check(lib.dsrt_render_accumulate_masked(self._h, C.byref(desc), int(first), int(count), int(stride), C.byref(acc), _tensor_ptr(mask), _tensor_ptr(n),
+                                                 C.c_void_p(self._raw_stream(stream)), C.byref(st) if st is not None else None), "dsrt_render_accumulate_masked")
         return st
 
     def select_unconverged(self, desc, sums, sum_sq, n, rel_tol, floor=0.0, n_min=0, n_max=0xFFFFFFFF, mask=None, want_active=True, stream=None):
         """dsrt_select_unconverged: (mask, active) -- the uint8 device tensor (height, width) of the pixels that still need samples (written into `mask` if one is
         given) and how many they are (None without want_active: then the call does not synchronise)."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq")
+        acc = self._accum(desc, sums, sum_sq)
         n = self._pixel_tensor(desc, n, _torch.int32, "n")
         mask = _torch.empty((desc.height, desc.width), dtype=_torch.uint8, device=sums.device) if mask is None else self._pixel_tensor(desc, mask, _torch.uint8, "mask")
-        acc = DsrtAccum(C.c_void_p(sums.data_ptr()), C.c_void_p(sum_sq.data_ptr()))
         active = C.c_uint32(0)
-        _check(lib.dsrt_select_unconverged(self._h, C.byref(desc), C.byref(acc), C.c_void_p(n.data_ptr()), float(rel_tol), float(floor), int(n_min), int(n_max),
-                                           C.c_void_p(mask.data_ptr()), C.byref(active) if want_active else None, C.c_void_p(self._raw_stream(stream))),
+        _check(lib.dsrt_select_unconverged(self._h, C.byref(desc), C.byref(acc), _tensor_ptr(n), float(rel_tol), float(floor), int(n_min), int(n_max),
+                                           _tensor_ptr(mask), C.byref(active) if want_active else None, C.c_void_p(self._raw_stream(stream))),
                "dsrt_select_unconverged")
         return mask, (active.value if want_active else None)
 
     def resolve_accumulated_counts(self, desc, sums, n, sum_sq=None, want_rgb8=True, want_f32=False, want_var=False, stream=None):
         """dsrt_resolve_accumulated_counts: resolve_accumulated with every pixel's own sample count `n` (int32 device tensor) in place of samples_done."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq", required=want_var)
+        acc = self._accum(desc, sums, sum_sq, sq_required=want_var)
         n = self._pixel_tensor(desc, n, _torch.int32, "n")
-        shape, dev = (desc.height, desc.width, 3), sums.device
-        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
-        f32 = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_f32 else None
-        var = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_var else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
-        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
-        _check(lib.dsrt_resolve_accumulated_counts(self._h, C.byref(desc), C.byref(acc), ptr(n), ptr(rgb), ptr(f32), ptr(var),
-                                                   C.c_void_p(self._raw_stream(stream))), "dsrt_resolve_accumulated_counts")
-        return rgb, f32, var
+        out = _outputs(desc, dict(rgb8=want_rgb8, f32=want_f32, var=want_var), sums.device)
+        _check(lib.dsrt_resolve_accumulated_counts(self._h, C.byref(desc), C.byref(acc), _tensor_ptr(n), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream))),
+               "dsrt_resolve_accumulated_counts")
+        return out
 
     def render_adaptive(self, desc, rel_tol, passes=8, min_passes=2, floor=0.0, want_rgb8=True, want_f32=False, want_var=False, stream=None):
         """dsrt_render_adaptive: the frame in up to `passes` interleaved passes, each pass from min_passes on over the pixels that have not converged to rel_tol.
         Returns (acc, (rgb8, f32, var), stats): the Accumulator holding the sums and the per-pixel counts `acc.n`, the images asked for, and a dict with
         passes_run, samples_total and active (pixels rendered by each pass that ran)."""
         acc = Accumulator(self, desc, moments=True, counts=True)
-        shape, dev = (desc.height, desc.width, 3), acc.sum.device
-        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
-        f32 = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_f32 else None
-        var = _torch.empty(shape, dtype=_torch.float32, device=dev) if want_var else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
-        a = DsrtAccum(ptr(acc.sum), ptr(acc.sum_sq))
+        out = _outputs(desc, dict(rgb8=want_rgb8, f32=want_f32, var=want_var), acc.sum.device)
+        a = DsrtAccum(_tensor_ptr(acc.sum), _tensor_ptr(acc.sum_sq))
         ad = capi.DsrtAdaptive(int(passes), int(min_passes), float(rel_tol), float(floor))
         st = capi.DsrtAdaptiveStats()
-        _check(lib.dsrt_render_adaptive(self._h, C.byref(desc), C.byref(ad), C.byref(a), ptr(acc.n), ptr(rgb), ptr(f32), ptr(var),
-                                        C.c_void_p(self._raw_stream(stream)), C.byref(st)), "dsrt_render_adaptive")
+        _check(lib.dsrt_render_adaptive(self._h, C.byref(desc), C.byref(ad), C.byref(a), _tensor_ptr(acc.n), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream)),
+                                        C.byref(st)), "dsrt_render_adaptive")
         acc.samples_done = None                    # the counts are per pixel now: acc.resolve_counts(), not acc.resolve()
-        return acc, (rgb, f32, var), {"passes_run": st.passes_run, "samples_total": st.samples_total, "active": list(st.active[:st.passes_run])}
+        return acc, out, {"passes_run": st.passes_run, "samples_total": st.samples_total, "active": list(st.active[:st.passes_run])}
 
-    # ---- the denoiser (include/dsrt.h, DENOISER): the variance-guided a-trous filter over sums and G-buffer guides ----
+    # ---- the denoiser (include/dsrt.h, DENOISER): the variance-guided a-trous filter over sums and G-buffer guides; with a `temporal` part, TEMPORAL ACCUMULATION:
+    # the same with reprojected frame history in front of its iterations ----
     def _guide_tensors(self, desc, guides):
         if set(guides) != set(DENOISE_GUIDES):
             raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
@@ -621,145 +620,115 @@ class Context:
             x, comps = guides[k], capi.GBUFFER_CHANNELS[k][1]
             if _torch is None or not isinstance(x, _torch.Tensor) or x.dtype != _torch.float32:
                 raise TypeError(f"guide {k} must be a float32 torch tensor")
-            if x.device.type != "cuda" or x.device.index != self.device:
-                raise ValueError(f"guide {k} is on {x.device}, the context is on cuda:{self.device}")
-            if not x.is_contiguous() or x.numel() != desc.width * desc.height * comps:
-                raise ValueError(f"guide {k} must be contiguous with width*height*{comps} elements")
-            out[k] = x
+            out[k] = self._device_tensor(x, _torch.float32, (desc.width * desc.height * comps, f"width*height*{comps}"), f"guide {k}")
         return out
+
+    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None):
+        """denoise_accumulated and, with temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None), denoise_temporal: the outputs `wants` names."""
+        acc = self._accum(desc, sums, sum_sq)
+        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
+        if n is None and samples_done is None:
+            raise ValueError(f"{what} needs samples_done or per-pixel counts n")
+        gd = capi.DsrtDenoiseGuides(**{k: _tensor_ptr(x) for k, x in self._guide_tensors(desc, guides).items()})
+        if temporal is not None:
+            prev_camera, history_prev, history_next, tp = temporal
+            for name, h in (("history_prev", history_prev), ("history_next", history_next)):
+                if h is None:
+                    continue
+                if not isinstance(h, _torch.Tensor) or h.dtype != _torch.float32 or h.device.type != "cuda" or h.device.index != self.device:
+                    raise TypeError(f"{name} must be a float32 torch tensor on cuda:{self.device}")
+                self._device_tensor(h, _torch.float32, (desc.width * desc.height * capi.HISTORY_FLOATS, f"width*height*{capi.HISTORY_FLOATS}"), name)
+            tp = temporal_defaults() if tp is None else tp
+        params = denoise_defaults() if params is None else params
+        out = _outputs(desc, wants, sums.device)
+        head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), _tensor_ptr(n), C.byref(gd))
+        tail = (C.byref(params), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream)))
+        if temporal is None:
+            _check(lib.dsrt_denoise_accumulated(*head, *tail), "dsrt_denoise_accumulated")
+        else:
+            _check(lib.dsrt_denoise_temporal(*head, C.byref(prev_camera) if prev_camera is not None else None, _tensor_ptr(history_prev), _tensor_ptr(history_next),
+                                             C.byref(tp), *tail), "dsrt_denoise_temporal")
+        return tuple(out)
+
+    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None):
+        """The same from numpy arrays into numpy arrays (temporal: (prev_camera, history_prev or None, DsrtTemporal or None); the next history is returned last)."""
+        H, W = desc.height, desc.width
+        S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
+        S2 = np.ascontiguousarray(sum_sq, np.uint64).reshape(H, W, 3)
+        cnt = np.ascontiguousarray(n, np.uint32).reshape(H, W) if n is not None else None
+        if set(guides) != set(DENOISE_GUIDES):
+            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
+        g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
+        acc = DsrtAccum(_array_ptr(S), _array_ptr(S2))
+        gd = capi.DsrtDenoiseGuides(**{k: _array_ptr(x) for k, x in g.items()})
+        if temporal is not None:
+            prev_camera, history_prev, tp = temporal
+            prev = None
+            if history_prev is not None:
+                prev = aligned_zeros(H * W * capi.HISTORY_FLOATS)
+                prev[:] = np.asarray(history_prev, np.float32).reshape(-1)
+            nxt = aligned_zeros(H * W * capi.HISTORY_FLOATS)
+            tp = temporal_defaults() if tp is None else tp
+        params = denoise_defaults() if params is None else params
+        out = _outputs(desc, wants)
+        head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), _array_ptr(cnt), C.byref(gd))
+        tail = (C.byref(params), *map(_array_ptr, out))
+        if temporal is None:
+            _check(lib.dsrt_denoise_accumulated_to_host(*head, *tail), "dsrt_denoise_accumulated_to_host")
+            return tuple(out)
+        _check(lib.dsrt_denoise_temporal_to_host(*head, C.byref(prev_camera) if prev_camera is not None else None, _array_ptr(prev), _array_ptr(nxt), C.byref(tp), *tail),
+               "dsrt_denoise_temporal_to_host")
+        return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
 
     def denoise_accumulated(self, desc, sums, sum_sq, guides, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
                             want_var=False, stream=None):
         """dsrt_denoise_accumulated: the filtered image of `sums` / `sum_sq` (int64 device tensors, as render_accumulate's) after `samples_done` samples per pixel
         or the per-pixel counts `n` (int32 device tensor), guided by `guides` = {"normal", "position", "albedo", "range": float32 device tensors, G-buffer
         channels}.  params: a DsrtDenoise (denoise_defaults()).  Returns (rgb8, f32, linear, var) device tensors of shape (height, width, 3), None where not asked for."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq")
-        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
-        if n is None and samples_done is None:
-            raise ValueError("denoise_accumulated needs samples_done or per-pixel counts n")
-        g = self._guide_tensors(desc, guides)
-        params = denoise_defaults() if params is None else params
-        shape, dev = (desc.height, desc.width, 3), sums.device
-        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
-        f32, lin, var = (_torch.empty(shape, dtype=_torch.float32, device=dev) if w else None for w in (want_f32, want_linear, want_var))
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
-        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
-        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
-        _check(lib.dsrt_denoise_accumulated(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(n), C.byref(gd), C.byref(params), ptr(rgb), ptr(f32),
-                                            ptr(lin), ptr(var), C.c_void_p(self._raw_stream(stream))), "dsrt_denoise_accumulated")
-        return rgb, f32, lin, var
+        return self._denoise("denoise_accumulated", desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var), stream)
 
     def denoise_accumulated_to_host(self, desc, sums, sum_sq, guides, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
                                     want_var=False):
         """dsrt_denoise_accumulated_to_host: the same from numpy arrays (uint64 sums (H, W, 3), uint32 counts (H, W), float32 guides) into numpy arrays."""
-        H, W = desc.height, desc.width
-        S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
-        S2 = np.ascontiguousarray(sum_sq, np.uint64).reshape(H, W, 3)
-        cnt = np.ascontiguousarray(n, np.uint32).reshape(H, W) if n is not None else None
-        if set(guides) != set(DENOISE_GUIDES):
-            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
-        g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
-        params = denoise_defaults() if params is None else params
-        rgb = np.zeros((H, W, 3), np.uint8) if want_rgb8 else None
-        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
-        acc = DsrtAccum(ptr(S), ptr(S2))
-        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
-        _check(lib.dsrt_denoise_accumulated_to_host(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(cnt), C.byref(gd), C.byref(params), ptr(rgb),
-                                                    ptr(f32), ptr(lin), ptr(var)), "dsrt_denoise_accumulated_to_host")
-        return rgb, f32, lin, var
+        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var))
 
     def render_denoised_to_host(self, desc, params=None, want_f32=False, want_linear=True, want_var=False):
         """dsrt_render_denoised_to_host: desc.spp samples, the G-buffer of the current camera and the filter, into numpy arrays: (rgb8, f32, linear, var, DsrtStats)."""
-        H, W = desc.height, desc.width
         params = denoise_defaults() if params is None else params
-        rgb = np.zeros((H, W, 3), np.uint8)
-        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
+        out = _outputs(desc, dict(rgb8=True, f32=want_f32, linear=want_linear, var=want_var))
         st = DsrtStats()
-        _check(lib.dsrt_render_denoised_to_host(self._h, C.byref(desc), C.byref(params), ptr(rgb), ptr(f32), ptr(lin), ptr(var), C.byref(st)), "dsrt_render_denoised_to_host")
-        return rgb, f32, lin, var, st
+        _check(lib.dsrt_render_denoised_to_host(self._h, C.byref(desc), C.byref(params), *map(_array_ptr, out), C.byref(st)), "dsrt_render_denoised_to_host")
+        return (*out, st)
 
-    # ---- temporal accumulation (include/dsrt.h, TEMPORAL ACCUMULATION): the denoiser with reprojected frame history in front of its iterations ----
     def denoise_temporal(self, desc, sums, sum_sq, guides, history_next, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None, params=None,
                          want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False, want_weight=False, stream=None):
         """dsrt_denoise_temporal: denoise_accumulated with the history stage.  history_prev / history_next: float32 device tensors of width*height*16 elements
         (the caller ping-pongs two); prev_camera: the GPUCamera history_prev was written under -- both None for the first frame of a sequence.  temporal: a
         DsrtTemporal (temporal_defaults()).  Returns (rgb8, f32, linear, var, prev_xy, weight) device tensors -- prev_xy (height, width, 2), weight (height, width) --
         None where not asked for."""
-        sums = self._sum_tensor(desc, sums, "sums")
-        sum_sq = self._sum_tensor(desc, sum_sq, "sum_sq")
-        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
-        if n is None and samples_done is None:
-            raise ValueError("denoise_temporal needs samples_done or per-pixel counts n")
-        g = self._guide_tensors(desc, guides)
-        for what, h in (("history_prev", history_prev), ("history_next", history_next)):
-            if h is None:
-                continue
-            if not isinstance(h, _torch.Tensor) or h.dtype != _torch.float32 or h.device.type != "cuda" or h.device.index != self.device:
-                raise TypeError(f"{what} must be a float32 torch tensor on cuda:{self.device}")
-            if not h.is_contiguous() or h.numel() != desc.width * desc.height * capi.HISTORY_FLOATS:
-                raise ValueError(f"{what} must be contiguous with width*height*{capi.HISTORY_FLOATS} elements")
-        params = denoise_defaults() if params is None else params
-        temporal = temporal_defaults() if temporal is None else temporal
-        shape, dev = (desc.height, desc.width, 3), sums.device
-        rgb = _torch.empty(shape, dtype=_torch.uint8, device=dev) if want_rgb8 else None
-        f32, lin, var = (_torch.empty(shape, dtype=_torch.float32, device=dev) if w else None for w in (want_f32, want_linear, want_var))
-        pxy = _torch.empty((desc.height, desc.width, 2), dtype=_torch.float32, device=dev) if want_prev_xy else None
-        wgt = _torch.empty((desc.height, desc.width), dtype=_torch.float32, device=dev) if want_weight else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
-        acc = DsrtAccum(ptr(sums), ptr(sum_sq))
-        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
-        _check(lib.dsrt_denoise_temporal(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(n), C.byref(gd), C.byref(prev_camera) if prev_camera is not None else None,
-                                         ptr(history_prev), ptr(history_next), C.byref(temporal), C.byref(params), ptr(rgb), ptr(f32), ptr(lin), ptr(var), ptr(pxy), ptr(wgt),
-                                         C.c_void_p(self._raw_stream(stream))), "dsrt_denoise_temporal")
-        return rgb, f32, lin, var, pxy, wgt
+        return self._denoise("denoise_temporal", desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight), stream,
+                             temporal=(prev_camera, history_prev, history_next, temporal))
 
     def denoise_temporal_to_host(self, desc, sums, sum_sq, guides, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None, params=None,
                                  want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=True, want_weight=True):
         """dsrt_denoise_temporal_to_host: the same from numpy arrays into numpy arrays.  history_prev: float32 (H, W, 16) or None.  Returns
         (rgb8, f32, linear, var, prev_xy, weight, history_next) -- history_next (H, W, 16), 64-byte aligned."""
-        H, W = desc.height, desc.width
-        S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
-        S2 = np.ascontiguousarray(sum_sq, np.uint64).reshape(H, W, 3)
-        cnt = np.ascontiguousarray(n, np.uint32).reshape(H, W) if n is not None else None
-        if set(guides) != set(DENOISE_GUIDES):
-            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
-        g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
-        prev = None
-        if history_prev is not None:
-            prev = aligned_zeros(H * W * capi.HISTORY_FLOATS)
-            prev[:] = np.asarray(history_prev, np.float32).reshape(-1)
-        nxt = aligned_zeros(H * W * capi.HISTORY_FLOATS)
-        params = denoise_defaults() if params is None else params
-        temporal = temporal_defaults() if temporal is None else temporal
-        rgb = np.zeros((H, W, 3), np.uint8) if want_rgb8 else None
-        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
-        pxy = np.zeros((H, W, 2), np.float32) if want_prev_xy else None
-        wgt = np.zeros((H, W), np.float32) if want_weight else None
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
-        acc = DsrtAccum(ptr(S), ptr(S2))
-        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
-        _check(lib.dsrt_denoise_temporal_to_host(self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(cnt), C.byref(gd),
-                                                 C.byref(prev_camera) if prev_camera is not None else None, ptr(prev), ptr(nxt), C.byref(temporal), C.byref(params), ptr(rgb), ptr(f32),
-                                                 ptr(lin), ptr(var), ptr(pxy), ptr(wgt)), "dsrt_denoise_temporal_to_host")
-        return rgb, f32, lin, var, pxy, wgt, nxt.reshape(H, W, capi.HISTORY_FLOATS)
+        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
+                                     dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight),
+                                     temporal=(prev_camera, history_prev, temporal))
 
     def render_denoised_temporal_to_host(self, desc, params=None, temporal=None, reset=False, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False):
         """dsrt_render_denoised_temporal_to_host: render_denoised_to_host with the history the CONTEXT keeps from call to call (reset=True starts a new sequence;
         change desc.seed from frame to frame).  Returns (rgb8, f32, linear, var, prev_xy, DsrtStats)."""
-        H, W = desc.height, desc.width
         params = denoise_defaults() if params is None else params
         temporal = temporal_defaults() if temporal is None else temporal
-        rgb = np.zeros((H, W, 3), np.uint8)
-        f32, lin, var = (np.zeros((H, W, 3), np.float32) if w else None for w in (want_f32, want_linear, want_var))
-        pxy = np.zeros((H, W, 2), np.float32) if want_prev_xy else None
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None          # noqa: E731
+        out = _outputs(desc, dict(rgb8=True, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy))
         st = DsrtStats()
-        _check(lib.dsrt_render_denoised_temporal_to_host(self._h, C.byref(desc), C.byref(params), C.byref(temporal), 1 if reset else 0, ptr(rgb), ptr(f32), ptr(lin), ptr(var),
-                                                         ptr(pxy), C.byref(st)), "dsrt_render_denoised_temporal_to_host")
-        return rgb, f32, lin, var, pxy, st
+        _check(lib.dsrt_render_denoised_temporal_to_host(self._h, C.byref(desc), C.byref(params), C.byref(temporal), 1 if reset else 0, *map(_array_ptr, out), C.byref(st)),
+               "dsrt_render_denoised_temporal_to_host")
+        return (*out, st)
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

@@ -377,6 +377,8 @@ constexpr size_t kListLenSched = 8;                          // masked accumulat
                                                              // the pre-pass's sched block, next to the words every fetch reads anyway and away from the queue words' atomics
 static_assert(4 + 2 * (size_t)kNumCounters <= kQueueLightWord, "counters overlap the second queue word");
 
+float inv_gamma_of(const DsrtRenderDesc& d) { return 1.0f / (d.gamma > 0.0f ? d.gamma : 1.0f); }        // gamma <= 0 is 1, src/gpu_render.cu:1043
+
 struct Tiling { int tile, tiles_x, tiles_y, total, mine, padded; };
 bool make_tiling(const DsrtRenderDesc& d, Tiling& t) {
     t.tile = d.tile_size > 0 ? d.tile_size : 8;
@@ -524,6 +526,44 @@ template <typename S>
 S pointers_as(void* const* mirrors) {              // the caller's list has sizeof(S) / sizeof(void*) entries from `mirrors` on, in S's order
     static_assert(std::is_trivially_copyable_v<S> && sizeof(S) % sizeof(void*) == 0, "a struct of pointers and nothing else");
     S s; std::memcpy(&s, mirrors, sizeof s); return s;
+}
+
+// A SAMPLE-SET FRAME'S BUFFERS, once: the sums and counts, the denoiser's guides, the image outputs and the temporal stage's four, each with its bytes per pixel, its
+// direction and the alignment its kernel needs.  check_denoise walks the table; the _to_host forms stage it (staged_frame_call).  A form leaves what it does not take null.
+struct FrameBuffers {
+    const void *sum, *sum_sq, *n;                                      // DsrtAccum, then the per-pixel counts
+    const void *normal, *position, *albedo, *range;                    // DsrtDenoiseGuides
+    const void *rgb8, *f32, *linear, *var;                             // the image outputs
+    const void *history_prev, *history_next, *prev_xy, *weight;        // the temporal stage's
+};
+struct FrameBufferKind { size_t bytes; Dir dir; size_t align; };
+constexpr size_t kHistoryBytes = 64;                                   // per pixel: include/dsrt.h, TEMPORAL ACCUMULATION
+constexpr FrameBufferKind kFrameBuffers[] = {
+    {24, Dir::In, 8}, {24, Dir::In, 8}, {4, Dir::In, 4},                                                  // (bytes per pixel, direction, alignment) in FrameBuffers' order,
+    {12, Dir::In, 4}, {12, Dir::In, 4}, {12, Dir::In, 4}, {4, Dir::In, 4},                                // a row of this table per row of the struct
+    {3, Dir::Out, 1}, {12, Dir::Out, 4}, {12, Dir::Out, 4}, {12, Dir::Out, 4},
+    {kHistoryBytes, Dir::In, 16}, {kHistoryBytes, Dir::Out, 16}, {8, Dir::Out, 4}, {4, Dir::Out, 4}};
+constexpr size_t kFrameBufferCount = sizeof(FrameBuffers) / sizeof(void*);
+constexpr size_t kFrameTemporal = offsetof(FrameBuffers, history_prev) / sizeof(void*);
+static_assert(sizeof kFrameBuffers / sizeof kFrameBuffers[0] == kFrameBufferCount, "kFrameBuffers has one entry per pointer of FrameBuffers");
+
+void frame_table(const FrameBuffers& b, size_t px, Staged (&s)[kFrameBufferCount]) {
+    const void* p[kFrameBufferCount];
+    std::memcpy(p, &b, sizeof p);
+    for (size_t k = 0; k < kFrameBufferCount; ++k) s[k] = Staged{p[k], px * kFrameBuffers[k].bytes, kFrameBuffers[k].dir};
+}
+DsrtAccum accum_of(const FrameBuffers& b) { return DsrtAccum{(uint64_t*)b.sum, (uint64_t*)b.sum_sq}; }
+
+// staged_call over a frame's table: call(the mirrors, by name) -> return code.  `finish`: the device has finished before the results are copied out.
+template <typename Call>
+int staged_frame_call(const FrameBuffers& host, size_t px, bool finish, Call&& call) {
+    Staged s[kFrameBufferCount];
+    frame_table(host, px, s);
+    return staged_call(s, [&](void* const* d) -> int {
+        if (int rc = call(pointers_as<FrameBuffers>(d))) return rc;
+        if (finish) HIP_TRY(hipStreamSynchronize(nullptr));
+        return DSRT_OK;
+    });
 }
 
 // Ray queries (raycast_kernel.hip).  Argument checks shared by the device and the host form: every range is known from `count`.
@@ -752,8 +792,7 @@ static int plan_render(const DsrtContext* ctx, const DsrtRenderDesc* desc, uint8
     f.sample_first = acc ? acc->first : 0;
     f.sample_stride = acc ? acc->stride : 1;
     f.max_depth = desc->max_depth > 0 ? desc->max_depth : 12;           // :723-725
-    const float gamma = desc->gamma > 0.0f ? desc->gamma : 1.0f;        // :1043
-    f.inv_gamma = 1.0f / gamma;
+    f.inv_gamma = inv_gamma_of(*desc);
     f.seed32 = (uint32_t)(desc->seed & 0xFFFFFFFFu);
     f.seed_hi = (uint32_t)(desc->seed >> 32);
     f.tile = t.tile; f.tiles_x = t.tiles_x; f.tiles_y = t.tiles_y;
@@ -1034,7 +1073,7 @@ static int read_render_stats(DsrtContext* ctx, const RenderPlan& p, DsrtStats* s
 }
 
 static int render_impl(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, void* stream_v, DsrtStats* stats, const BatchInput* batch,
-                       const AccumInput* acc = nullptr) {
+                              const AccumInput* acc = nullptr) {
     RenderPlan p;
     int rc = plan_render(ctx, desc, d_rgb8, d_f32, batch, acc, p);          // every refusal: nothing has been enqueued
     if (rc) return rc;
@@ -1128,12 +1167,24 @@ int dsrt_render_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* h
 // ---- Sample sets (include/dsrt.h, dsrt_render_accumulate): rng_mode 1 sums of any set of a pixel's samples, added into caller-owned buffers ----
 namespace {
 int accum_fail(const char* fn, const char* why) { set_error(std::string(fn) + ": " + why); return DSRT_ERR_INVALID; }
+// (`static` below: inside extern "C" a function of an unnamed namespace keeps its plain name, and without it the library would export that name)
 
-// Everything dsrt_render_accumulate refuses, checked before anything is launched or written: of the context, the frame and the set (ctx and desc are given) ...
+// What every entry point over a frame's sums refuses of `desc`, checked like everything below before any HIP call and before anything is written.  Where the
+// entry points differ, a parameter says so: a launch that renders (`renders`) words the rng_mode refusal for its caller and leaves math_mode and the size to
+// plan_render; the denoiser numbers pixels with 31 bits (`limit_2_31`).  (samples_done: check_sums, check_denoise; collect_counters: check_masked_desc.)
+static int check_frame_desc(const char* fn, const DsrtRenderDesc* desc, bool renders, bool limit_2_31) {
+    if (desc->rng_mode != 1) return accum_fail(fn, renders ? "sample sets need rng_mode 1 (rng_mode 0 draws a pixel's samples from one serial stream)" : "accumulated sums are rng_mode 1's");
+    if (!renders && desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
+    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
+    if (!renders && (desc->width < 2 || desc->height < 2)) return accum_fail(fn, "width and height must be >= 2");
+    if (limit_2_31 && (unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) return accum_fail(fn, "image too large (2^31 pixels)");
+    return DSRT_OK;
+}
+
+// Everything dsrt_render_accumulate refuses: of the context, the frame and the set (ctx and desc are given) ...
 int check_sample_set(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride) {
     if (!resident_scene(ctx, fn)) return DSRT_ERR_NO_SCENE;
-    if (desc->rng_mode != 1) return accum_fail(fn, "sample sets need rng_mode 1 (rng_mode 0 draws a pixel's samples from one serial stream)");
-    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
+    if (int rc = check_frame_desc(fn, desc, true, false)) return rc;
     if (first < 0) return accum_fail(fn, "first < 0");
     if (count < 1) return accum_fail(fn, "count < 1");
     if (stride < 1) return accum_fail(fn, "stride < 1");
@@ -1142,115 +1193,159 @@ int check_sample_set(const char* fn, const DsrtContext* ctx, const DsrtRenderDes
     return DSRT_OK;
 }
 
-// ... and of the sums.
-int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc) {
-    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
-    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL (it is required; sum_sq is the optional one)");
-    return check_sample_set(fn, ctx, desc, first, count, stride);
-}
-
-int check_resolve(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const void* rgb8, const void* f32, const void* var) {
-    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
-    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL");
-    if (desc->rng_mode != 1) return accum_fail(fn, "accumulated sums are rng_mode 1's");
-    if (desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
-    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
-    if (desc->width < 2 || desc->height < 2) return accum_fail(fn, "width and height must be >= 2");
-    if (samples_done < 1) return accum_fail(fn, "samples_done < 1");
-    if (!rgb8 && !f32 && !var) return accum_fail(fn, "no output");
-    if (var && !acc->sum_sq) return accum_fail(fn, "the variance needs DsrtAccum.sum_sq");
-    if (var && samples_done < 2) return accum_fail(fn, "the variance needs samples_done >= 2");
+int check_masked_desc(const char* fn, const DsrtRenderDesc* desc) {
+    if (desc->collect_counters != 0) return accum_fail(fn, "masked launches use the production and checked kernels only (collect_counters must be 0)");
     return DSRT_OK;
 }
+
+// ... and of the sums; a masked launch (`masked`: dsrt_render_accumulate_masked) needs its mask too.
+int check_accumulate(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, bool masked, const uint8_t* mask) {
+    if (!ctx || !desc || !acc) return accum_fail(fn, "null argument");
+    if (!acc->sum) return accum_fail(fn, "DsrtAccum.sum is NULL (it is required; sum_sq is the optional one)");
+    if (int rc = check_sample_set(fn, ctx, desc, first, count, stride)) return rc;
+    if (!masked) return DSRT_OK;
+    if (!mask) return accum_fail(fn, "the mask is NULL (dsrt_render_accumulate renders every pixel)");
+    return check_masked_desc(fn, desc);
+}
+
+// dsrt_render_accumulate and (`masked`) dsrt_render_accumulate_masked: mask (null = every pixel) and n as AccumInput has them ...
+static int accumulate_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, bool masked, const uint8_t* d_mask,
+                           uint32_t* d_n, void* stream, DsrtStats* stats) {
+    if (int rc = check_accumulate(fn, ctx, desc, first, count, stride, acc, masked, d_mask)) return rc;
+    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq, d_mask, d_n};
+    return render_impl(ctx, desc, nullptr, nullptr, stream, stats, nullptr, &in);
+}
+
+// ... and their _to_host forms: sums and counts in and out.
+struct AccumMirrors { DsrtAccum acc; const uint8_t* mask; uint32_t* n; };        // the staged list below, by name
+static int accumulate_to_host(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, bool masked, const uint8_t* h_mask,
+                              uint32_t* h_n, DsrtStats* stats) {
+    if (int rc = check_accumulate(fn, ctx, desc, first, count, stride, h_acc, masked, h_mask)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * desc->height;
+    const Staged s[4] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::InOut}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::InOut}, {h_mask, px, Dir::In},
+                         {h_n, px * sizeof(uint32_t), Dir::InOut}};
+    DsrtStats local;
+    return staged_call(s, [&](void* const* d) {
+        const AccumMirrors m = pointers_as<AccumMirrors>(d);
+        return accumulate_impl(fn, ctx, desc, first, count, stride, &m.acc, masked, m.mask, m.n, nullptr, stats ? stats : &local);
+    });
+}
+
+// What the two resolves, dsrt_select_unconverged and the adaptive driver refuse.  The checks ask whether a buffer is given, never what it holds: have_args (acc, and the
+// counts where they are needed), have_sum, have_sq say so (the adaptive _to_host driver checks before it has allocated any).  `samples_done`: null where per-pixel counts
+// stand in for it; `outputs`: the resolve's three, null for the convergence test, whose output is the mask.
+static int check_sums(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, bool have_args, bool have_sum, bool have_sq, const int* samples_done, bool need_sq,
+                      const void* const* outputs) {
+    if (!ctx || !desc || !have_args) return accum_fail(fn, "null argument");
+    if (!have_sum) return accum_fail(fn, "DsrtAccum.sum is NULL");
+    if (int rc = check_frame_desc(fn, desc, false, false)) return rc;
+    if (samples_done && *samples_done < 1) return accum_fail(fn, "samples_done < 1");
+    if (need_sq && !have_sq) return accum_fail(fn, "the variance needs DsrtAccum.sum_sq");
+    if (outputs && !outputs[0] && !outputs[1] && !outputs[2]) return accum_fail(fn, "no output");
+    if (samples_done && need_sq && *samples_done < 2) return accum_fail(fn, "the variance needs samples_done >= 2");
+    return DSRT_OK;
+}
+
+// dsrt_resolve_accumulated and dsrt_resolve_accumulated_counts: every pixel's count is samples_done, or (`per_pixel`) its own entry of d_n.
+static int resolve_sums(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, bool per_pixel, int samples_done, const uint32_t* d_n, uint8_t* d_rgb8,
+                        float* d_f32, float* d_var_of_mean, hipStream_t stream) {
+    const void* outputs[3] = {d_rgb8, d_f32, d_var_of_mean};
+    int rc = check_sums(fn, ctx, desc, acc && (d_n || !per_pixel), acc && acc->sum, acc && acc->sum_sq, per_pixel ? nullptr : &samples_done, d_var_of_mean != nullptr, outputs);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, maybe) comes first
+    const RenderLaunchers& rl = render_launchers(desc->math_mode == 1);
+    const size_t px = (size_t)desc->width * desc->height;
+    const unsigned long long* sum = (const unsigned long long*)acc->sum;
+    const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;       // (the second moment serves the variance only)
+    HIP_TRY(per_pixel ? rl.launch_resolve_counts(sum, d_n, inv_gamma_of(*desc), px, d_rgb8, d_f32, sq, d_var_of_mean, stream)
+                      : rl.launch_resolve(sum, samples_done, inv_gamma_of(*desc), px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
+    return DSRT_OK;
+}
+
+// The table's entries [from, to) against those before them and among themselves: alignment; then each of their outputs against every input up to `to` (over_input) and
+// against every other output not checked against it yet (over_output); then the outputs before `from` against their inputs (old_over_input; nothing to do for from = 0).
+static int check_frame_table(const char* fn, const Staged (&s)[kFrameBufferCount], size_t from, size_t to, const char* over_input, const char* over_output, const char* old_over_input) {
+    for (size_t k = from; k < to; ++k)
+        if ((uintptr_t)s[k].host & (kFrameBuffers[k].align - 1))
+            return accum_fail(fn, kFrameBuffers[k].align == 8 ? "a sum pointer is not 8-byte aligned" : kFrameBuffers[k].align == 16 ? "a history buffer is not 16-byte aligned" : "pointer not 4-byte aligned");
+    for (size_t a = from; a < to; ++a) {
+        if (s[a].dir != Dir::Out) continue;
+        for (size_t i = 0; i < to; ++i) if (s[i].dir == Dir::In && ranges_overlap(s[a], s[i])) return accum_fail(fn, over_input);
+        for (size_t b = 0; b < to; ++b) if (s[b].dir == Dir::Out && (b < from || b > a) && ranges_overlap(s[a], s[b])) return accum_fail(fn, over_output);
+    }
+    for (size_t a = 0; a < from; ++a)
+        for (size_t i = from; i < to; ++i) if (s[a].dir == Dir::Out && s[i].dir == Dir::In && ranges_overlap(s[a], s[i])) return accum_fail(fn, old_over_input);
+    return DSRT_OK;
+}
+
+// A frame's sums, counts and guides on the device for the length of a _to_host call, sums and counts zeroed, with the views of them the entry points take.
+struct FrameScratch {
+    DevBuf<unsigned long long> sum, sq;
+    DevBuf<uint32_t> n;
+    DevBuf<float> normal, position, albedo, range;
+    DsrtAccum acc{};
+    DsrtDenoiseGuides guides{};
+    DsrtGBuffer gb{};                                                  // the guides' four channels and no other
+    int init(size_t px, bool counts, bool with_guides) {
+        int rc;
+        if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (counts && (rc = n.alloc(px)))) return rc;
+        if (with_guides && ((rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px)))) return rc;
+        HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
+        if (counts) HIP_TRY(hipMemset(n.p, 0, px * sizeof(uint32_t)));
+        acc = DsrtAccum{(uint64_t*)sum.p, (uint64_t*)sq.p};
+        guides = DsrtDenoiseGuides{normal.p, position.p, albedo.p, range.p};
+        gb.normal = normal.p; gb.position = position.p; gb.albedo = albedo.p; gb.range = range.p;
+        return DSRT_OK;
+    }
+};
 }  // namespace
 
 int dsrt_render_accumulate(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, void* stream, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_accumulate", [&]() -> int {
-    const int rc = check_accumulate("dsrt_render_accumulate", ctx, desc, first, count, stride, acc);
-    if (rc) return rc;
-    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq, nullptr, nullptr};
-    return render_impl(ctx, desc, nullptr, nullptr, stream, stats, nullptr, &in);
+    return accumulate_impl("dsrt_render_accumulate", ctx, desc, first, count, stride, acc, false, nullptr, nullptr, stream, stats);
     });
 }
 
 int dsrt_render_accumulate_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_accumulate_to_host", [&]() -> int {
-    if (int rc = check_accumulate("dsrt_render_accumulate_to_host", ctx, desc, first, count, stride, h_acc)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)desc->width * desc->height * 3 * sizeof(uint64_t);
-    const Staged s[2] = {{h_acc->sum, bytes, Dir::InOut}, {h_acc->sum_sq, bytes, Dir::InOut}};
-    DsrtStats local;
-    return staged_call(s, [&](void* const* d) {
-        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
-        return dsrt_render_accumulate(ctx, desc, first, count, stride, &acc, nullptr, stats ? stats : &local);
-    });
+    return accumulate_to_host("dsrt_render_accumulate_to_host", ctx, desc, first, count, stride, h_acc, false, nullptr, nullptr, stats);
     });
 }
 
 int dsrt_resolve_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, uint8_t* d_rgb8, float* d_f32,
                              float* d_var_of_mean, void* stream_v) {
     return dsrt::guarded("dsrt_resolve_accumulated", [&]() -> int {
-    int rc = check_resolve("dsrt_resolve_accumulated", ctx, desc, acc, samples_done, d_rgb8, d_f32, d_var_of_mean);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, maybe) comes first
-    const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
-    const size_t px = (size_t)desc->width * desc->height;
-    const unsigned long long* sum = (const unsigned long long*)acc->sum;
-    const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;
-    HIP_TRY(render_launchers(desc->math_mode == 1).launch_resolve(sum, samples_done, inv_gamma, px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
-    return DSRT_OK;
+    return resolve_sums("dsrt_resolve_accumulated", ctx, desc, acc, false, samples_done, nullptr, d_rgb8, d_f32, d_var_of_mean, (hipStream_t)stream_v);
     });
 }
 
 int dsrt_resolve_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, uint8_t* h_rgb8, float* h_f32,
                                      float* h_var_of_mean) {
     return dsrt::guarded("dsrt_resolve_accumulated_to_host", [&]() -> int {
-    if (int rc = check_resolve("dsrt_resolve_accumulated_to_host", ctx, desc, h_acc, samples_done, h_rgb8, h_f32, h_var_of_mean)) return rc;
+    const void* outputs[3] = {h_rgb8, h_f32, h_var_of_mean};
+    if (int rc = check_sums("dsrt_resolve_accumulated_to_host", ctx, desc, h_acc != nullptr, h_acc && h_acc->sum, h_acc && h_acc->sum_sq, &samples_done, h_var_of_mean != nullptr, outputs))
+        return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t px = (size_t)desc->width * desc->height;
-    const Staged s[5] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {h_var_of_mean ? h_acc->sum_sq : nullptr, px * 3 * sizeof(uint64_t), Dir::In},   // (the second
-                         {h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_var_of_mean, px * 3 * sizeof(float), Dir::Out}};              //  moment serves the variance only)
-    return staged_call(s, [&](void* const* d) {
-        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
-        return dsrt_resolve_accumulated(ctx, desc, &acc, samples_done, (uint8_t*)d[2], (float*)d[3], (float*)d[4], nullptr);
+    FrameBuffers h{};
+    h.sum = h_acc->sum; h.sum_sq = h_var_of_mean ? h_acc->sum_sq : nullptr;          // (the second moment serves the variance only)
+    h.rgb8 = h_rgb8; h.f32 = h_f32; h.var = h_var_of_mean;
+    return staged_frame_call(h, (size_t)desc->width * desc->height, false, [&](const FrameBuffers& m) {
+        const DsrtAccum acc = accum_of(m);
+        return dsrt_resolve_accumulated(ctx, desc, &acc, samples_done, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.var, nullptr);
     });
     });
 }
 
 // ---- Adaptive sampling (include/dsrt.h, ADAPTIVE SAMPLING): masked sample sets, the convergence test that makes the masks, the per-pixel resolve, the driver ----
 namespace {
-int check_masked_desc(const char* fn, const DsrtRenderDesc* desc) {
-    if (desc->collect_counters != 0) return accum_fail(fn, "masked launches use the production and checked kernels only (collect_counters must be 0)");
-    return DSRT_OK;
-}
-
-int check_accumulate_masked(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, bool have_mask) {
-    if (int rc = check_accumulate(fn, ctx, desc, first, count, stride, acc)) return rc;
-    if (!have_mask) return accum_fail(fn, "the mask is NULL (dsrt_render_accumulate renders every pixel)");
-    return check_masked_desc(fn, desc);
-}
-
-// What dsrt_select_unconverged and dsrt_resolve_accumulated_counts refuse (`outputs`: the resolve's three; null for the test, whose output is the mask).
-// The checks ask whether a buffer is given, never what it holds: have_sum, have_sq, have_n say so (the _to_host driver checks before it has allocated any).
-int check_counts(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, bool have_sum, bool have_sq, bool have_n, bool need_sq, const void* const* outputs) {
-    if (!ctx || !desc || !have_n) return accum_fail(fn, "null argument");
-    if (!have_sum) return accum_fail(fn, "DsrtAccum.sum is NULL");
-    if (desc->rng_mode != 1) return accum_fail(fn, "accumulated sums are rng_mode 1's");
-    if (desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
-    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
-    if (desc->width < 2 || desc->height < 2) return accum_fail(fn, "width and height must be >= 2");
-    if (need_sq && !have_sq) return accum_fail(fn, "the variance needs DsrtAccum.sum_sq");
-    if (outputs && !outputs[0] && !outputs[1] && !outputs[2]) return accum_fail(fn, "no output");
-    return DSRT_OK;
-}
-
-int check_adaptive(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* ad, bool have_sum, bool have_sq, bool have_n, const void* rgb8,
+int check_adaptive(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* ad, bool have_args, bool have_sum, bool have_sq, const void* rgb8,
                    const void* f32, const void* var) {
     if (!ad) return accum_fail(fn, "null argument");
     const void* outputs[3] = {rgb8, f32, var};
-    if (int rc = check_counts(fn, ctx, desc, have_sum, have_sq, have_n, true, outputs)) return rc;
+    if (int rc = check_sums(fn, ctx, desc, have_args, have_sum, have_sq, nullptr, true, outputs)) return rc;
     if (int rc = check_sample_set(fn, ctx, desc, 0, 1, 1)) return rc;                         // whatever a masked launch refuses of ctx and desc
     if (int rc = check_masked_desc(fn, desc)) return rc;
     const int spp = desc->spp < 1 ? 1 : desc->spp;
@@ -1264,33 +1359,21 @@ int check_adaptive(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc*
 int dsrt_render_accumulate_masked(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* acc, const uint8_t* d_mask,
                                   uint32_t* d_n, void* stream, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_accumulate_masked", [&]() -> int {
-    const int rc = check_accumulate_masked("dsrt_render_accumulate_masked", ctx, desc, first, count, stride, acc, d_mask != nullptr);
-    if (rc) return rc;
-    const AccumInput in{first, count, stride, (unsigned long long*)acc->sum, (unsigned long long*)acc->sum_sq, d_mask, d_n};
-    return render_impl(ctx, desc, nullptr, nullptr, stream, stats, nullptr, &in);
+    return accumulate_impl("dsrt_render_accumulate_masked", ctx, desc, first, count, stride, acc, true, d_mask, d_n, stream, stats);
     });
 }
 
 int dsrt_render_accumulate_masked_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int first, int count, int stride, const DsrtAccum* h_acc, const uint8_t* h_mask,
                                           uint32_t* h_n, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_accumulate_masked_to_host", [&]() -> int {
-    if (int rc = check_accumulate_masked("dsrt_render_accumulate_masked_to_host", ctx, desc, first, count, stride, h_acc, h_mask != nullptr)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t px = (size_t)desc->width * desc->height;
-    const Staged s[4] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::InOut}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::InOut}, {h_mask, px, Dir::In},
-                         {h_n, px * sizeof(uint32_t), Dir::InOut}};
-    DsrtStats local;
-    return staged_call(s, [&](void* const* d) {
-        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
-        return dsrt_render_accumulate_masked(ctx, desc, first, count, stride, &acc, (const uint8_t*)d[2], (uint32_t*)d[3], nullptr, stats ? stats : &local);
-    });
+    return accumulate_to_host("dsrt_render_accumulate_masked_to_host", ctx, desc, first, count, stride, h_acc, true, h_mask, h_n, stats);
     });
 }
 
 int dsrt_select_unconverged(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, const uint32_t* d_n, float rel_tol, float floor, uint32_t n_min,
                             uint32_t n_max, uint8_t* d_mask, uint32_t* h_active, void* stream_v) {
     return dsrt::guarded("dsrt_select_unconverged", [&]() -> int {
-    int rc = check_counts("dsrt_select_unconverged", ctx, desc, acc && acc->sum, acc && acc->sum_sq, acc && d_n, true, nullptr);
+    int rc = check_sums("dsrt_select_unconverged", ctx, desc, acc && d_n, acc && acc->sum, acc && acc->sum_sq, nullptr, true, nullptr);
     if (rc) return rc;
     if (!d_mask) return accum_fail("dsrt_select_unconverged", "the mask is NULL");
     if (!(rel_tol >= 0.0f) || !(floor >= 0.0f)) return accum_fail("dsrt_select_unconverged", "rel_tol and floor must be >= 0");
@@ -1310,17 +1393,7 @@ int dsrt_select_unconverged(DsrtContext* ctx, const DsrtRenderDesc* desc, const 
 int dsrt_resolve_accumulated_counts(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, const uint32_t* d_n, uint8_t* d_rgb8, float* d_f32,
                                     float* d_var_of_mean, void* stream_v) {
     return dsrt::guarded("dsrt_resolve_accumulated_counts", [&]() -> int {
-    const void* outputs[3] = {d_rgb8, d_f32, d_var_of_mean};
-    int rc = check_counts("dsrt_resolve_accumulated_counts", ctx, desc, acc && acc->sum, acc && acc->sum_sq, acc && d_n, d_var_of_mean != nullptr, outputs);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    if ((rc = launch_begin(ctx, stream, {}))) return rc;
-    const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
-    const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;
-    HIP_TRY(render_launchers(desc->math_mode == 1).launch_resolve_counts((const unsigned long long*)acc->sum, d_n, inv_gamma, (size_t)desc->width * desc->height, d_rgb8,
-                                                                         d_f32, sq, d_var_of_mean, stream));
-    return DSRT_OK;
+    return resolve_sums("dsrt_resolve_accumulated_counts", ctx, desc, acc, true, 0, d_n, d_rgb8, d_f32, d_var_of_mean, (hipStream_t)stream_v);
     });
 }
 
@@ -1329,7 +1402,7 @@ int dsrt_resolve_accumulated_counts(DsrtContext* ctx, const DsrtRenderDesc* desc
 int dsrt_render_adaptive(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAdaptive* ad, const DsrtAccum* acc, uint32_t* d_n, uint8_t* d_rgb8, float* d_f32,
                          float* d_var_of_mean, void* stream_v, DsrtAdaptiveStats* stats) {
     return dsrt::guarded("dsrt_render_adaptive", [&]() -> int {
-    int rc = check_adaptive("dsrt_render_adaptive", ctx, desc, ad, acc && acc->sum, acc && acc->sum_sq, acc && d_n, d_rgb8, d_f32, d_var_of_mean);
+    int rc = check_adaptive("dsrt_render_adaptive", ctx, desc, ad, acc && d_n, acc && acc->sum, acc && acc->sum_sq, d_rgb8, d_f32, d_var_of_mean);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
@@ -1365,35 +1438,30 @@ int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, c
                                  DsrtAdaptiveStats* stats) {
     return dsrt::guarded("dsrt_render_adaptive_to_host", [&]() -> int {
     if (!ctx || !desc) return accum_fail("dsrt_render_adaptive_to_host", "null argument");
-    const size_t px = (size_t)desc->width * (size_t)desc->height;
-    DevBuf<unsigned long long> sum, sq;                     // the frame's sums live on the device for the call; the counts come back only if asked for
-    DevBuf<uint32_t> n;
     if (int rc = check_adaptive("dsrt_render_adaptive_to_host", ctx, desc, ad, true, true, true, h_rgb8, h_f32, h_var_of_mean)) return rc;   // (the call owns sums and counts)
     HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * (size_t)desc->height;
+    FrameScratch f;                                         // the frame's sums live on the device for the call; the counts come back only if asked for
     int rc;
-    if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (rc = n.alloc(px))) return rc;
-    HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(n.p, 0, px * sizeof(uint32_t)));
-    const DsrtAccum acc{(uint64_t*)sum.p, (uint64_t*)sq.p};
-    const Staged s[3] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_var_of_mean, px * 3 * sizeof(float), Dir::Out}};
-    if ((rc = staged_call(s, [&](void* const* d) -> int {
-            const int r = dsrt_render_adaptive(ctx, desc, ad, &acc, n.p, (uint8_t*)d[0], (float*)d[1], (float*)d[2], nullptr, stats);
-            if (r) return r;
-            HIP_TRY(hipStreamSynchronize(nullptr));
-            return DSRT_OK;
+    if ((rc = f.init(px, true, false))) return rc;
+    FrameBuffers h{};
+    h.rgb8 = h_rgb8; h.f32 = h_f32; h.var = h_var_of_mean;
+    if ((rc = staged_frame_call(h, px, true, [&](const FrameBuffers& m) {
+            return dsrt_render_adaptive(ctx, desc, ad, &f.acc, f.n.p, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.var, nullptr, stats);
         }))) return rc;
-    if (h_n) HIP_TRY(hipMemcpy(h_n, n.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_n) HIP_TRY(hipMemcpy(h_n, f.n.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return DSRT_OK;
     });
 }
 
 // ---- The denoiser (include/dsrt.h, DENOISER; denoise_kernel.hip): prepare, one a-trous launch per iteration, output.  It reads the caller's sums, counts and guides
-// and writes the caller's outputs and the context's own seven records per pixel; the render buffers, camera and sun are not touched. ----
-namespace {
-constexpr size_t kDenoiseGuideBytes[4] = {12, 12, 12, 4};                       // DsrtDenoiseGuides: normal, position, albedo, range
-static_assert(sizeof(DsrtDenoiseGuides) == 4 * sizeof(void*), "kDenoiseGuideBytes has one entry per pointer of DsrtDenoiseGuides");
+// and writes the caller's outputs and the context's own seven records per pixel; the render buffers, camera and sun are not touched.
+// Temporal accumulation (include/dsrt.h, TEMPORAL ACCUMULATION; temporal_kernel.hip) is the denoiser with the history stage in front of its iterations. ----
 
+// The temporal stage's part of a call (dsrt_denoise_temporal): null for the plain denoiser.
+struct TemporalInput { const GPUCamera* prev_camera; const float* prev; float* next; const DsrtTemporal* tp; float* prev_xy; float* weight; };
+
+namespace {
 int check_denoise_params(const char* fn, const DsrtDenoise* dn) {
     if (!dn) return accum_fail(fn, "null argument");
     if (dn->iterations < 0 || dn->iterations > 6) return accum_fail(fn, "iterations must be between 0 and 6");
@@ -1401,47 +1469,6 @@ int check_denoise_params(const char* fn, const DsrtDenoise* dn) {
     if (!(dn->sigma_l > 0.0f) || !(dn->sigma_z > 0.0f) || !(dn->sigma_a > 0.0f)) return accum_fail(fn, "sigma_l, sigma_z and sigma_a must be > 0");
     return DSRT_OK;
 }
-
-// Everything dsrt_denoise_accumulated refuses, before anything is launched or written; the same for the host form's host pointers.
-int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* n, const DsrtDenoiseGuides* guides,
-                  const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
-    if (!ctx || !desc || !acc || !guides || !dn) return accum_fail(fn, "null argument");
-    if (!acc->sum || !acc->sum_sq) return accum_fail(fn, "DsrtAccum.sum or sum_sq is NULL (the filter is guided by the variance: both are required)");
-    if (!guides->normal || !guides->position || !guides->albedo || !guides->range) return accum_fail(fn, "a guide channel is NULL (normal, position, albedo and range are required)");
-    if (desc->rng_mode != 1) return accum_fail(fn, "accumulated sums are rng_mode 1's");
-    if (desc->math_mode != 0 && desc->math_mode != 1) return accum_fail(fn, "math_mode must be 0 or 1");
-    if (desc->shard_count > 1) return accum_fail(fn, "sample sets of tile shards (shard_count > 1) are not supported");
-    if (desc->width < 2 || desc->height < 2) return accum_fail(fn, "width and height must be >= 2");
-    if ((unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) return accum_fail(fn, "image too large (2^31 pixels)");
-    if (!n && samples_done < 2) return accum_fail(fn, "samples_done < 2 (the variance needs two samples; pass per-pixel counts otherwise)");
-    if (int rc = check_denoise_params(fn, dn)) return rc;
-    if (!rgb8 && !f32 && !linear && !var) return accum_fail(fn, "no output");
-    const size_t px = (size_t)desc->width * desc->height;
-    Staged in[7] = {{acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {n, px * sizeof(uint32_t), Dir::In}};
-    channels(*guides, kDenoiseGuideBytes, px, Dir::In, in + 3);
-    const Staged out[4] = {{rgb8, px * 3, Dir::Out}, {f32, px * 3 * sizeof(float), Dir::Out}, {linear, px * 3 * sizeof(float), Dir::Out}, {var, px * 3 * sizeof(float), Dir::Out}};
-    if (((uintptr_t)acc->sum | (uintptr_t)acc->sum_sq) & 7u) return accum_fail(fn, "a sum pointer is not 8-byte aligned");
-    for (int k = 2; k < 7; ++k) if ((uintptr_t)in[k].host & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
-    for (int k = 1; k < 4; ++k) if ((uintptr_t)out[k].host & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
-    for (int a = 0; a < 4; ++a) {
-        for (const Staged& i : in) if (ranges_overlap(out[a], i)) return accum_fail(fn, "an output range overlaps an input range");
-        for (int b = a + 1; b < 4; ++b) if (ranges_overlap(out[a], out[b])) return accum_fail(fn, "two output ranges overlap");
-    }
-    return DSRT_OK;
-}
-}  // namespace
-
-void dsrt_denoise_defaults(DsrtDenoise* out) {
-    if (!out) return;
-    out->iterations = 5; out->normal_power_log2 = 5;
-    out->sigma_l = 1.0f; out->sigma_z = 0.01f; out->sigma_a = 0.1f;          // sigma_l: 1, not SVGF's 4 (include/dsrt.h says why)
-}
-
-// The temporal stage's part of a launch (dsrt_denoise_temporal, checked there): null for the plain denoiser.
-struct TemporalInput { const GPUCamera* prev_camera; const float* prev; float* next; const DsrtTemporal* tp; float* prev_xy; float* weight; };
-
-namespace {
-constexpr size_t kHistoryBytes = 64;                                            // per pixel: include/dsrt.h, TEMPORAL ACCUMULATION
 
 int check_temporal_params(const char* fn, const DsrtTemporal* tp) {
     if (!tp) return accum_fail(fn, "null argument (DsrtTemporal)");
@@ -1452,33 +1479,38 @@ int check_temporal_params(const char* fn, const DsrtTemporal* tp) {
     return DSRT_OK;
 }
 
-// Everything dsrt_denoise_temporal refuses, before anything is launched or written; the same for the host form's host pointers.
-int check_temporal(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* n, const DsrtDenoiseGuides* guides,
-                   const TemporalInput& t, const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
-    if (int rc = check_denoise(fn, ctx, desc, acc, samples_done, n, guides, dn, rgb8, f32, linear, var)) return rc;
-    if ((t.prev_camera != nullptr) != (t.prev != nullptr)) return accum_fail(fn, "the previous camera and the previous history go together: both NULL (first frame) or both given");
-    if (!t.next) return accum_fail(fn, "the next history is NULL (it is required)");
-    if (int rc = check_temporal_params(fn, t.tp)) return rc;
-    if (((uintptr_t)t.prev | (uintptr_t)t.next) & 15u) return accum_fail(fn, "a history buffer is not 16-byte aligned");
-    if (((uintptr_t)t.prev_xy | (uintptr_t)t.weight) & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
-    const size_t px = (size_t)desc->width * desc->height;
-    Staged in[8] = {{acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {n, px * sizeof(uint32_t), Dir::In}};
-    channels(*guides, kDenoiseGuideBytes, px, Dir::In, in + 3);
-    in[7] = Staged{t.prev, px * kHistoryBytes, Dir::In};
-    const Staged out[7] = {{t.next, px * kHistoryBytes, Dir::Out}, {t.prev_xy, px * 2 * sizeof(float), Dir::Out}, {t.weight, px * sizeof(float), Dir::Out},
-                           {rgb8, px * 3, Dir::Out}, {f32, px * 3 * sizeof(float), Dir::Out}, {linear, px * 3 * sizeof(float), Dir::Out}, {var, px * 3 * sizeof(float), Dir::Out}};
-    for (int a = 0; a < 3; ++a) {                                                // (the four image outputs among themselves and against the inputs: check_denoise)
-        for (const Staged& i : in) if (ranges_overlap(out[a], i)) return accum_fail(fn, "the next history, prev_xy or weight overlaps an input or the previous history");
-        for (int b = a + 1; b < 7; ++b) if (ranges_overlap(out[a], out[b])) return accum_fail(fn, "the next history, prev_xy or weight overlaps another output");
-    }
-    for (int a = 3; a < 7; ++a) if (ranges_overlap(out[a], in[7])) return accum_fail(fn, "an output range overlaps the previous history");
-    return DSRT_OK;
+// The buffers of a denoiser call, device or host form alike (the outputs as the caller gave them: an output not asked for is null).
+static FrameBuffers denoise_buffers(const DsrtAccum& acc, const uint32_t* n, const DsrtDenoiseGuides& g, const TemporalInput* t, const void* rgb8, const void* f32, const void* linear, const void* var) {
+    return FrameBuffers{acc.sum, acc.sum_sq, n, g.normal, g.position, g.albedo, g.range, rgb8, f32, linear, var,
+                        t ? t->prev : nullptr, t ? t->next : nullptr, t ? t->prev_xy : nullptr, t ? t->weight : nullptr};
 }
 
-// The launches of dsrt_denoise_accumulated and dsrt_denoise_temporal (arguments checked by the caller): prepare, the temporal stage if there is one, the iterations, output.
-int denoise_launches(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
-                     const TemporalInput* t, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, hipStream_t stream) {
+// Everything dsrt_denoise_accumulated and (with `t`) dsrt_denoise_temporal refuse, before anything is launched or written; the same for the host forms' host pointers.
+int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* n, const DsrtDenoiseGuides* guides,
+                  const TemporalInput* t, const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
+    if (!ctx || !desc || !acc || !guides || !dn) return accum_fail(fn, "null argument");
+    if (!acc->sum || !acc->sum_sq) return accum_fail(fn, "DsrtAccum.sum or sum_sq is NULL (the filter is guided by the variance: both are required)");
+    if (!guides->normal || !guides->position || !guides->albedo || !guides->range) return accum_fail(fn, "a guide channel is NULL (normal, position, albedo and range are required)");
+    if (int rc = check_frame_desc(fn, desc, false, true)) return rc;
+    if (!n && samples_done < 2) return accum_fail(fn, "samples_done < 2 (the variance needs two samples; pass per-pixel counts otherwise)");
+    if (int rc = check_denoise_params(fn, dn)) return rc;
+    if (!rgb8 && !f32 && !linear && !var) return accum_fail(fn, "no output");
+    Staged s[kFrameBufferCount];
+    frame_table(denoise_buffers(*acc, n, *guides, t, rgb8, f32, linear, var), (size_t)desc->width * desc->height, s);
+    if (int rc = check_frame_table(fn, s, 0, kFrameTemporal, "an output range overlaps an input range", "two output ranges overlap", nullptr)) return rc;
+    if (!t) return DSRT_OK;
+    if ((t->prev_camera != nullptr) != (t->prev != nullptr)) return accum_fail(fn, "the previous camera and the previous history go together: both NULL (first frame) or both given");
+    if (!t->next) return accum_fail(fn, "the next history is NULL (it is required)");
+    if (int rc = check_temporal_params(fn, t->tp)) return rc;
+    return check_frame_table(fn, s, kFrameTemporal, kFrameBufferCount, "the next history, prev_xy or weight overlaps an input or the previous history",
+                             "the next history, prev_xy or weight overlaps another output", "an output range overlaps the previous history");
+}
+
+// dsrt_denoise_accumulated and dsrt_denoise_temporal: the checks, then prepare, the temporal stage if there is one, the iterations, output.
+static int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                        const TemporalInput* t, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, hipStream_t stream) {
     int rc;
+    if ((rc = check_denoise(fn, ctx, desc, acc, samples_done, d_n, guides, t, dn, d_rgb8, d_f32, d_linear, d_var))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)desc->width * desc->height;
     // (growing frees the old records: the launch that may still read them has to be over first)
@@ -1505,83 +1537,78 @@ int denoise_launches(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAcc
     }
     for (int i = 0; i < dn->iterations; ++i)
         HIP_TRY(launch_denoise_atrous(b, i & 1, desc->width, desc->height, 1 << i, dn->normal_power_log2, dn->sigma_l, dn->sigma_z, dn->sigma_a, stream));
-    const float inv_gamma = 1.0f / (desc->gamma > 0.0f ? desc->gamma : 1.0f);        // as dsrt_render
-    HIP_TRY(launch_denoise_output(b, dn->iterations & 1, px, inv_gamma, desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
+    HIP_TRY(launch_denoise_output(b, dn->iterations & 1, px, inv_gamma_of(*desc), desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
     return launch_finish(ctx, stream, nullptr);                                      // the records are the context's: its next launch on any stream comes behind
 }
+
+// Their _to_host forms: the same call on device mirrors of the frame's table, the device finished before the results are copied out.
+static int denoise_to_host(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n, const DsrtDenoiseGuides* h_guides,
+                           const TemporalInput* ht, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var) {
+    if (int rc = check_denoise(fn, ctx, desc, h_acc, samples_done, h_n, h_guides, ht, dn, h_rgb8, h_f32, h_linear, h_var)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const FrameBuffers h = denoise_buffers(*h_acc, h_n, *h_guides, ht, h_rgb8, h_f32, h_linear, h_var);
+    return staged_frame_call(h, (size_t)desc->width * desc->height, true, [&](const FrameBuffers& m) {
+        const DsrtAccum acc = accum_of(m);
+        const DsrtDenoiseGuides g{(const float*)m.normal, (const float*)m.position, (const float*)m.albedo, (const float*)m.range};
+        const TemporalInput t{ht ? ht->prev_camera : nullptr, (const float*)m.history_prev, (float*)m.history_next, ht ? ht->tp : nullptr, (float*)m.prev_xy, (float*)m.weight};
+        return denoise_impl(fn, ctx, desc, &acc, samples_done, (const uint32_t*)m.n, &g, ht ? &t : nullptr, dn, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
+                            (float*)m.var, nullptr);
+    });
+}
+
+// The convenience forms (dsrt_render_denoised_to_host, and `temporal` dsrt_render_denoised_temporal_to_host): what they refuse; *spp is the frame's samples.
+static int check_render_denoised(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* dn, bool temporal, const DsrtTemporal* tp, bool any_output, int* spp) {
+    if (!ctx || !desc) return accum_fail(fn, "null argument");
+    if (int rc = check_denoise_params(fn, dn)) return rc;
+    if (temporal) if (int rc = check_temporal_params(fn, tp)) return rc;
+    if (!any_output) return accum_fail(fn, "no output");
+    *spp = desc->spp < 1 ? 1 : desc->spp;
+    if (int rc = check_sample_set(fn, ctx, desc, 0, *spp, 1)) return rc;              // DSRT_ERR_NO_SCENE before an upload; rng_mode 1, no shards
+    if (*spp < 2) return accum_fail(fn, "spp < 2 (the variance needs two samples)");
+    return DSRT_OK;
+}
+
+// ... and their three steps on a frame's scratch buffers `f`, the images into mirrors of the host's: desc->spp samples with second moments, the G-buffer of the current
+// camera, the filter (with `t`, its history stage: prev_xy is the one temporal output they return).
+static int render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int spp, const FrameScratch& f, const TemporalInput* t, const DsrtDenoise* dn, uint8_t* h_rgb8,
+                                   float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, DsrtStats* stats) {
+    FrameBuffers h{};
+    h.rgb8 = h_rgb8; h.f32 = h_f32; h.linear = h_linear; h.var = h_var; h.prev_xy = h_prev_xy;
+    DsrtStats local;
+    return staged_frame_call(h, (size_t)desc->width * (size_t)desc->height, true, [&](const FrameBuffers& m) -> int {
+        int r;
+        if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &f.acc, nullptr, stats ? stats : &local))) return r;
+        if ((r = dsrt_render_gbuffer(ctx, desc, &f.gb, nullptr, nullptr))) return r;
+        return t ? dsrt_denoise_temporal(ctx, desc, &f.acc, spp, nullptr, &f.guides, t->prev_camera, t->prev, t->next, t->tp, dn, (uint8_t*)m.rgb8, (float*)m.f32,
+                                         (float*)m.linear, (float*)m.var, (float*)m.prev_xy, nullptr, nullptr)
+                 : dsrt_denoise_accumulated(ctx, desc, &f.acc, spp, nullptr, &f.guides, dn, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear, (float*)m.var, nullptr);
+    });
+}
 }  // namespace
+
+void dsrt_denoise_defaults(DsrtDenoise* out) {
+    if (!out) return;
+    out->iterations = 5; out->normal_power_log2 = 5;
+    out->sigma_l = 1.0f; out->sigma_z = 0.01f; out->sigma_a = 0.1f;          // sigma_l: 1, not SVGF's 4 (include/dsrt.h says why)
+}
+
+void dsrt_temporal_defaults(DsrtTemporal* out) {
+    if (!out) return;
+    out->alpha_min = 0.1f; out->normal_cos_min = 0.9f; out->plane_tol = 0.01f; out->min_support = 0.9f;      // min_support: 0.9, not one tap of four (include/dsrt.h says why)
+}
 
 int dsrt_denoise_accumulated(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
                              const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, void* stream_v) {
     return dsrt::guarded("dsrt_denoise_accumulated", [&]() -> int {
-    if (int rc = check_denoise("dsrt_denoise_accumulated", ctx, desc, acc, samples_done, d_n, guides, dn, d_rgb8, d_f32, d_linear, d_var)) return rc;
-    return denoise_launches(ctx, desc, acc, samples_done, d_n, guides, nullptr, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
+    return denoise_impl("dsrt_denoise_accumulated", ctx, desc, acc, samples_done, d_n, guides, nullptr, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
     });
 }
 
 int dsrt_denoise_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n, const DsrtDenoiseGuides* h_guides,
                                      const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var) {
     return dsrt::guarded("dsrt_denoise_accumulated_to_host", [&]() -> int {
-    if (int rc = check_denoise("dsrt_denoise_accumulated_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, dn, h_rgb8, h_f32, h_linear, h_var)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t px = (size_t)desc->width * desc->height;
-    Staged s[11] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {h_n, px * sizeof(uint32_t), Dir::In}};
-    channels(*h_guides, kDenoiseGuideBytes, px, Dir::In, s + 3);
-    s[7] = Staged{h_rgb8, px * 3, Dir::Out};
-    s[8] = Staged{h_f32, px * 3 * sizeof(float), Dir::Out};
-    s[9] = Staged{h_linear, px * 3 * sizeof(float), Dir::Out};
-    s[10] = Staged{h_var, px * 3 * sizeof(float), Dir::Out};
-    return staged_call(s, [&](void* const* d) -> int {
-        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
-        const DsrtDenoiseGuides g = pointers_as<DsrtDenoiseGuides>(d + 3);
-        const int r = dsrt_denoise_accumulated(ctx, desc, &acc, samples_done, (const uint32_t*)d[2], &g, dn, (uint8_t*)d[7], (float*)d[8], (float*)d[9], (float*)d[10], nullptr);
-        if (r) return r;
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return DSRT_OK;
+    return denoise_to_host("dsrt_denoise_accumulated_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, nullptr, dn, h_rgb8, h_f32, h_linear, h_var);
     });
-    });
-}
-
-// The convenience form: desc->spp samples with second moments, the G-buffer of the current camera, the filter; sums and guides live on the device for the call.
-int dsrt_render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, DsrtStats* stats) {
-    return dsrt::guarded("dsrt_render_denoised_to_host", [&]() -> int {
-    const char* fn = "dsrt_render_denoised_to_host";
-    if (!ctx || !desc) return accum_fail(fn, "null argument");
-    if (int rc = check_denoise_params(fn, dn)) return rc;
-    if (!h_rgb8 && !h_f32 && !h_linear && !h_var) return accum_fail(fn, "no output");
-    const int spp = desc->spp < 1 ? 1 : desc->spp;
-    if (int rc = check_sample_set(fn, ctx, desc, 0, spp, 1)) return rc;               // DSRT_ERR_NO_SCENE before an upload; rng_mode 1, no shards
-    if (spp < 2) return accum_fail(fn, "spp < 2 (the variance needs two samples)");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t px = (size_t)desc->width * (size_t)desc->height;
-    DevBuf<unsigned long long> sum, sq;
-    DevBuf<float> normal, position, albedo, range;
-    int rc;
-    if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px))) return rc;
-    HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
-    const DsrtAccum acc{(uint64_t*)sum.p, (uint64_t*)sq.p};
-    const DsrtDenoiseGuides guides{normal.p, position.p, albedo.p, range.p};
-    DsrtGBuffer gb;
-    std::memset(&gb, 0, sizeof gb);
-    gb.normal = normal.p; gb.position = position.p; gb.albedo = albedo.p; gb.range = range.p;
-    const Staged s[4] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_linear, px * 3 * sizeof(float), Dir::Out}, {h_var, px * 3 * sizeof(float), Dir::Out}};
-    DsrtStats local;
-    return staged_call(s, [&](void* const* d) -> int {
-        int r;
-        if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &acc, nullptr, stats ? stats : &local))) return r;
-        if ((r = dsrt_render_gbuffer(ctx, desc, &gb, nullptr, nullptr))) return r;
-        if ((r = dsrt_denoise_accumulated(ctx, desc, &acc, spp, nullptr, &guides, dn, (uint8_t*)d[0], (float*)d[1], (float*)d[2], (float*)d[3], nullptr))) return r;
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return DSRT_OK;
-    });
-    });
-}
-
-// ---- Temporal accumulation (include/dsrt.h, TEMPORAL ACCUMULATION; temporal_kernel.hip): the denoiser with the history stage in front of its iterations ----
-void dsrt_temporal_defaults(DsrtTemporal* out) {
-    if (!out) return;
-    out->alpha_min = 0.1f; out->normal_cos_min = 0.9f; out->plane_tol = 0.01f; out->min_support = 0.9f;      // min_support: 0.9, not one tap of four (include/dsrt.h says why)
 }
 
 int dsrt_denoise_temporal(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
@@ -1589,8 +1616,7 @@ int dsrt_denoise_temporal(DsrtContext* ctx, const DsrtRenderDesc* desc, const Ds
                           uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, float* d_prev_xy, float* d_weight, void* stream_v) {
     return dsrt::guarded("dsrt_denoise_temporal", [&]() -> int {
     const TemporalInput t{prev_camera, d_history_prev, d_history_next, tp, d_prev_xy, d_weight};
-    if (int rc = check_temporal("dsrt_denoise_temporal", ctx, desc, acc, samples_done, d_n, guides, t, dn, d_rgb8, d_f32, d_linear, d_var)) return rc;
-    return denoise_launches(ctx, desc, acc, samples_done, d_n, guides, &t, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
+    return denoise_impl("dsrt_denoise_temporal", ctx, desc, acc, samples_done, d_n, guides, &t, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
     });
 }
 
@@ -1599,75 +1625,39 @@ int dsrt_denoise_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, 
                                   uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, float* h_weight) {
     return dsrt::guarded("dsrt_denoise_temporal_to_host", [&]() -> int {
     const TemporalInput ht{prev_camera, h_history_prev, h_history_next, tp, h_prev_xy, h_weight};
-    if (int rc = check_temporal("dsrt_denoise_temporal_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, ht, dn, h_rgb8, h_f32, h_linear, h_var)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t px = (size_t)desc->width * desc->height;
-    Staged s[15] = {{h_acc->sum, px * 3 * sizeof(uint64_t), Dir::In}, {h_acc->sum_sq, px * 3 * sizeof(uint64_t), Dir::In}, {h_n, px * sizeof(uint32_t), Dir::In}};
-    channels(*h_guides, kDenoiseGuideBytes, px, Dir::In, s + 3);
-    s[7] = Staged{h_rgb8, px * 3, Dir::Out};
-    s[8] = Staged{h_f32, px * 3 * sizeof(float), Dir::Out};
-    s[9] = Staged{h_linear, px * 3 * sizeof(float), Dir::Out};
-    s[10] = Staged{h_var, px * 3 * sizeof(float), Dir::Out};
-    s[11] = Staged{h_history_prev, px * kHistoryBytes, Dir::In};
-    s[12] = Staged{h_history_next, px * kHistoryBytes, Dir::Out};
-    s[13] = Staged{h_prev_xy, px * 2 * sizeof(float), Dir::Out};
-    s[14] = Staged{h_weight, px * sizeof(float), Dir::Out};
-    return staged_call(s, [&](void* const* d) -> int {
-        const DsrtAccum acc = pointers_as<DsrtAccum>(d);
-        const DsrtDenoiseGuides g = pointers_as<DsrtDenoiseGuides>(d + 3);
-        const int r = dsrt_denoise_temporal(ctx, desc, &acc, samples_done, (const uint32_t*)d[2], &g, prev_camera, (const float*)d[11], (float*)d[12], tp, dn, (uint8_t*)d[7],
-                                            (float*)d[8], (float*)d[9], (float*)d[10], (float*)d[13], (float*)d[14], nullptr);
-        if (r) return r;
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return DSRT_OK;
-    });
+    return denoise_to_host("dsrt_denoise_temporal_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, &ht, dn, h_rgb8, h_f32, h_linear, h_var);
     });
 }
 
-// The convenience form: dsrt_render_denoised_to_host's three steps, with the histories and the previous camera kept by the context from call to call.
+// The convenience form: sums and guides live on the device for the call.
+int dsrt_render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_denoised_to_host", [&]() -> int {
+    int spp, rc;
+    if ((rc = check_render_denoised("dsrt_render_denoised_to_host", ctx, desc, dn, false, nullptr, h_rgb8 || h_f32 || h_linear || h_var, &spp))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    FrameScratch f;
+    if ((rc = f.init((size_t)desc->width * (size_t)desc->height, false, true))) return rc;
+    return render_denoised_to_host(ctx, desc, spp, f, nullptr, dn, h_rgb8, h_f32, h_linear, h_var, nullptr, stats);
+    });
+}
+
+// The same with the histories and the previous camera kept by the context from call to call.
 int dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* dn, const DsrtTemporal* tp, int reset, uint8_t* h_rgb8, float* h_f32,
                                           float* h_linear, float* h_var, float* h_prev_xy, DsrtStats* stats) {
     return dsrt::guarded("dsrt_render_denoised_temporal_to_host", [&]() -> int {
-    const char* fn = "dsrt_render_denoised_temporal_to_host";
-    if (!ctx || !desc) return accum_fail(fn, "null argument");
-    if (int rc = check_denoise_params(fn, dn)) return rc;
-    if (int rc = check_temporal_params(fn, tp)) return rc;
-    if (!h_rgb8 && !h_f32 && !h_linear && !h_var) return accum_fail(fn, "no output");
-    const int spp = desc->spp < 1 ? 1 : desc->spp;
-    if (int rc = check_sample_set(fn, ctx, desc, 0, spp, 1)) return rc;               // DSRT_ERR_NO_SCENE before an upload; rng_mode 1, no shards
-    if (spp < 2) return accum_fail(fn, "spp < 2 (the variance needs two samples)");
+    int spp, rc;
+    if ((rc = check_render_denoised("dsrt_render_denoised_temporal_to_host", ctx, desc, dn, true, tp, h_rgb8 || h_f32 || h_linear || h_var, &spp))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)desc->width * (size_t)desc->height;
     const bool fresh = reset != 0 || !ctx->tp_valid || ctx->tp_width != desc->width || ctx->tp_height != desc->height;
-    DevBuf<unsigned long long> sum, sq;
-    DevBuf<float> normal, position, albedo, range;
-    int rc;
-    if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px))) return rc;
+    FrameScratch f;
+    if ((rc = f.init(px, false, true))) return rc;
     if (fresh) ctx->tp_valid = false;                                                 // (growing does not keep the contents: a sequence of another size is over either way)
     for (DevBuf<float4>& h : ctx->tp_hist) if ((rc = h.grow(px * 4))) return rc;      // (only this call, which is synchronous, uses them: nothing in flight reads them)
-    HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(sq.p, 0, px * 3 * sizeof(unsigned long long)));
-    const DsrtAccum acc{(uint64_t*)sum.p, (uint64_t*)sq.p};
-    const DsrtDenoiseGuides guides{normal.p, position.p, albedo.p, range.p};
-    DsrtGBuffer gb;
-    std::memset(&gb, 0, sizeof gb);
-    gb.normal = normal.p; gb.position = position.p; gb.albedo = albedo.p; gb.range = range.p;
     const GPUCamera camera = ctx->frame.camera, prev_camera = ctx->tp_camera;
-    const float* prev = fresh ? nullptr : (const float*)ctx->tp_hist[ctx->tp_cur].p;
-    float* next = (float*)ctx->tp_hist[fresh ? 0 : ctx->tp_cur ^ 1].p;
-    const Staged s[5] = {{h_rgb8, px * 3, Dir::Out}, {h_f32, px * 3 * sizeof(float), Dir::Out}, {h_linear, px * 3 * sizeof(float), Dir::Out}, {h_var, px * 3 * sizeof(float), Dir::Out},
-                         {h_prev_xy, px * 2 * sizeof(float), Dir::Out}};
-    DsrtStats local;
-    rc = staged_call(s, [&](void* const* d) -> int {
-        int r;
-        if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &acc, nullptr, stats ? stats : &local))) return r;
-        if ((r = dsrt_render_gbuffer(ctx, desc, &gb, nullptr, nullptr))) return r;
-        if ((r = dsrt_denoise_temporal(ctx, desc, &acc, spp, nullptr, &guides, fresh ? nullptr : &prev_camera, prev, next, tp, dn, (uint8_t*)d[0], (float*)d[1], (float*)d[2],
-                                       (float*)d[3], (float*)d[4], nullptr, nullptr))) return r;
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return DSRT_OK;
-    });
-    if (rc) return rc;
+    const TemporalInput t{fresh ? nullptr : &prev_camera, fresh ? nullptr : (const float*)ctx->tp_hist[ctx->tp_cur].p, (float*)ctx->tp_hist[fresh ? 0 : ctx->tp_cur ^ 1].p, tp,
+                          nullptr, nullptr};
+    if ((rc = render_denoised_to_host(ctx, desc, spp, f, &t, dn, h_rgb8, h_f32, h_linear, h_var, h_prev_xy, stats))) return rc;
     ctx->tp_cur = fresh ? 0 : ctx->tp_cur ^ 1;
     ctx->tp_camera = camera; ctx->tp_width = desc->width; ctx->tp_height = desc->height;
     ctx->tp_valid = true;

@@ -30,6 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <sys/stat.h>
 #include <vector>
@@ -183,172 +184,133 @@ int main(int argc, char** argv) {
     DsrtRenderDesc d;
     std::memset(&d, 0, sizeof d);
     d.width = width; d.height = height; d.spp = spp; d.max_depth = depth; d.gamma = 2.0f; d.seed = 1337; d.rng_mode = rng_mode; d.math_mode = math_mode;
-    const size_t image_bytes = (size_t)width * height * 3;
-    if (adaptive) {
-        const size_t px = (size_t)width * height;
-        std::vector<uint8_t> img(image_bytes);
-        std::vector<uint32_t> n(px);
-        std::vector<float> spp_map(px), var(variance ? image_bytes : 0);
-        const DsrtAdaptive ad{adaptive_passes, adaptive_min, adaptive_tol, adaptive_floor};
-        for (size_t q = 0; q < ids.size(); ++q) {
-            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
-            DsrtAdaptiveStats st;
-            if (dsrt_render_adaptive_to_host(ctx, &d, &ad, n.data(), img.data(), nullptr, variance ? var.data() : nullptr, &st) != DSRT_OK) return fail("rendering adaptively");
-            char stem[64];
-            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
-            const std::string base = out_dir + stem, path = base + (png ? ".png" : ".ppm");
-            if ((png ? dsrt_write_png(path.c_str(), img.data(), width, height) : dsrt_write_ppm(path.c_str(), img.data(), width, height)) != DSRT_OK) return fail("writing the frame");
-            for (size_t i = 0; i < px; ++i) spp_map[i] = (float)n[i];
-            if (dsrt_write_pfm((base + "_spp.pfm").c_str(), spp_map.data(), width, height, 1) != DSRT_OK) return fail("writing the sample counts");
-            if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
-            std::printf("adaptive: %d of %d passes, %.1f %% of the frame's %d samples per pixel; pixels per pass:", st.passes_run, adaptive_passes,
-                        100.0 * (double)st.samples_total / ((double)px * spp), spp);
-            for (int p = 0; p < st.passes_run; ++p) std::printf(" %u", st.active[p]);
-            std::printf("\nSaved %s, %s_spp.pfm%s\n", path.c_str(), base.c_str(), variance ? " and _var.pfm" : "");
-        }
-        dsrt_ctx_destroy(ctx);
-        dsrt_host_scene_destroy(hs);
-        std::printf("Done.\n");
+    const size_t px = (size_t)width * height, image_bytes = px * 3;
+    const std::string ext = png ? ".png" : ".ppm";
+    auto frame_base = [&](size_t id) { char stem[64]; std::snprintf(stem, sizeof stem, "/frame_%04zu", id); return out_dir + stem; };
+    auto write_image = [&](const std::string& path, const uint8_t* image) {
+        return (png ? dsrt_write_png(path.c_str(), image, width, height) : dsrt_write_ppm(path.c_str(), image, width, height)) == DSRT_OK;
+    };
+
+    // The modes that render frame by frame: one step each, over buffers that stay empty where the mode does not use them.
+    const bool host_sums = (denoise && !temporal) || (!denoise && !adaptive && (passes != 0 || variance));
+    std::vector<uint8_t> img(image_bytes), raw(denoise ? image_bytes : 0);
+    std::vector<float> var(variance ? image_bytes : 0);
+    std::vector<uint64_t> sum(host_sums ? image_bytes : 0), sq(host_sums && (denoise || variance) ? image_bytes : 0);
+    const DsrtAccum acc{sum.data(), sq.empty() ? nullptr : sq.data()};
+    auto write_var = [&](const std::string& base) { return !variance || dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) == DSRT_OK; };
+    DsrtDenoise dn;
+    dsrt_denoise_defaults(&dn);
+    if (denoise_iterations >= 0) dn.iterations = denoise_iterations;
+    std::function<int(size_t, const std::string&)> frame_step;           // (index into ids, <out_dir>/frame_NNNN) -> exit code; empty: the batch launches below
+
+    std::vector<uint32_t> n(adaptive ? px : 0);
+    std::vector<float> spp_map(adaptive ? px : 0);
+    const DsrtAdaptive ad{adaptive_passes, adaptive_min, adaptive_tol, adaptive_floor};
+    if (adaptive) frame_step = [&](size_t, const std::string& base) -> int {
+        DsrtAdaptiveStats st;
+        if (dsrt_render_adaptive_to_host(ctx, &d, &ad, n.data(), img.data(), nullptr, variance ? var.data() : nullptr, &st) != DSRT_OK) return fail("rendering adaptively");
+        const std::string path = base + ext;
+        if (!write_image(path, img.data())) return fail("writing the frame");
+        for (size_t i = 0; i < px; ++i) spp_map[i] = (float)n[i];
+        if (dsrt_write_pfm((base + "_spp.pfm").c_str(), spp_map.data(), width, height, 1) != DSRT_OK) return fail("writing the sample counts");
+        if (!write_var(base)) return fail("writing the variance");
+        std::printf("adaptive: %d of %d passes, %.1f %% of the frame's %d samples per pixel; pixels per pass:", st.passes_run, adaptive_passes,
+                    100.0 * (double)st.samples_total / ((double)px * spp), spp);
+        for (int p = 0; p < st.passes_run; ++p) std::printf(" %u", st.active[p]);
+        std::printf("\nSaved %s, %s_spp.pfm%s\n", path.c_str(), base.c_str(), variance ? " and _var.pfm" : "");
         return 0;
-    }
-    if (denoise && temporal) {
-        // Each frame in pose order through the convenience form, the history kept by the context; the raw image is the same samples in one launch.
-        const size_t px = (size_t)width * height;
-        std::vector<uint8_t> raw(image_bytes), img(image_bytes);
-        std::vector<float> var(variance ? image_bytes : 0), prev_xy(flow ? px * 2 : 0), flow_px(flow ? px * 3 : 0);
-        DsrtDenoise dn;
-        dsrt_denoise_defaults(&dn);
-        if (denoise_iterations >= 0) dn.iterations = denoise_iterations;
-        DsrtTemporal tp;
-        dsrt_temporal_defaults(&tp);
-        const std::string ext = png ? ".png" : ".ppm";
-        auto write = [&](const std::string& path, const std::vector<uint8_t>& image) {
-            return (png ? dsrt_write_png(path.c_str(), image.data(), width, height) : dsrt_write_ppm(path.c_str(), image.data(), width, height)) == DSRT_OK;
-        };
-        for (size_t q = 0; q < ids.size(); ++q) {
-            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
-            d.seed = 1337 + (uint64_t)ids[q];
-            if (dsrt_render_denoised_temporal_to_host(ctx, &d, &dn, &tp, q == 0 ? 1 : 0, img.data(), nullptr, nullptr, variance ? var.data() : nullptr,
-                                                      flow ? prev_xy.data() : nullptr, nullptr) != DSRT_OK) return fail("rendering with temporal accumulation");
-            if (dsrt_render_to_host(ctx, &d, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("rendering the raw image");
-            char stem[64];
-            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
-            const std::string base = out_dir + stem;
-            if (!write(base + ext, img) || !write(base + "_raw" + ext, raw)) return fail("writing the frame");
-            if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
-            if (flow) {
-                for (size_t i = 0; i < px; ++i) {
-                    flow_px[3 * i + 0] = prev_xy[2 * i + 0] - (float)(i % (size_t)width);
-                    flow_px[3 * i + 1] = prev_xy[2 * i + 1] - (float)(i / (size_t)width);
-                    flow_px[3 * i + 2] = 0.0f;
-                }
-                if (dsrt_write_pfm((base + "_flow.pfm").c_str(), flow_px.data(), width, height, 3) != DSRT_OK) return fail("writing the flow");
+    };
+
+    // --denoise --temporal: each frame in pose order through the convenience form, the history kept by the context; the raw image is the same samples in one launch.
+    std::vector<float> prev_xy(flow ? px * 2 : 0), flow_px(flow ? px * 3 : 0);
+    DsrtTemporal tp;
+    dsrt_temporal_defaults(&tp);
+    if (denoise && temporal) frame_step = [&](size_t q, const std::string& base) -> int {
+        d.seed = 1337 + (uint64_t)ids[q];
+        if (dsrt_render_denoised_temporal_to_host(ctx, &d, &dn, &tp, q == 0 ? 1 : 0, img.data(), nullptr, nullptr, variance ? var.data() : nullptr,
+                                                  flow ? prev_xy.data() : nullptr, nullptr) != DSRT_OK) return fail("rendering with temporal accumulation");
+        if (dsrt_render_to_host(ctx, &d, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("rendering the raw image");
+        if (!write_image(base + ext, img.data()) || !write_image(base + "_raw" + ext, raw.data())) return fail("writing the frame");
+        if (!write_var(base)) return fail("writing the variance");
+        if (flow) {
+            for (size_t i = 0; i < px; ++i) {
+                flow_px[3 * i + 0] = prev_xy[2 * i + 0] - (float)(i % (size_t)width);
+                flow_px[3 * i + 1] = prev_xy[2 * i + 1] - (float)(i / (size_t)width);
+                flow_px[3 * i + 2] = 0.0f;
             }
-            std::printf("denoise: %d iterations, temporal, seed %llu\nSaved %s, %s_raw%s%s%s\n", dn.iterations, (unsigned long long)d.seed, (base + ext).c_str(), base.c_str(),
-                        ext.c_str(), variance ? ", _var.pfm" : "", flow ? ", _flow.pfm" : "");
+            if (dsrt_write_pfm((base + "_flow.pfm").c_str(), flow_px.data(), width, height, 3) != DSRT_OK) return fail("writing the flow");
         }
-        dsrt_ctx_destroy(ctx);
-        dsrt_host_scene_destroy(hs);
-        std::printf("Done.\n");
+        std::printf("denoise: %d iterations, temporal, seed %llu\nSaved %s, %s_raw%s%s%s\n", dn.iterations, (unsigned long long)d.seed, (base + ext).c_str(), base.c_str(),
+                    ext.c_str(), variance ? ", _var.pfm" : "", flow ? ", _flow.pfm" : "");
         return 0;
-    }
-    if (denoise) {
-        // Each frame: its sums with second moments, the raw image they resolve to, the G-buffer of its camera, the filter (include/dsrt.h, DENOISER).
-        const size_t px = (size_t)width * height;
-        std::vector<uint64_t> sum(image_bytes), sq(image_bytes);
-        std::vector<uint8_t> raw(image_bytes), img(image_bytes);
-        std::vector<float> normal(image_bytes), position(image_bytes), albedo(image_bytes), range(px), var(variance ? image_bytes : 0);
-        const DsrtAccum acc{sum.data(), sq.data()};
-        const DsrtDenoiseGuides guides{normal.data(), position.data(), albedo.data(), range.data()};
-        DsrtGBuffer g;
-        std::memset(&g, 0, sizeof g);
-        g.normal = normal.data(); g.position = position.data(); g.albedo = albedo.data(); g.range = range.data();
-        DsrtDenoise dn;
-        dsrt_denoise_defaults(&dn);
-        if (denoise_iterations >= 0) dn.iterations = denoise_iterations;
-        const std::string ext = png ? ".png" : ".ppm";
-        auto write = [&](const std::string& path, const std::vector<uint8_t>& image) {
-            return (png ? dsrt_write_png(path.c_str(), image.data(), width, height) : dsrt_write_ppm(path.c_str(), image.data(), width, height)) == DSRT_OK;
-        };
-        for (size_t q = 0; q < ids.size(); ++q) {
-            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
-            std::fill(sum.begin(), sum.end(), 0);
-            std::fill(sq.begin(), sq.end(), 0);
-            if (dsrt_render_accumulate_to_host(ctx, &d, 0, spp, 1, &acc, nullptr) != DSRT_OK) return fail("rendering the samples");
-            if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, spp, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving the raw image");
-            if (dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK) return fail("rendering the G-buffer");
-            if (dsrt_denoise_accumulated_to_host(ctx, &d, &acc, spp, nullptr, &guides, &dn, img.data(), nullptr, nullptr, variance ? var.data() : nullptr) != DSRT_OK)
-                return fail("denoising");
-            char stem[64];
-            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
-            const std::string base = out_dir + stem;
-            if (!write(base + ext, img) || !write(base + "_raw" + ext, raw)) return fail("writing the frame");
-            if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
-            std::printf("denoise: %d iterations\nSaved %s, %s_raw%s%s\n", dn.iterations, (base + ext).c_str(), base.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
-        }
-        dsrt_ctx_destroy(ctx);
-        dsrt_host_scene_destroy(hs);
-        std::printf("Done.\n");
+    };
+
+    // --denoise: each frame's sums with second moments, the raw image they resolve to, the G-buffer of its camera, the filter (include/dsrt.h, DENOISER).
+    const bool guided = denoise && !temporal;
+    std::vector<float> normal(guided ? image_bytes : 0), position(guided ? image_bytes : 0), albedo(guided ? image_bytes : 0), range(guided ? px : 0);
+    const DsrtDenoiseGuides guides{normal.data(), position.data(), albedo.data(), range.data()};
+    DsrtGBuffer g;
+    std::memset(&g, 0, sizeof g);
+    g.normal = normal.data(); g.position = position.data(); g.albedo = albedo.data(); g.range = range.data();
+    if (guided) frame_step = [&](size_t, const std::string& base) -> int {
+        std::fill(sum.begin(), sum.end(), 0);
+        std::fill(sq.begin(), sq.end(), 0);
+        if (dsrt_render_accumulate_to_host(ctx, &d, 0, spp, 1, &acc, nullptr) != DSRT_OK) return fail("rendering the samples");
+        if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, spp, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving the raw image");
+        if (dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK) return fail("rendering the G-buffer");
+        if (dsrt_denoise_accumulated_to_host(ctx, &d, &acc, spp, nullptr, &guides, &dn, img.data(), nullptr, nullptr, variance ? var.data() : nullptr) != DSRT_OK)
+            return fail("denoising");
+        if (!write_image(base + ext, img.data()) || !write_image(base + "_raw" + ext, raw.data())) return fail("writing the frame");
+        if (!write_var(base)) return fail("writing the variance");
+        std::printf("denoise: %d iterations\nSaved %s, %s_raw%s%s\n", dn.iterations, (base + ext).c_str(), base.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
         return 0;
-    }
-    if (passes != 0 || variance) {
-        // Each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
-        // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).
+    };
+
+    // --passes / --variance: each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
+    // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).
+    if (!adaptive && !denoise && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
         const int P = passes > 0 ? passes : 1;
-        std::vector<uint64_t> sum(image_bytes), sq(variance ? image_bytes : 0);
-        std::vector<uint8_t> img(image_bytes);
-        std::vector<float> var(variance ? image_bytes : 0);
-        const DsrtAccum acc{sum.data(), variance ? sq.data() : nullptr};
-        for (size_t q = 0; q < ids.size(); ++q) {
-            if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
-            std::fill(sum.begin(), sum.end(), 0ull);
-            std::fill(sq.begin(), sq.end(), 0ull);
-            int done = 0;
-            char stem[64];
-            std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[q]);
-            const std::string base = out_dir + stem, ext = png ? ".png" : ".ppm";
-            for (int p = 0; p < P; ++p) {
-                const int count = (spp - p + P - 1) / P;
-                DsrtStats st;
-                if (dsrt_render_accumulate_to_host(ctx, &d, p, count, P, &acc, &st) != DSRT_OK) return fail("rendering a pass");
-                done += count;
-                if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, done, img.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving a pass");
-                const std::string path = p + 1 < P || passes > 0 ? base + "_pass" + std::to_string(p + 1) + "of" + std::to_string(P) + ext : base + ext;
-                if ((png ? dsrt_write_png(path.c_str(), img.data(), width, height) : dsrt_write_ppm(path.c_str(), img.data(), width, height)) != DSRT_OK) return fail("writing the frame");
-                std::printf("pass %d/%d: %d samples per pixel, kernel %.3f ms; saved %s\n", p + 1, P, done, st.kernel_ms, path.c_str());
-            }
-            if (passes > 0 && (png ? dsrt_write_png((base + ext).c_str(), img.data(), width, height) : dsrt_write_ppm((base + ext).c_str(), img.data(), width, height)) != DSRT_OK)
-                return fail("writing the frame");
-            if (variance) {
-                if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, done, nullptr, nullptr, var.data()) != DSRT_OK) return fail("resolving the variance");
-                if (dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) != DSRT_OK) return fail("writing the variance");
-                std::printf("Saved %s_var.pfm\n", base.c_str());
-            }
-            std::printf("Saved %s%s\n", base.c_str(), ext.c_str());
+        std::fill(sum.begin(), sum.end(), 0ull);
+        std::fill(sq.begin(), sq.end(), 0ull);
+        int done = 0;
+        for (int p = 0; p < P; ++p) {
+            const int count = (spp - p + P - 1) / P;
+            DsrtStats st;
+            if (dsrt_render_accumulate_to_host(ctx, &d, p, count, P, &acc, &st) != DSRT_OK) return fail("rendering a pass");
+            done += count;
+            if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, done, img.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving a pass");
+            const std::string path = p + 1 < P || passes > 0 ? base + "_pass" + std::to_string(p + 1) + "of" + std::to_string(P) + ext : base + ext;
+            if (!write_image(path, img.data())) return fail("writing the frame");
+            std::printf("pass %d/%d: %d samples per pixel, kernel %.3f ms; saved %s\n", p + 1, P, done, st.kernel_ms, path.c_str());
         }
-        dsrt_ctx_destroy(ctx);
-        dsrt_host_scene_destroy(hs);
-        std::printf("Done.\n");
+        if (passes > 0 && !write_image(base + ext, img.data())) return fail("writing the frame");
+        if (variance) {
+            if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, done, nullptr, nullptr, var.data()) != DSRT_OK) return fail("resolving the variance");
+            if (!write_var(base)) return fail("writing the variance");
+            std::printf("Saved %s_var.pfm\n", base.c_str());
+        }
+        std::printf("Saved %s%s\n", base.c_str(), ext.c_str());
         return 0;
+    };
+
+    for (size_t q = 0; frame_step && q < ids.size(); ++q) {
+        if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
+        if (const int rc = frame_step(q, frame_base(ids[q]))) return rc;
     }
     size_t per_launch = 32;
     while (per_launch > 1 && (unsigned long long)per_launch * width * height * (rng_mode == 1 ? 16ull : 1ull) >= (1ull << 32)) per_launch /= 2;
-    std::vector<uint8_t> fb(image_bytes * std::min(per_launch, std::max<size_t>(ids.size(), 1)));
-    for (size_t k = 0; k < ids.size(); k += per_launch) {
+    std::vector<uint8_t> fb(frame_step ? 0 : image_bytes * std::min(per_launch, std::max<size_t>(ids.size(), 1)));
+    for (size_t k = 0; !frame_step && k < ids.size(); k += per_launch) {
         const size_t n = std::min(per_launch, ids.size() - k);
         DsrtStats st;
         if (dsrt_render_batch_to_host(ctx, &d, (int)n, cams.data() + k, suns.data() + 3 * k, fb.data(), &st) != DSRT_OK) return fail("rendering");
         std::printf("\nframes %zu..%zu: kernel %.3f ms (%.1f Msamples/s)\n", ids[k], ids[k + n - 1], st.kernel_ms, (double)n * width * height * spp / (st.kernel_ms * 1e3));
         for (size_t q = 0; q < n; ++q) {
-            char name[64];
-            std::snprintf(name, sizeof name, png ? "/frame_%04zu.png" : "/frame_%04zu.ppm", ids[k + q]);
-            const std::string path = out_dir + name;
-            const uint8_t* img = fb.data() + q * image_bytes;
-            if ((png ? dsrt_write_png(path.c_str(), img, width, height) : dsrt_write_ppm(path.c_str(), img, width, height)) != DSRT_OK) return fail("writing the frame");
+            const std::string base = frame_base(ids[k + q]), path = base + ext;
+            if (!write_image(path, fb.data() + q * image_bytes)) return fail("writing the frame");
             std::printf("Saved %s\n", path.c_str());
             if (gbuffer) {
                 // the frame's ground truth: the context's camera and sun are set to this frame's (the batch launch above took them as arguments)
-                const size_t px = (size_t)width * height;
                 std::vector<float> range(px), normal(px * 3);
                 std::vector<uint8_t> flags(px);
                 DsrtGBuffer g;
@@ -356,9 +318,6 @@ int main(int argc, char** argv) {
                 g.range = range.data(); g.normal = normal.data(); g.flags = flags.data();
                 if (dsrt_scene_set_camera_sun(ctx, &cams[k + q], suns.data() + 3 * (k + q)) != DSRT_OK || dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK)
                     return fail("rendering the G-buffer");
-                char stem[64];
-                std::snprintf(stem, sizeof stem, "/frame_%04zu", ids[k + q]);
-                const std::string base = out_dir + stem;
                 if (dsrt_write_pfm((base + "_range.pfm").c_str(), range.data(), width, height, 1) != DSRT_OK ||
                     dsrt_write_pfm((base + "_normal.pfm").c_str(), normal.data(), width, height, 3) != DSRT_OK) return fail("writing the G-buffer");
                 if (!write_mask_pgm(base + "_mask.pgm", flags, width, height, DSRT_GB_HIT) || !write_mask_pgm(base + "_sunlit.pgm", flags, width, height, DSRT_GB_SUN_VISIBLE)) {
