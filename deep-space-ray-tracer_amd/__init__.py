@@ -242,6 +242,20 @@ def temporal_defaults(**changes):
     return p
 
 
+UPSCALE_GUIDES = DENOISE_GUIDES + ("flags",)                         # DsrtUpscaleGuides' channels; "flags" (uint8) is the optional one
+
+
+def upscale_defaults(**changes):
+    """dsrt_upscale_defaults: the DsrtUpscale the library fills (normal_power_log2, sigma_z, sigma_a, use_sun), with `changes` applied."""
+    p = capi.DsrtUpscale()
+    lib.dsrt_upscale_defaults(C.byref(p))
+    for k, v in changes.items():
+        if k not in dict(capi.DsrtUpscale._fields_):
+            raise ValueError(f"DsrtUpscale has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def aligned_zeros(count, dtype=np.float32, align=64):
     """A zeroed numpy array of `count` elements whose data starts on an `align`-byte boundary (a host history buffer must be 16-byte aligned)."""
     raw = np.zeros(count * np.dtype(dtype).itemsize + align, np.uint8)
@@ -312,7 +326,7 @@ def _array_ptr(a):
 
 
 _OUTPUTS = {"rgb8": (np.uint8, (3,)), "f32": (np.float32, (3,)), "linear": (np.float32, (3,)), "var": (np.float32, (3,)), "prev_xy": (np.float32, (2,)),
-            "weight": (np.float32, ())}
+            "weight": (np.float32, ()), "support": (np.float32, ())}
 
 
 def _outputs(desc, wants, device=None):
@@ -729,6 +743,67 @@ class Context:
         _check(lib.dsrt_render_denoised_temporal_to_host(self._h, C.byref(desc), C.byref(params), C.byref(temporal), 1 if reset else 0, *map(_array_ptr, out), C.byref(st)),
                "dsrt_render_denoised_temporal_to_host")
         return (*out, st)
+
+    # ---- the upscaler (include/dsrt.h, UPSCALER): a low-resolution linear image to the output resolution, guided by the G-buffers of both rasters ----
+    def _upscale_guides(self, guides, width, height, what, on_device):
+        """DsrtUpscaleGuides of {"normal", "position", "albedo", "range"[, "flags"]} at width x height, and the arrays that keep its pointers alive."""
+        if not set(DENOISE_GUIDES) <= set(guides) <= set(UPSCALE_GUIDES):
+            raise ValueError(f"{what} guides must hold {list(DENOISE_GUIDES)} and optionally 'flags', not {sorted(guides)}")
+        keep = {}
+        for k in UPSCALE_GUIDES:
+            x = guides.get(k)
+            if x is None:
+                continue
+            dt, comps = capi.GBUFFER_CHANNELS[k]
+            n = width * height * comps
+            if on_device:
+                keep[k] = self._device_tensor(x, getattr(_torch, np.dtype(dt).name), (n, f"{what} width*height*{comps} = {n}"), f"{what} guide {k}")
+            else:
+                keep[k] = np.ascontiguousarray(x, dt).reshape(n)
+        ptr = _tensor_ptr if on_device else _array_ptr
+        return capi.DsrtUpscaleGuides(**{k: ptr(x) for k, x in keep.items()}), keep
+
+    def upscale_guided(self, desc, lo_width, lo_height, lo_linear, lo_guides, hi_guides, lo_var=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
+                       want_var=False, want_support=False, stream=None):
+        """dsrt_upscale_guided (torch device tensors) or dsrt_upscale_guided_to_host (numpy arrays, chosen by lo_linear's type): the lo_width x lo_height linear image
+        `lo_linear` (float32, lo_height*lo_width*3; `lo_var` its variance, needed for want_var) at desc.width x desc.height.  lo_guides / hi_guides: the G-buffer
+        channels {"normal", "position", "albedo", "range"} and optionally "flags" (uint8) of the two rasters, same camera.  params: a DsrtUpscale (upscale_defaults()).
+        Returns (rgb8, f32, linear, var, support) of shape (height, width[, 3]), None where not asked for."""
+        on_device = _torch is not None and isinstance(lo_linear, _torch.Tensor)
+        w, h = int(lo_width), int(lo_height)
+        n = w * h * 3
+        if on_device:
+            numel = (n, f"lo_width*lo_height*3 = {n}")
+            lin = self._device_tensor(lo_linear, _torch.float32, numel, "lo_linear")
+            var = self._device_tensor(lo_var, _torch.float32, numel, "lo_var", required=False)
+        else:
+            lin = np.ascontiguousarray(lo_linear, np.float32).reshape(n)
+            var = np.ascontiguousarray(lo_var, np.float32).reshape(n) if lo_var is not None else None
+        lo, keep_lo = self._upscale_guides(lo_guides, w, h, "low-resolution", on_device)
+        hi, keep_hi = self._upscale_guides(hi_guides, desc.width, desc.height, "output", on_device)
+        params = upscale_defaults() if params is None else params
+        out = _outputs(desc, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, support=want_support), lin.device if on_device else None)
+        ptr = _tensor_ptr if on_device else _array_ptr
+        head = (self._h, C.byref(desc), w, h, ptr(lin), ptr(var), C.byref(lo), C.byref(hi), C.byref(params), *map(ptr, out))
+        if on_device:
+            _check(lib.dsrt_upscale_guided(*head, C.c_void_p(self._raw_stream(stream))), "dsrt_upscale_guided")
+        else:
+            _check(lib.dsrt_upscale_guided_to_host(*head), "dsrt_upscale_guided_to_host")
+        del keep_lo, keep_hi
+        return out
+
+    def render_upscaled_to_host(self, lo_desc, out_width, out_height, denoise=None, params=None, want_f32=False, want_linear=True, want_var=False, want_lo_rgb8=False):
+        """dsrt_render_upscaled_to_host: lo_desc.spp samples at lo_desc's size, the denoiser (`denoise`: a DsrtDenoise, None = the plain mean), the G-buffers of both
+        rasters and the upscaler, into numpy arrays of out_height x out_width: (rgb8, f32, linear, var, lo_rgb8, DsrtStats); lo_rgb8 is the low-resolution image."""
+        params = upscale_defaults() if params is None else params
+        hi = DsrtRenderDesc.from_buffer_copy(lo_desc)
+        hi.width, hi.height = int(out_width), int(out_height)
+        out = _outputs(hi, dict(rgb8=True, f32=want_f32, linear=want_linear, var=want_var))
+        lo_rgb8 = np.zeros((lo_desc.height, lo_desc.width, 3), np.uint8) if want_lo_rgb8 else None
+        st = DsrtStats()
+        _check(lib.dsrt_render_upscaled_to_host(self._h, C.byref(lo_desc), hi.width, hi.height, C.byref(denoise) if denoise is not None else None, C.byref(params),
+                                                *map(_array_ptr, out), _array_ptr(lo_rgb8), C.byref(st)), "dsrt_render_upscaled_to_host")
+        return (*out, lo_rgb8, st)
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

@@ -134,6 +134,14 @@ class DsrtTemporal(C.Structure):
     _fields_ = [("alpha_min", C.c_float), ("normal_cos_min", C.c_float), ("plane_tol", C.c_float), ("min_support", C.c_float)]
 
 
+class DsrtUpscaleGuides(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("normal", "position", "albedo", "range", "flags")]
+
+
+class DsrtUpscale(C.Structure):
+    _fields_ = [("normal_power_log2", C.c_int), ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("use_sun", C.c_int)]
+
+
 HISTORY_FLOATS = 16                                                     # per pixel of a temporal history buffer (include/dsrt.h, TEMPORAL ACCUMULATION)
 
 # The ray-query channels (include/dsrt.h, dsrt_trace_rays): name -> (numpy dtype, components per ray), in DsrtRayHits' order.
@@ -167,6 +175,7 @@ EXPORTS = [
     "dsrt_render_accumulate_masked", "dsrt_render_accumulate_masked_to_host", "dsrt_select_unconverged", "dsrt_resolve_accumulated_counts", "dsrt_render_adaptive", "dsrt_render_adaptive_to_host",
     "dsrt_denoise_defaults", "dsrt_denoise_accumulated", "dsrt_denoise_accumulated_to_host", "dsrt_render_denoised_to_host",
     "dsrt_temporal_defaults", "dsrt_denoise_temporal", "dsrt_denoise_temporal_to_host", "dsrt_render_denoised_temporal_to_host",
+    "dsrt_upscale_defaults", "dsrt_upscale_guided", "dsrt_upscale_guided_to_host", "dsrt_render_upscaled_to_host",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -278,6 +287,10 @@ def load():
     sig("dsrt_denoise_temporal_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), P(GPUCamera), vp, vp, P(DsrtTemporal), P(DsrtDenoise),
                                                   vp, vp, vp, vp, vp, vp])
     sig("dsrt_render_denoised_temporal_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtDenoise), P(DsrtTemporal), C.c_int, vp, vp, vp, vp, vp, P(DsrtStats)])
+    sig("dsrt_upscale_defaults", None, [P(DsrtUpscale)])
+    sig("dsrt_upscale_guided", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp, vp])
+    sig("dsrt_upscale_guided_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp])
+    sig("dsrt_render_upscaled_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, P(DsrtDenoise), P(DsrtUpscale), vp, vp, vp, vp, vp, P(DsrtStats)])
     sig("dsrt_selftest_math", C.c_int, [vp, C.c_int, vp, C.c_float, vp, C.c_int])
     sig("dsrt_selftest_devkat", C.c_int, [vp, C.c_int, vp, vp, C.c_int])
     sig("dsrt_selftest_philox", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp])
@@ -293,7 +306,7 @@ def load():
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
     for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
-                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal)):      # DSRT_SIZEOF_* of include/dsrt.h, in order
+                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale)):      # DSRT_SIZEOF_* of include/dsrt.h, in order
         if lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

@@ -346,6 +346,7 @@ struct DsrtContext {
     DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
     DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
     DevBuf<float4> dn_cl[2], dn_vl[2], dn_nr, dn_xf, dn_al;   // dsrt_denoise_accumulated: 7 records of 16 bytes per pixel (launchers.h, DenoiseBuffers)
+    DevBuf<float4> up_rec[5];       // dsrt_upscale_guided: 5 records of 16 bytes per LOW-resolution pixel (launchers.h, UpscaleRecords)
     // dsrt_render_denoised_temporal_to_host: the sequence the context keeps -- two histories (tp_hist[tp_cur] holds the last frame's), that frame's camera and size
     DevBuf<float4> tp_hist[2];
     GPUCamera tp_camera{};
@@ -530,35 +531,42 @@ S pointers_as(void* const* mirrors) {              // the caller's list has size
 
 // A SAMPLE-SET FRAME'S BUFFERS, once: the sums and counts, the denoiser's guides, the image outputs and the temporal stage's four, each with its bytes per pixel, its
 // direction and the alignment its kernel needs.  check_denoise walks the table; the _to_host forms stage it (staged_frame_call).  A form leaves what it does not take null.
+// The upscaler (dsrt_upscale_guided) has two rasters: the rows above are then the OUTPUT resolution's (its guides and images), and its own rows hold what it reads and
+// writes at the LOW resolution (`lo` in the table: that raster's pixel count sizes them), the output raster's flags and the support.
 struct FrameBuffers {
     const void *sum, *sum_sq, *n;                                      // DsrtAccum, then the per-pixel counts
     const void *normal, *position, *albedo, *range;                    // DsrtDenoiseGuides
     const void *rgb8, *f32, *linear, *var;                             // the image outputs
     const void *history_prev, *history_next, *prev_xy, *weight;        // the temporal stage's
+    const void *lo_linear, *lo_var, *lo_normal, *lo_position, *lo_albedo, *lo_range, *lo_flags, *lo_rgb8;      // the upscaler's, low resolution ...
+    const void *flags, *support;                                       // ... and output resolution
 };
-struct FrameBufferKind { size_t bytes; Dir dir; size_t align; };
+struct FrameBufferKind { size_t bytes; Dir dir; size_t align; bool lo = false; };
 constexpr size_t kHistoryBytes = 64;                                   // per pixel: include/dsrt.h, TEMPORAL ACCUMULATION
 constexpr FrameBufferKind kFrameBuffers[] = {
     {24, Dir::In, 8}, {24, Dir::In, 8}, {4, Dir::In, 4},                                                  // (bytes per pixel, direction, alignment) in FrameBuffers' order,
     {12, Dir::In, 4}, {12, Dir::In, 4}, {12, Dir::In, 4}, {4, Dir::In, 4},                                // a row of this table per row of the struct
     {3, Dir::Out, 1}, {12, Dir::Out, 4}, {12, Dir::Out, 4}, {12, Dir::Out, 4},
-    {kHistoryBytes, Dir::In, 16}, {kHistoryBytes, Dir::Out, 16}, {8, Dir::Out, 4}, {4, Dir::Out, 4}};
+    {kHistoryBytes, Dir::In, 16}, {kHistoryBytes, Dir::Out, 16}, {8, Dir::Out, 4}, {4, Dir::Out, 4},
+    {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {4, Dir::In, 4, true}, {1, Dir::In, 1, true},
+    {3, Dir::Out, 1, true}, {1, Dir::In, 1}, {4, Dir::Out, 4}};
 constexpr size_t kFrameBufferCount = sizeof(FrameBuffers) / sizeof(void*);
 constexpr size_t kFrameTemporal = offsetof(FrameBuffers, history_prev) / sizeof(void*);
+constexpr size_t kFrameUpscale = offsetof(FrameBuffers, lo_linear) / sizeof(void*);
 static_assert(sizeof kFrameBuffers / sizeof kFrameBuffers[0] == kFrameBufferCount, "kFrameBuffers has one entry per pointer of FrameBuffers");
 
-void frame_table(const FrameBuffers& b, size_t px, Staged (&s)[kFrameBufferCount]) {
+void frame_table(const FrameBuffers& b, size_t px, Staged (&s)[kFrameBufferCount], size_t px_lo = 0) {
     const void* p[kFrameBufferCount];
     std::memcpy(p, &b, sizeof p);
-    for (size_t k = 0; k < kFrameBufferCount; ++k) s[k] = Staged{p[k], px * kFrameBuffers[k].bytes, kFrameBuffers[k].dir};
+    for (size_t k = 0; k < kFrameBufferCount; ++k) s[k] = Staged{p[k], (kFrameBuffers[k].lo ? px_lo : px) * kFrameBuffers[k].bytes, kFrameBuffers[k].dir};
 }
 DsrtAccum accum_of(const FrameBuffers& b) { return DsrtAccum{(uint64_t*)b.sum, (uint64_t*)b.sum_sq}; }
 
 // staged_call over a frame's table: call(the mirrors, by name) -> return code.  `finish`: the device has finished before the results are copied out.
 template <typename Call>
-int staged_frame_call(const FrameBuffers& host, size_t px, bool finish, Call&& call) {
+int staged_frame_call(const FrameBuffers& host, size_t px, bool finish, Call&& call, size_t px_lo = 0) {
     Staged s[kFrameBufferCount];
-    frame_table(host, px, s);
+    frame_table(host, px, s, px_lo);
     return staged_call(s, [&](void* const* d) -> int {
         if (int rc = call(pointers_as<FrameBuffers>(d))) return rc;
         if (finish) HIP_TRY(hipStreamSynchronize(nullptr));
@@ -1502,7 +1510,7 @@ int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* 
     if ((t->prev_camera != nullptr) != (t->prev != nullptr)) return accum_fail(fn, "the previous camera and the previous history go together: both NULL (first frame) or both given");
     if (!t->next) return accum_fail(fn, "the next history is NULL (it is required)");
     if (int rc = check_temporal_params(fn, t->tp)) return rc;
-    return check_frame_table(fn, s, kFrameTemporal, kFrameBufferCount, "the next history, prev_xy or weight overlaps an input or the previous history",
+    return check_frame_table(fn, s, kFrameTemporal, kFrameUpscale, "the next history, prev_xy or weight overlaps an input or the previous history",
                              "the next history, prev_xy or weight overlaps another output", "an output range overlaps the previous history");
 }
 
@@ -1662,6 +1670,147 @@ int dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc
     ctx->tp_camera = camera; ctx->tp_width = desc->width; ctx->tp_height = desc->height;
     ctx->tp_valid = true;
     return DSRT_OK;
+    });
+}
+
+// ---- The upscaler (include/dsrt.h, UPSCALER; upscale_kernel.hip): pack the low-resolution frame, one launch over the output pixels.  It reads the caller's colour,
+// variance and the two rasters' guides and writes the caller's outputs and the context's own five records per low-resolution pixel. ----
+namespace {
+static int check_upscale_params(const char* fn, const DsrtUpscale* up) {
+    if (!up) return accum_fail(fn, "null argument (DsrtUpscale)");
+    if (up->normal_power_log2 < 0 || up->normal_power_log2 > 8) return accum_fail(fn, "normal_power_log2 must be between 0 and 8");
+    if (!(up->sigma_z > 0.0f) || !(up->sigma_a > 0.0f)) return accum_fail(fn, "sigma_z and sigma_a must be > 0");
+    return DSRT_OK;
+}
+
+// The buffers of an upscaler call, device or host form alike: the shared rows are the output raster's.
+static FrameBuffers upscale_buffers(const float* lo_linear, const float* lo_var, const DsrtUpscaleGuides& lo, const DsrtUpscaleGuides& hi, const void* rgb8, const void* f32,
+                                    const void* linear, const void* var, const void* support) {
+    FrameBuffers b{};
+    b.normal = hi.normal; b.position = hi.position; b.albedo = hi.albedo; b.range = hi.range; b.flags = hi.flags;
+    b.rgb8 = rgb8; b.f32 = f32; b.linear = linear; b.var = var; b.support = support;
+    b.lo_linear = lo_linear; b.lo_var = lo_var;
+    b.lo_normal = lo.normal; b.lo_position = lo.position; b.lo_albedo = lo.albedo; b.lo_range = lo.range; b.lo_flags = lo.flags;
+    return b;
+}
+static DsrtUpscaleGuides lo_guides_of(const FrameBuffers& m) { return DsrtUpscaleGuides{(const float*)m.lo_normal, (const float*)m.lo_position, (const float*)m.lo_albedo, (const float*)m.lo_range, (const uint8_t*)m.lo_flags}; }
+static DsrtUpscaleGuides hi_guides_of(const FrameBuffers& m) { return DsrtUpscaleGuides{(const float*)m.normal, (const float*)m.position, (const float*)m.albedo, (const float*)m.range, (const uint8_t*)m.flags}; }
+
+// What of the two rasters' sizes is refused (desc's own is check_frame_desc's).
+static int check_upscale_sizes(const char* fn, int lo_width, int lo_height, int width, int height) {
+    if (lo_width < 2 || lo_height < 2) return accum_fail(fn, "lo_width and lo_height must be >= 2");
+    if (width < lo_width || height < lo_height) return accum_fail(fn, "the output must be at least as large as the low-resolution frame (W >= lo_width, H >= lo_height)");
+    return DSRT_OK;
+}
+
+// Everything dsrt_upscale_guided refuses, before anything is launched or written; the same for the host form's host pointers.
+static int check_upscale(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* lo_linear, const float* lo_var,
+                         const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const DsrtUpscale* up, const uint8_t* rgb8, const float* f32, const float* linear,
+                         const float* var, const float* support) {
+    if (!ctx || !desc || !lo_linear || !lo || !hi || !up) return accum_fail(fn, "null argument");
+    for (const DsrtUpscaleGuides* g : {lo, hi})
+        if (!g->normal || !g->position || !g->albedo || !g->range) return accum_fail(fn, "a guide channel is NULL (normal, position, albedo and range are required; flags is the optional one)");
+    if (int rc = check_frame_desc(fn, desc, false, true)) return rc;
+    if (int rc = check_upscale_sizes(fn, lo_width, lo_height, desc->width, desc->height)) return rc;
+    if (int rc = check_upscale_params(fn, up)) return rc;
+    if (!rgb8 && !f32 && !linear && !var && !support) return accum_fail(fn, "no output");
+    if (var && !lo_var) return accum_fail(fn, "the variance output needs the low-resolution variance (d_lo_var)");
+    Staged s[kFrameBufferCount];
+    frame_table(upscale_buffers(lo_linear, lo_var, *lo, *hi, rgb8, f32, linear, var, support), (size_t)desc->width * desc->height, s, (size_t)lo_width * lo_height);
+    return check_frame_table(fn, s, 0, kFrameBufferCount, "an output range overlaps an input range", "two output ranges overlap", nullptr);
+}
+
+static int upscale_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* d_lo_linear, const float* d_lo_var,
+                        const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const DsrtUpscale* up, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var,
+                        float* d_support, hipStream_t stream) {
+    int rc;
+    if ((rc = check_upscale(fn, ctx, desc, lo_width, lo_height, d_lo_linear, d_lo_var, lo, hi, up, d_rgb8, d_f32, d_linear, d_var, d_support))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px_lo = (size_t)lo_width * lo_height;
+    // (growing frees the old records: the launch that may still read them has to be over first)
+    if (ctx->up_rec[4].n < px_lo && ctx->done_valid) HIP_TRY(hipEventSynchronize(ctx->done));
+    for (DevBuf<float4>& r : ctx->up_rec) if ((rc = r.grow(px_lo))) return rc;
+    const UpscaleRecords rec{ctx->up_rec[0].p, ctx->up_rec[1].p, ctx->up_rec[2].p, ctx->up_rec[3].p, ctx->up_rec[4].p};
+    if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (the denoiser, a G-buffer) comes first
+    HIP_TRY(launch_upscale_pack(d_lo_linear, d_lo_var, lo->normal, lo->position, lo->albedo, lo->range, lo->flags, px_lo, rec, stream));
+    UpscaleArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.cr = rec.cr; a.vf = rec.vf; a.nn = rec.nn; a.xx = rec.xx; a.aa = rec.aa;
+    a.hi_normal = hi->normal; a.hi_position = hi->position; a.hi_albedo = hi->albedo; a.hi_range = hi->range; a.hi_flags = hi->flags;
+    a.out_rgb8 = d_rgb8; a.out_f32 = d_f32; a.out_linear = d_linear; a.out_var = d_var; a.out_support = d_support;
+    a.w = lo_width; a.h = lo_height; a.W = desc->width; a.H = desc->height;
+    a.normal_power_log2 = up->normal_power_log2; a.use_sun = up->use_sun != 0; a.lo_has_flags = lo->flags != nullptr;
+    a.sigma_z = up->sigma_z; a.sigma_a = up->sigma_a; a.inv_gamma = inv_gamma_of(*desc);
+    HIP_TRY(launch_upscale(a, desc->math_mode == 1, stream));
+    return launch_finish(ctx, stream, nullptr);                                      // the records are the context's: its next launch on any stream comes behind
+}
+}  // namespace
+
+void dsrt_upscale_defaults(DsrtUpscale* out) {
+    if (!out) return;
+    out->normal_power_log2 = 5; out->sigma_z = 0.01f; out->sigma_a = 0.1f; out->use_sun = 1;
+}
+
+int dsrt_upscale_guided(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* d_lo_linear, const float* d_lo_var, const DsrtUpscaleGuides* lo,
+                        const DsrtUpscaleGuides* hi, const DsrtUpscale* up, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, float* d_support, void* stream_v) {
+    return dsrt::guarded("dsrt_upscale_guided", [&]() -> int {
+    return upscale_impl("dsrt_upscale_guided", ctx, desc, lo_width, lo_height, d_lo_linear, d_lo_var, lo, hi, up, d_rgb8, d_f32, d_linear, d_var, d_support, (hipStream_t)stream_v);
+    });
+}
+
+int dsrt_upscale_guided_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* h_lo_linear, const float* h_lo_var,
+                                const DsrtUpscaleGuides* h_lo, const DsrtUpscaleGuides* h_hi, const DsrtUpscale* up, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var,
+                                float* h_support) {
+    return dsrt::guarded("dsrt_upscale_guided_to_host", [&]() -> int {
+    const char* fn = "dsrt_upscale_guided_to_host";
+    if (int rc = check_upscale(fn, ctx, desc, lo_width, lo_height, h_lo_linear, h_lo_var, h_lo, h_hi, up, h_rgb8, h_f32, h_linear, h_var, h_support)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const FrameBuffers h = upscale_buffers(h_lo_linear, h_lo_var, *h_lo, *h_hi, h_rgb8, h_f32, h_linear, h_var, h_support);
+    return staged_frame_call(h, (size_t)desc->width * desc->height, true, [&](const FrameBuffers& m) {
+        const DsrtUpscaleGuides lo = lo_guides_of(m), hi = hi_guides_of(m);
+        return upscale_impl(fn, ctx, desc, lo_width, lo_height, (const float*)m.lo_linear, (const float*)m.lo_var, &lo, &hi, up, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
+                            (float*)m.var, (float*)m.support, nullptr);
+    }, (size_t)lo_width * lo_height);
+    });
+}
+
+// The convenience form: the five calls of include/dsrt.h, the low-resolution frame and both rasters' guides on the device for the call.
+int dsrt_render_upscaled_to_host(DsrtContext* ctx, const DsrtRenderDesc* lo_desc, int out_width, int out_height, const DsrtDenoise* denoise, const DsrtUpscale* up,
+                                 uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, uint8_t* h_lo_rgb8, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_upscaled_to_host", [&]() -> int {
+    const char* fn = "dsrt_render_upscaled_to_host";
+    DsrtDenoise dn;
+    dsrt_denoise_defaults(&dn);
+    if (denoise) dn = *denoise; else dn.iterations = 0;
+    int spp, rc;
+    if (!ctx || !lo_desc) return accum_fail(fn, "null argument");
+    DsrtRenderDesc hi_desc = *lo_desc;
+    hi_desc.width = out_width; hi_desc.height = out_height;
+    if ((rc = check_frame_desc(fn, lo_desc, false, true)) || (rc = check_frame_desc(fn, &hi_desc, false, true))) return rc;
+    if ((rc = check_upscale_sizes(fn, lo_desc->width, lo_desc->height, out_width, out_height)) || (rc = check_upscale_params(fn, up))) return rc;
+    if ((rc = check_render_denoised(fn, ctx, lo_desc, &dn, false, nullptr, h_rgb8 || h_f32 || h_linear || h_var, &spp))) return rc;      // (the scene is looked for last)
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px_lo = (size_t)lo_desc->width * (size_t)lo_desc->height, px = (size_t)out_width * (size_t)out_height;
+    FrameScratch f, g;                                                    // f: the low-resolution frame's sums and guides; g: the output raster's guides (its sums are not used)
+    DevBuf<float> lo_linear, lo_var;
+    DevBuf<uint8_t> lo_flags, hi_flags;
+    if ((rc = f.init(px_lo, false, true)) || (rc = lo_linear.alloc(px_lo * 3)) || (rc = lo_var.alloc(px_lo * 3)) || (rc = lo_flags.alloc(px_lo))) return rc;
+    if ((rc = g.normal.alloc(px * 3)) || (rc = g.position.alloc(px * 3)) || (rc = g.albedo.alloc(px * 3)) || (rc = g.range.alloc(px)) || (rc = hi_flags.alloc(px))) return rc;
+    f.gb.flags = lo_flags.p;
+    g.gb.normal = g.normal.p; g.gb.position = g.position.p; g.gb.albedo = g.albedo.p; g.gb.range = g.range.p; g.gb.flags = hi_flags.p;
+    const DsrtUpscaleGuides lo{f.normal.p, f.position.p, f.albedo.p, f.range.p, lo_flags.p}, hi{g.normal.p, g.position.p, g.albedo.p, g.range.p, hi_flags.p};
+    FrameBuffers h{};
+    h.rgb8 = h_rgb8; h.f32 = h_f32; h.linear = h_linear; h.var = h_var; h.lo_rgb8 = h_lo_rgb8;
+    DsrtStats local;
+    return staged_frame_call(h, px, true, [&](const FrameBuffers& m) -> int {
+        int r;
+        if ((r = dsrt_render_accumulate(ctx, lo_desc, 0, spp, 1, &f.acc, nullptr, stats ? stats : &local))) return r;
+        if ((r = dsrt_render_gbuffer(ctx, lo_desc, &f.gb, nullptr, nullptr))) return r;
+        if ((r = dsrt_denoise_accumulated(ctx, lo_desc, &f.acc, spp, nullptr, &f.guides, &dn, (uint8_t*)m.lo_rgb8, nullptr, lo_linear.p, lo_var.p, nullptr))) return r;
+        if ((r = dsrt_render_gbuffer(ctx, &hi_desc, &g.gb, nullptr, nullptr))) return r;
+        return dsrt_upscale_guided(ctx, &hi_desc, lo_desc->width, lo_desc->height, lo_linear.p, lo_var.p, &lo, &hi, up, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
+                                   (float*)m.var, nullptr, nullptr);
+    }, px_lo);
     });
 }
 

@@ -75,4 +75,20 @@ struct TemporalArgs {
 };
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
 
+// upscale_kernel.hip (include/dsrt.h, UPSCALER).  The LOW-resolution frame packed for the taps, one 16-byte record per low-resolution pixel each: {c.rgb, range},
+// {v.rgb, flags as a bit pattern}, {N, 0}, {X, 0}, {A, 0}.  pack fills them (var and flags may be null: zeros); the upscale launch reads them and the OUTPUT
+// resolution's guides as the caller has them, and writes the outputs that are not null.
+struct UpscaleRecords { float4* cr; float4* vf; float4* nn; float4* xx; float4* aa; };
+struct UpscaleArgs {
+    const float4* cr; const float4* vf; const float4* nn; const float4* xx; const float4* aa;
+    const float* hi_normal; const float* hi_position; const float* hi_albedo; const float* hi_range; const uint8_t* hi_flags;
+    uint8_t* out_rgb8; float* out_f32; float* out_linear; float* out_var; float* out_support;
+    int w, h, W, H;                      // low resolution, output resolution
+    int normal_power_log2, use_sun, lo_has_flags;
+    float sigma_z, sigma_a, inv_gamma;
+};
+hipError_t launch_upscale_pack(const float* linear, const float* var, const float* normal, const float* position, const float* albedo, const float* range,
+                               const uint8_t* flags, size_t n_pixels, const UpscaleRecords& r, hipStream_t stream);
+hipError_t launch_upscale(const UpscaleArgs& a, bool device_libm, hipStream_t stream);
+
 }  // namespace dsrt

@@ -160,6 +160,8 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_DENOISE_GUIDES: return sizeof(DsrtDenoiseGuides);
         case DSRT_SIZEOF_DENOISE: return sizeof(DsrtDenoise);
         case DSRT_SIZEOF_TEMPORAL: return sizeof(DsrtTemporal);
+        case DSRT_SIZEOF_UPSCALE_GUIDES: return sizeof(DsrtUpscaleGuides);
+        case DSRT_SIZEOF_UPSCALE: return sizeof(DsrtUpscale);
         default: return 0;
     }
 }

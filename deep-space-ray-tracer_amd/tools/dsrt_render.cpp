@@ -8,7 +8,8 @@
 //   * the scene is flattened, BVH-built and uploaded ONCE; only camera and sun change per frame (the reference
 //     rebuilds and re-uploads everything per frame, :405);
 //   * the output directory is created if missing but never emptied (the reference deletes its contents, :41-50);
-//   * PPM (or PNG with --png): there is no ImageMagick shell-out (:28-36) and no upscaling step (:438-447);
+//   * PPM (or PNG with --png): there is no ImageMagick shell-out (:28-36), and --upscale does not shell out to a learned upscaler (:194-215, :438-447): in
+//     rng_mode 0 the flag is announced as unsupported and ignored; in rng_mode 1 see below;
 //   * --gbuffer also writes each frame's ground truth next to it (include/dsrt.h, dsrt_render_gbuffer): <frame>_range.pfm, <frame>_normal.pfm,
 //     <frame>_mask.pgm (255 where the centre ray hits) and <frame>_sunlit.pgm (255 where that hit sees the Sun).
 //   * rng_mode 1 only: --passes P renders each frame as P interleaved sample sets and writes <frame>_pass<p>of<P> after each (a preview that
@@ -27,6 +28,11 @@
 //     history as it is, and frame i (its index in the pose file) is rendered with seed 1337 + i: the blend takes the frames' noise as independent, which one seed for
 //     all frames would not give.  <frame>_raw is that frame's own samples, undenoised.  --flow also writes <frame>_flow.pfm: per pixel where its surface point was
 //     in the previous frame, as (fx - x, fy - y, 0) in pixels (NaN where it was not in view, and in the first frame) -- optical-flow ground truth.
+//   * rng_mode 1 only: --upscale [S] (S = 2 .. 8, default 4, the reference's default scale) renders each frame at --width x --height and reconstructs it at
+//     S*width x S*height with the G-buffer-guided upscaler (include/dsrt.h, UPSCALER: dsrt_render_upscaled_to_host, the library's default parameters): the
+//     full-resolution G-buffer of the same camera keeps silhouettes, creases, material edges and sun-shadow edges at the output resolution.  Writes <frame> at the
+//     output size and <frame>_lowres, byte for byte the frame the same command writes without --upscale.  With --denoise [ITER] the denoiser runs between the two
+//     steps; --variance writes the upscaled variance as <frame>_var.pfm.  Does not combine with --temporal, --adaptive, --passes or --gbuffer.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -59,6 +65,8 @@ int main(int argc, char** argv) {
     float adaptive_tol = 0.0f, adaptive_floor = 0.0f;
     bool adaptive = false, adaptive_detail = false, denoise = false, temporal = false, flow = false;
     int denoise_iterations = -1;                                    // -1: the library's default
+    bool upscale = false;
+    int upscale_factor = 4;                                         // the reference's scale (src/main.cpp:444)
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -95,10 +103,20 @@ int main(int argc, char** argv) {
         }
         else if (a == "--temporal") temporal = true;                // with --denoise: reprojected frame history (include/dsrt.h, TEMPORAL ACCUMULATION)
         else if (a == "--flow") flow = true;                        // with --temporal: <frame>_flow.pfm, every pixel's displacement from the previous frame
-        else if (a == "--upscale") std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow]\n"); return 2; }
+        else if (a == "--upscale") {                                // rng_mode 1: G-buffer-guided upscaling by the optional factor (include/dsrt.h, UPSCALER)
+            upscale = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') upscale_factor = std::atoi(argv[++i]);
+        }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
+    if (upscale && rng_mode != 1) {                                 // the reference's bytes are not upscaled here: the flag is announced and ignored, as it always was
+        std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
+        upscale = false;
+    }
+    if (upscale && (upscale_factor < 2 || upscale_factor > 8)) { std::fprintf(stderr, "dsrt_render: --upscale S must be between 2 and 8\n"); return 2; }
+    if (upscale && (temporal || adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --upscale does not combine with --temporal / --adaptive / --passes / --gbuffer\n"); return 2; }
+    if (upscale && spp < 2) { std::fprintf(stderr, "dsrt_render: --upscale needs --spp 2 or more\n"); return 2; }
     if (adaptive_detail && !adaptive) { std::fprintf(stderr, "dsrt_render: --adaptive-passes, --adaptive-min-passes and --adaptive-floor need --adaptive TOL\n"); return 2; }
     if (adaptive && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --adaptive needs --rng-mode 1 (or --fast)\n"); return 2; }
     if (adaptive && (passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --adaptive does not combine with --passes / --gbuffer\n"); return 2; }
@@ -192,9 +210,9 @@ int main(int argc, char** argv) {
     };
 
     // The modes that render frame by frame: one step each, over buffers that stay empty where the mode does not use them.
-    const bool host_sums = (denoise && !temporal) || (!denoise && !adaptive && (passes != 0 || variance));
-    std::vector<uint8_t> img(image_bytes), raw(denoise ? image_bytes : 0);
-    std::vector<float> var(variance ? image_bytes : 0);
+    const bool host_sums = !upscale && ((denoise && !temporal) || (!denoise && !adaptive && (passes != 0 || variance)));
+    std::vector<uint8_t> img(image_bytes), raw(denoise && !upscale ? image_bytes : 0);
+    std::vector<float> var(variance && !upscale ? image_bytes : 0);
     std::vector<uint64_t> sum(host_sums ? image_bytes : 0), sq(host_sums && (denoise || variance) ? image_bytes : 0);
     const DsrtAccum acc{sum.data(), sq.empty() ? nullptr : sq.data()};
     auto write_var = [&](const std::string& base) { return !variance || dsrt_write_pfm((base + "_var.pfm").c_str(), var.data(), width, height, 3) == DSRT_OK; };
@@ -246,7 +264,7 @@ int main(int argc, char** argv) {
     };
 
     // --denoise: each frame's sums with second moments, the raw image they resolve to, the G-buffer of its camera, the filter (include/dsrt.h, DENOISER).
-    const bool guided = denoise && !temporal;
+    const bool guided = denoise && !temporal && !upscale;
     std::vector<float> normal(guided ? image_bytes : 0), position(guided ? image_bytes : 0), albedo(guided ? image_bytes : 0), range(guided ? px : 0);
     const DsrtDenoiseGuides guides{normal.data(), position.data(), albedo.data(), range.data()};
     DsrtGBuffer g;
@@ -268,7 +286,7 @@ int main(int argc, char** argv) {
 
     // --passes / --variance: each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
     // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).
-    if (!adaptive && !denoise && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
+    if (!adaptive && !denoise && !upscale && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
         const int P = passes > 0 ? passes : 1;
         std::fill(sum.begin(), sum.end(), 0ull);
         std::fill(sq.begin(), sq.end(), 0ull);
@@ -290,6 +308,25 @@ int main(int argc, char** argv) {
             std::printf("Saved %s_var.pfm\n", base.c_str());
         }
         std::printf("Saved %s%s\n", base.c_str(), ext.c_str());
+        return 0;
+    };
+
+    // --upscale: the frame at --width x --height (denoised with --denoise), both rasters' G-buffers and the guided upscaler, through the convenience form.
+    const int out_w = width * upscale_factor, out_h = height * upscale_factor;
+    const size_t out_values = upscale ? (size_t)out_w * out_h * 3 : 0;
+    std::vector<uint8_t> big(out_values);
+    std::vector<float> big_var(variance ? out_values : 0);
+    DsrtUpscale up;
+    dsrt_upscale_defaults(&up);
+    if (upscale) frame_step = [&](size_t, const std::string& base) -> int {
+        if (dsrt_render_upscaled_to_host(ctx, &d, out_w, out_h, denoise ? &dn : nullptr, &up, big.data(), nullptr, nullptr, variance ? big_var.data() : nullptr, img.data(),
+                                         nullptr) != DSRT_OK) return fail("rendering and upscaling");
+        const std::string path = base + ext;
+        if ((png ? dsrt_write_png(path.c_str(), big.data(), out_w, out_h) : dsrt_write_ppm(path.c_str(), big.data(), out_w, out_h)) != DSRT_OK ||
+            !write_image(base + "_lowres" + ext, img.data())) return fail("writing the frame");
+        if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), big_var.data(), out_w, out_h, 3) != DSRT_OK) return fail("writing the variance");
+        std::printf("upscale: %d x %d -> %d x %d%s\nSaved %s, %s_lowres%s%s\n", width, height, out_w, out_h, denoise ? ", denoised in between" : "", path.c_str(), base.c_str(),
+                    ext.c_str(), variance ? " and _var.pfm" : "");
         return 0;
     };
 

@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -56,6 +56,8 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_DENOISE_GUIDES 12
 #define DSRT_SIZEOF_DENOISE     13
 #define DSRT_SIZEOF_TEMPORAL    14
+#define DSRT_SIZEOF_UPSCALE_GUIDES 15
+#define DSRT_SIZEOF_UPSCALE     16
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -698,6 +700,92 @@ int  dsrt_denoise_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc,
                                    uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, float* h_weight);
 int  dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* params, const DsrtTemporal* temporal, int reset, uint8_t* h_rgb8,
                                            float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, DsrtStats* stats);
+
+/*
+ * UPSCALER (on top of the DENOISER and the G-BUFFER): a full-resolution frame out of a low-resolution render.  Joint bilateral upsampling (Kopf et al. 2007) whose
+ * guides are GROUND TRUTH at the output resolution: the Monte-Carlo radiance is rendered (and denoised) at w x h, the G-buffer -- normal, position, albedo, range and
+ * the sun-visibility bit of every pixel-centre ray, a few milliseconds at 4K -- at W x H, and every output pixel gathers the 4 x 4 low-resolution pixels around it
+ * that lie on its own surface, in its own material and on its own side of the sun's shadow edge.  Silhouettes, creases, material edges and the hard shadows of the
+ * delta light stay at the output resolution.  Like the denoiser it uses correctly rounded fp32 operations only: tests/_upscale_model.py reproduces every bit.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written; dot is the DENOISER's; / and floorf are
+ * the IEEE ones; the constants are float literals.
+ *   Inputs.  Low resolution w x h: linear colour c (3 floats per pixel: the denoiser's d_linear, or a resolved mean), optionally its variance v, the guides N, X, A,
+ *     range, optionally flags (the G-buffer's uint8 channel).  Output resolution W x H, W >= w and H >= h (no integer factor required): the same guides from a G-buffer
+ *     of the SAME camera pose and field of view.  The camera's lower_left_corner / horizontal / vertical do not depend on the image size, so dsrt_render_gbuffer with
+ *     desc->width, height = W, H and the context's unchanged camera is that G-buffer.
+ *   Per output pixel P = (X, Y) (Y the buffer row, 0 the top row), R = range_hi[P]:
+ *     !(R <= FLT_MAX) (a miss, or a NaN): c' = +0, v' = +0, support = +0 -- space stays black and the silhouette is the full-resolution G-buffer's.  Otherwise
+ *     the position in the low-resolution buffer -- the G-buffer's pixel-centre ray parameter u = (x + 0.5) / (W - 1) mapped from one raster to the other:
+ *       fx  = (((float)X + 0.5f) / (float)(W-1)) * (float)(w-1) - 0.5f
+ *       fyk = (((float)(H-1-Y) + 0.5f) / (float)(H-1)) * (float)(h-1) - 0.5f
+ *       fy  = (float)(h-1) - fyk
+ *       x0  = (int)floorf(fx);   y0 = (int)floorf(fy)
+ *     Taps qy = y0-1 .. y0+2 (outer), qx = x0-1 .. x0+2 (inner); a tap outside the low-resolution image is skipped.  Spatial weight, a tent of radius 2 (the sixteen
+ *     weights sum to 4 in exact arithmetic):
+ *       bx = fmaxf(1.0f - 0.5f*fabsf((float)qx - fx), 0.0f);   by likewise with qy and fy;   b = bx*by
+ *     LEVEL 1 (guided).  A tap is also skipped when !(range_q <= FLT_MAX), or -- with use_sun != 0 and both flags arrays given -- when
+ *     ((flags_q ^ flags_P) & DSRT_GB_SUN_VISIBLE) != 0.  For the other taps
+ *       wn  = fmaxf(dot(N_P, N_q), 0.0f);   normal_power_log2 times: wn = wn*wn
+ *       D   = X_q - X_P;   ez = fabsf(dot(N_P, D)) / (sigma_z * R)
+ *       da  = A_q - A_P;   ea2 = dot(da, da) / (sigma_a*sigma_a)
+ *       wt  = (b * wn) / ((1.0f + ez*ez) * (1.0f + ea2))
+ *       sw += wt;   sc.k += wt*c_q.k;   sv.k += (wt*wt)*v_q.k                          (k = r, g, b; all sums start at +0.0f)
+ *     sw > 0:  c'.k = sc.k/sw,  v'.k = sv.k/(sw*sw),  support = sw.
+ *     LEVEL 2 (fallback, when !(sw > 0)).  The same loop and the same quotients over EVERY tap inside the image with wt = b alone -- low-resolution miss pixels count
+ *     too: a partly covered low-resolution pixel still carries light -- and support = +0.  At least one tap is always inside the image with positive weight:
+ *     fx lies in (-0.5, w-1] (X = 0 gives 0.5 (w-1)/(W-1) - 0.5 > -0.5; X = W-1 gives (w-1) - 0.5 (1 - (w-1)/(W-1)) <= w-1), so either x0 >= 0 and tap x0 is
+ *     a column of the image at a distance below 1, weight above 0.5, or x0 = -1 and tap x0+1 = 0 is at a distance below 0.5, weight above 0.75; fy lies in
+ *     [0, h-0.5) and tap y0 is a row of the image, weight above 0.5; a few units in the last place of fx or fy change neither.  So level 2 never divides by zero.
+ *   Outputs.  d_linear = c', d_var = v', d_support = support (one float per pixel: 0 exactly where the miss rule or level 2 applied); d_rgb8 and d_f32 are
+ *     dsrt_resolve_accumulated's tone map and 8-bit store applied to c' (desc->gamma; desc->math_mode chooses powf as it does there).
+ * DELIBERATELY NOT IN: albedo demodulation (divide by the low-resolution albedo, multiply by the full-resolution one).  Every sample is clamped to [0,1] before it is
+ * summed (the reference's src/gpu_render.cu:935) and the sun's radiance is 1e5, so a sunlit pixel's mean is NOT albedo times irradiance, and demodulating it is wrong.
+ * The albedo is an edge-stopping guide only.
+ * Guides must be finite wherever `range` is finite; the call does not check.
+ *
+ * dsrt_upscale_guided: desc gives W, H (width, height), gamma and math_mode (rng_mode must be 1 like everywhere in this family; the sampling fields are ignored);
+ *   lo / hi are the guides at w x h and W x H (flags optional in each); at least one of d_rgb8 (bytes, W*H*3), d_f32, d_linear, d_var (floats, W*H*3) and d_support
+ *   (floats, W*H).  Asynchronous on `stream`; like dsrt_denoise_accumulated it waits for the context's previous launch, the next launch waits for it, it needs no scene,
+ *   and the context's camera, sun and render buffers are left as they were.  Inputs are read only.  Working memory (80 bytes per LOW-resolution pixel: five 16-byte
+ *   records {c, range}, {v, flags}, {N}, {X}, {A}) belongs to the context: allocated on first use, grown for a larger frame, freed by dsrt_ctx_destroy.
+ *   DSRT_ERR_INVALID: what the denoiser refuses of desc (rng_mode != 1, math_mode not 0 or 1, shard_count > 1, W or H < 2, 2^31 pixels); lo_width or lo_height < 2;
+ *   W < lo_width or H < lo_height; a NULL ctx, desc, colour, guide struct, normal / position / albedo / range channel or params; normal_power_log2 outside [0, 8]; a
+ *   sigma that is not > 0 (NaN is refused); no output; d_var without d_lo_var; a pointer not aligned to its element; an output range that overlaps an input range or
+ *   another output.  A refused call touches no buffer.
+ * dsrt_upscale_guided_to_host: the same from HOST buffers into HOST buffers, synchronously.
+ * dsrt_render_upscaled_to_host: the convenience form.  lo_desc plans the low-resolution frame (w x h, spp >= 2, rng_mode 1); in order: lo_desc->spp samples with second
+ *   moments at w x h; the G-buffer at w x h (normal, position, albedo, range, flags); dsrt_denoise_accumulated with `denoise` (NULL = the defaults with iterations 0:
+ *   the plain mean and variance); the G-buffer at out_width x out_height; dsrt_upscale_guided.  The result is exactly that chain of five calls.  h_lo_rgb8 (optional,
+ *   w*h*3 bytes) receives the low-resolution image of the third step: dsrt_render_denoised_to_host's.  DSRT_ERR_NO_SCENE before an upload.  stats (optional): the
+ *   accumulate launch's.
+ * dsrt_upscale_defaults: the denoiser's where the terms are the denoiser's -- normal_power_log2 5, sigma_z 0.01, sigma_a 0.1 -- and use_sun 1.
+ *   The values stayed where they started.  Measured on the CPU model (tests/test_upscale_host.py), MSE over the output pixels that hit against
+ *   256 spp at the output size, relative to bilinear interpolation of the same denoised low-resolution image: station_near 100 x 56 -> 200 x 112 at 16 spp 0.775 (0.880
+ *   with use_sun 0), textured 48 x 32 -> 96 x 64 at 8 spp 0.695 (1.454 with use_sun 0: without the bit the guides concentrate the weight on fewer taps across a shadow
+ *   edge they cannot see, and the result is worse than no guides at all -- use_sun 1 is what makes the default work, and a caller without the flags channel should know).
+ *   Against the same sample budget rendered natively (spp / 4 at the output size, denoised) the upscaled frame's error is 1.70 times on the station, whose trusses are
+ *   thinner than a low-resolution pixel, and 0.80 times in the textured room.  On an MI355X the kernel takes 74 us at 960 x 540 -> 1920 x 1080 and 270 us at
+ *   1920 x 1080 -> 3840 x 2160 (a third of one a-trous iteration at the output size), the call 0.14 and 0.37 ms.
+ */
+typedef struct DsrtUpscaleGuides {   /* DEVICE (HOST for _to_host) buffers, one raster's width*height elements, image order: channels of DsrtGBuffer */
+    const float*   normal;           /* x3 */
+    const float*   position;         /* x3 */
+    const float*   albedo;           /* x3 */
+    const float*   range;            /* x1, +inf on a miss */
+    const uint8_t* flags;            /* optional: DSRT_GB_*; only DSRT_GB_SUN_VISIBLE is looked at */
+} DsrtUpscaleGuides;
+typedef struct DsrtUpscale { int normal_power_log2; float sigma_z, sigma_a; int use_sun; } DsrtUpscale;
+void dsrt_upscale_defaults(DsrtUpscale* out);
+int  dsrt_upscale_guided(DsrtContext* ctx, const DsrtRenderDesc* desc /* width, height = W, H; gamma; math_mode */, int lo_width, int lo_height, const float* d_lo_linear,
+                         const float* d_lo_var /* optional */, const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const DsrtUpscale* params, uint8_t* d_rgb8,
+                         float* d_f32, float* d_linear, float* d_var, float* d_support, void* stream);
+int  dsrt_upscale_guided_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* h_lo_linear, const float* h_lo_var,
+                                 const DsrtUpscaleGuides* h_lo, const DsrtUpscaleGuides* h_hi, const DsrtUpscale* params, uint8_t* h_rgb8, float* h_f32, float* h_linear,
+                                 float* h_var, float* h_support);
+int  dsrt_render_upscaled_to_host(DsrtContext* ctx, const DsrtRenderDesc* lo_desc, int out_width, int out_height, const DsrtDenoise* denoise /* NULL = iterations 0 */,
+                                  const DsrtUpscale* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, uint8_t* h_lo_rgb8 /* optional, w*h*3 */,
+                                  DsrtStats* stats);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
