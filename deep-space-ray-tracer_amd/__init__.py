@@ -38,6 +38,13 @@ def _f3(v):
     return (C.c_float * 3)(float(v[0]), float(v[1]), float(v[2]))
 
 
+def _poses(poses):
+    p = np.ascontiguousarray(poses, dtype=np.float32)
+    if p.size % 12:
+        raise ValueError("poses: 12 floats per body")
+    return p.reshape(-1, 12)
+
+
 class HostScene:
     """Flattened scene + BVH on the host (DsrtHostScene)."""
 
@@ -88,13 +95,41 @@ class HostScene:
             _check(lib.dsrt_host_scene_build_bvh(self._h), "dsrt_host_scene_build_bvh")
         elif kind == "sah":
             _check(lib.dsrt_host_scene_build_bvh_sah(self._h), "dsrt_host_scene_build_bvh_sah")
+        elif kind == "bodies":                       # one subtree per body under a chain of top nodes (include/dsrt.h, MOVABLE RIGID BODIES)
+            _check(lib.dsrt_host_scene_build_bvh_bodies(self._h), "dsrt_host_scene_build_bvh_bodies")
         elif kind == "lbvh":                         # built on the GPU (device 0 unless set_lbvh_device says otherwise)
             ms, tot = C.c_float(), C.c_float()
             _check(lib.dsrt_host_scene_build_bvh_gpu(self._h, int(getattr(self, "lbvh_device", 0)), C.byref(ms), C.byref(tot)), "dsrt_host_scene_build_bvh_gpu")
             self.lbvh_build_ms, self.lbvh_total_ms = ms.value, tot.value
         else:
-            raise ValueError("build_bvh kind must be 'median', 'sah' or 'lbvh'")
+            raise ValueError("build_bvh kind must be 'median', 'sah', 'lbvh' or 'bodies'")
         self._built = True
+        return self
+
+    def begin_body(self):
+        """Start a movable body (dsrt_host_scene_begin_body): triangles added from now on belong to it.  Returns its index, 1 .. 15."""
+        b = lib.dsrt_host_scene_begin_body(self._h)
+        if b < 0:
+            _check(b, "dsrt_host_scene_begin_body")
+        return b
+
+    @property
+    def body_count(self):
+        return lib.dsrt_host_scene_body_count(self._h)
+
+    def body_range(self, body):
+        """(first triangle, number of triangles) of a body."""
+        first, n = C.c_int(), C.c_int()
+        _check(lib.dsrt_host_scene_body_range(self._h, int(body), C.byref(first), C.byref(n)), "dsrt_host_scene_body_range")
+        return first.value, n.value
+
+    def build_bvh_bodies(self):
+        return self.build_bvh("bodies")
+
+    def set_body_poses(self, first_body, poses):
+        """The CPU statement of Context.set_body_poses: `poses` is (count, 12) float32, row-major 3x4 [R | t], applied to the REST pose."""
+        p = _poses(poses)
+        _check(lib.dsrt_host_scene_set_body_poses(self._h, int(first_body), int(p.shape[0]), p.ctypes.data if p.size else None), "dsrt_host_scene_set_body_poses")
         return self
 
     @property
@@ -379,6 +414,43 @@ class Context:
 
     def upload_device(self, scene_device_view):
         _check(lib.dsrt_scene_upload_device(self._h, C.byref(scene_device_view)), "dsrt_scene_upload_device")
+
+    def upload_bodies(self, host_scene, frame):
+        """Upload a HostScene that carries the bodies tree and keep resident what set_body_poses needs (dsrt_scene_upload_bodies); `frame` is a GPUScene that
+        supplies camera, params and Sun (e.g. host_scene.view(camera, sun))."""
+        _check(lib.dsrt_scene_upload_bodies(self._h, host_scene._h, C.byref(frame)), "dsrt_scene_upload_bodies")
+
+    @property
+    def body_count(self):
+        return lib.dsrt_ctx_body_count(self._h)
+
+    def set_body_poses(self, first_body, poses, stream=None, want_ms=False):
+        """Pose bodies first_body ... of the resident scene on the device (dsrt_scene_set_body_poses; synchronous).  want_ms: returns (total, transform, refit, chain) ms."""
+        p = _poses(poses)
+        ms = C.c_float()
+        _check(lib.dsrt_scene_set_body_poses(self._h, int(first_body), int(p.shape[0]), p.ctypes.data if p.size else None, C.c_void_p(stream) if stream else None,
+                                             C.byref(ms) if want_ms else None), "dsrt_scene_set_body_poses")
+        if not want_ms:
+            return None
+        split = (C.c_float * 3)()
+        _check(lib.dsrt_ctx_body_update_ms(self._h, split), "dsrt_ctx_body_update_ms")
+        return (ms.value, *split)
+
+    def read_scene_words(self, array, first_word=0, n_words=None):
+        """Test hook (dsrt_selftest_read_scene_words): 32-bit words of a resident array -- 0 node records, 1 triangle pair records, 2 shading records.
+        n_words None: everything from first_word on."""
+        if n_words is None:                          # (out = NULL: the hook only says whether the range lies inside the array)
+            inside = lambda n: lib.dsrt_selftest_read_scene_words(self._h, int(array), int(first_word), n, None) == 0
+            lo, hi = 0, 1
+            while inside(hi):
+                lo, hi = hi, hi * 2
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (mid, hi) if inside(mid) else (lo, mid)
+            n_words = lo
+        out = np.zeros(int(n_words), np.uint32)
+        _check(lib.dsrt_selftest_read_scene_words(self._h, int(array), int(first_word), int(n_words), out.ctypes.data), "dsrt_selftest_read_scene_words")
+        return out
 
     def set_camera_sun(self, camera, sun_dir):
         _check(lib.dsrt_scene_set_camera_sun(self._h, C.byref(camera), _f3(sun_dir)), "dsrt_scene_set_camera_sun")

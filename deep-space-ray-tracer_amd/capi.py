@@ -142,6 +142,7 @@ class DsrtUpscale(C.Structure):
     _fields_ = [("normal_power_log2", C.c_int), ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("use_sun", C.c_int)]
 
 
+MAX_BODIES = 16                                                         # DSRT_MAX_BODIES of include/dsrt.h
 HISTORY_FLOATS = 16                                                     # per pixel of a temporal history buffer (include/dsrt.h, TEMPORAL ACCUMULATION)
 
 # The ray-query channels (include/dsrt.h, dsrt_trace_rays): name -> (numpy dtype, components per ray), in DsrtRayHits' order.
@@ -176,6 +177,8 @@ EXPORTS = [
     "dsrt_denoise_defaults", "dsrt_denoise_accumulated", "dsrt_denoise_accumulated_to_host", "dsrt_render_denoised_to_host",
     "dsrt_temporal_defaults", "dsrt_denoise_temporal", "dsrt_denoise_temporal_to_host", "dsrt_render_denoised_temporal_to_host",
     "dsrt_upscale_defaults", "dsrt_upscale_guided", "dsrt_upscale_guided_to_host", "dsrt_render_upscaled_to_host",
+    "dsrt_host_scene_begin_body", "dsrt_host_scene_body_count", "dsrt_host_scene_body_range", "dsrt_host_scene_build_bvh_bodies", "dsrt_host_scene_set_body_poses",
+    "dsrt_scene_upload_bodies", "dsrt_scene_set_body_poses", "dsrt_ctx_body_count", "dsrt_ctx_body_update_ms", "dsrt_selftest_read_scene_words",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -291,6 +294,16 @@ def load():
     sig("dsrt_upscale_guided", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp, vp])
     sig("dsrt_upscale_guided_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp])
     sig("dsrt_render_upscaled_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, P(DsrtDenoise), P(DsrtUpscale), vp, vp, vp, vp, vp, P(DsrtStats)])
+    sig("dsrt_host_scene_begin_body", C.c_int, [vp])
+    sig("dsrt_host_scene_body_count", C.c_int, [vp])
+    sig("dsrt_host_scene_body_range", C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int)])
+    sig("dsrt_host_scene_build_bvh_bodies", C.c_int, [vp])
+    sig("dsrt_host_scene_set_body_poses", C.c_int, [vp, C.c_int, C.c_int, vp])
+    sig("dsrt_scene_upload_bodies", C.c_int, [vp, vp, P(GPUScene)])
+    sig("dsrt_scene_set_body_poses", C.c_int, [vp, C.c_int, C.c_int, vp, vp, P(C.c_float)])
+    sig("dsrt_ctx_body_count", C.c_int, [vp])
+    sig("dsrt_ctx_body_update_ms", C.c_int, [vp, P(C.c_float)])
+    sig("dsrt_selftest_read_scene_words", C.c_int, [vp, C.c_int, C.c_size_t, C.c_size_t, vp])
     sig("dsrt_selftest_math", C.c_int, [vp, C.c_int, vp, C.c_float, vp, C.c_int])
     sig("dsrt_selftest_devkat", C.c_int, [vp, C.c_int, vp, vp, C.c_int])
     sig("dsrt_selftest_philox", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp])

@@ -245,6 +245,7 @@ extern "C" int dsrt_host_scene_build_bvh_gpu(DsrtHostScene* hs, int device, floa
         hs->tri_indices.clear();
         hs->nodes.clear();
         hs->bvh_height = 0;
+        hs->bodies_tree = false;
         hs->bvh_valid = false;
         const size_t n = hs->tris.size();
         if (n == 0) { hs->bvh_valid = true; if (build_ms) *build_ms = 0; if (total_ms) *total_ms = 0; return DSRT_OK; }

@@ -77,6 +77,21 @@ struct FrameState {
 };
 FrameState frame_of(const GPUScene& s) { return FrameState{s.camera, s.sun_dir, s.sun_radiance, s.sun_enabled ? 1 : 0}; }
 
+// What dsrt_scene_upload_bodies keeps resident beside the scene for dsrt_scene_set_body_poses (launchers.h, BodiesView; layout: DESIGN.md).
+struct BodiesResident {
+    int n_bodies = 0;
+    DevBuf<float4> rest_v, rest_n, pair_box;
+    DevBuf<float> poses, pads, root_box;
+    DevBuf<int2> refit;
+    DevBuf<int4> chain;
+    std::vector<int> entry_start;                  // n_bodies + 1: body b's movable entries are [entry_start[b], entry_start[b + 1])
+    std::vector<int2> depth_range;                 // {first, count} into `refit`, one per depth that has movable records, deepest first
+    BodiesView view{};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float last_ms[3] = {0, 0, 0};
+    ~BodiesResident() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 // The scene in traversal layout, owning its device memory.
 struct PackedScene {
     DevBuf<float4> pairs, tri_pairs, tri_shade, tri_uv, tri_cert, materials;
@@ -91,6 +106,7 @@ struct PackedScene {
     float scene_extent = 0.0f, scene_centre[3] = {0, 0, 0};
     bool lean = false;              // no spheres, no textures, Lambertian materials only: the production launches use the kernels' LEAN instantiation (path_machine.h)
     bool valid = false;
+    std::unique_ptr<BodiesResident> bodies;   // uploaded with dsrt_scene_upload_bodies
 };
 
 float4 as_f4(float a, float b, float c, float d) { return make_float4(a, b, c, d); }
@@ -121,9 +137,14 @@ struct PackArrays {
     std::vector<int2> big;
 };
 
+// What pack_tree knows about where things went, for a caller that asks (dsrt_scene_upload_bodies): per node record its node and depth, per pair record its one or
+// two source triangles (-1 = none).  A leaf's first pair record is in its reference.
+struct PackReport { std::vector<int> record_node, record_depth; std::vector<int2> pair_src; };
+
 // Appends the tree (nodes, tri_indices) over the scene's triangles.  Validates every index the kernel will follow, so the fast (unchecked) kernel build never sees
 // an out-of-range reference.  `cert_boxes` (null, or 6 floats per TRIANGLE): appended per slot to arr.cert -- the certified second tree's records.
-int pack_tree(const GPUScene& h, const GPUBVHNode* nodes, int M, const int* tri_indices, int n_indexed, bool textured, const float* cert_boxes, PackArrays& arr, PackedTree& out) {
+int pack_tree(const GPUScene& h, const GPUBVHNode* nodes, int M, const int* tri_indices, int n_indexed, bool textured, const float* cert_boxes, PackArrays& arr, PackedTree& out,
+              PackReport* report = nullptr) {
     const int N = h.num_triangles;
     for (int i = 0; i < n_indexed; ++i) if (tri_indices[i] < 0 || tri_indices[i] >= N) { set_error("tri_indices entry out of range"); return DSRT_ERR_INVALID; }
     // internal node -> slot in `pairs`, assigned in a depth-first walk from the root (also detects cycles / sharing)
@@ -182,6 +203,7 @@ int pack_tree(const GPUScene& h, const GPUBVHNode* nodes, int M, const int* tri_
             arr.isect.push_back(as_f4(q[0][4], q[1][4], q[0][5], q[1][5]));
             arr.isect.push_back(as_f4(q[0][6], q[1][6], q[0][7], q[1][7]));
             arr.isect.push_back(as_f4(q[0][8], q[1][8], 0.0f, 0.0f));
+            if (report) report->pair_src.push_back(make_int2(tri_indices[n.tri_offset + i], i + 1 < n.tri_count ? tri_indices[n.tri_offset + i + 1] : -1));
         }
         return first_pair;
     };
@@ -206,6 +228,7 @@ int pack_tree(const GPUScene& h, const GPUBVHNode* nodes, int M, const int* tri_
         rec[3] = as_f4(bits(ref_left), bits(ref_right), l.bbox_min.x + l.bbox_max.x, r.bbox_min.x + r.bbox_max.x);   // the x sums of the ordering test, in float as the kernel would form them
     }
     arr.depth_of_all.insert(arr.depth_of_all.end(), depth_of.begin(), depth_of.end());
+    if (report) { report->record_node = order; report->record_depth = depth_of; }
     const GPUBVHNode& root = nodes[0];
     out.lo[0] = root.bbox_min.x; out.lo[1] = root.bbox_min.y; out.lo[2] = root.bbox_min.z;
     out.hi[0] = root.bbox_max.x; out.hi[1] = root.bbox_max.y; out.hi[2] = root.bbox_max.z;
@@ -215,7 +238,7 @@ int pack_tree(const GPUScene& h, const GPUBVHNode* nodes, int M, const int* tri_
 }
 
 // Host-side conversion of reference-layout arrays into the traversal layout.  `second_tree`: also build and pack the certified second tree (below).
-int pack_scene(const GPUScene& h, PackedScene& out, bool second_tree) {
+int pack_scene(const GPUScene& h, PackedScene& out, bool second_tree, PackReport* report = nullptr) {
     const int N = h.num_triangles, M = h.num_bvh_nodes;
     if (N < 0 || M < 0 || h.num_spheres < 0 || h.num_materials < 0 || h.num_textures < 0 || h.texture_pool_floats < 0) {
         set_error("scene has a negative count"); return DSRT_ERR_INVALID;
@@ -264,7 +287,7 @@ int pack_scene(const GPUScene& h, PackedScene& out, bool second_tree) {
                 for (int a = 0; a < 3; ++a) out.scene_centre[a] = 0.5f * ((&root.bbox_min.x)[a] + (&root.bbox_max.x)[a]);
             }
         }
-        int rc = pack_tree(h, h.bvh_nodes, M, h.tri_indices, N, textured, nullptr, arr, ref_tree);
+        int rc = pack_tree(h, h.bvh_nodes, M, h.tri_indices, N, textured, nullptr, arr, ref_tree, report);
         if (rc) return rc;
         for (int a = 0; a < 3; ++a) { v.root_lo[a] = ref_tree.lo[a]; v.root_hi[a] = ref_tree.hi[a]; v.accel_root_lo[a] = acc_tree.lo[a]; v.accel_root_hi[a] = acc_tree.hi[a]; }
         v.root_ref = ref_tree.root_ref;
@@ -361,14 +384,114 @@ struct DsrtContext {
 namespace {
 
 // A fresh PackedScene for this context (clones made earlier keep the one they share until they are re-cloned or destroyed).
-int install_scene(DsrtContext* ctx, const GPUScene& host_layout) {
+int build_bodies(const DsrtHostScene& hs, const PackReport& rep, PackedScene& sc);
+
+// `bodies`: the host scene with the bodies tree that `host_layout` views (dsrt_scene_upload_bodies): no second tree, and the resident data of a pose update.
+int install_scene(DsrtContext* ctx, const GPUScene& host_layout, const DsrtHostScene* bodies = nullptr) {
     auto fresh = std::make_shared<PackedScene>();
     ctx->scene.reset();
-    const int rc = pack_scene(host_layout, *fresh, ctx->want_second_tree);
+    PackReport report;
+    int rc = pack_scene(host_layout, *fresh, ctx->want_second_tree && !bodies, bodies ? &report : nullptr);
     if (rc) return rc;
+    if (bodies && (rc = build_bodies(*bodies, report, *fresh))) return rc;
     ctx->scene = std::move(fresh);
     ctx->frame = ctx->scene->frame;
     ctx->tp_valid = false;                         // a new scene: the temporal history of the old one is void
+    return DSRT_OK;
+}
+
+static_assert(kMaxBodies == DSRT_MAX_BODIES, "launchers.h and include/dsrt.h disagree on the number of bodies");
+
+// What a pose update needs resident, from the host scene's bodies tree and from where pack_tree put its nodes and triangles.
+int build_bodies(const DsrtHostScene& hs, const PackReport& rep, PackedScene& sc) {
+    auto bd = std::make_unique<BodiesResident>();
+    const int B = (int)hs.body_start.size();
+    const int M = (int)hs.nodes.size(), N = (int)hs.tris.size();
+    bd->n_bodies = B;
+    auto body_of_tri = [&](int t) { int b = 0; while (b + 1 < B && hs.body_start[b + 1] <= t) ++b; return b; };
+    std::vector<int> node_body(M, -1), root_body_of(M, -1);                 // -1: a top node of the chain
+    for (int b = 0; b < B; ++b) {
+        if (hs.body_root[b] < 0) continue;
+        root_body_of[hs.body_root[b]] = b;
+        for (int i = 0; i < hs.body_nodes[b]; ++i) node_body[hs.body_root[b] + i] = b;
+    }
+    // movable entries, by body and then by pair record; the box of every pair record as the scene stands
+    const size_t P = rep.pair_src.size();
+    const int first_movable = B > 1 ? hs.body_start[1] : N;
+    std::vector<std::vector<int>> by_body(B);
+    std::vector<float4> box(2 * P);
+    for (size_t pr = 0; pr < P; ++pr) {
+        const int2 src = rep.pair_src[pr];
+        float lo[3], hi[3];
+        for (int w = 0; w < 2; ++w) {
+            const int t = w ? src.y : src.x;
+            if (t < 0) continue;
+            const float* v = &hs.tris[t].v0.x;
+            for (int k = 0; k < 3; ++k)
+                for (int a = 0; a < 3; ++a) {
+                    const float c = v[3 * k + a];
+                    if (w == 0 && k == 0) lo[a] = hi[a] = c; else { lo[a] = fminf(lo[a], c); hi[a] = fmaxf(hi[a], c); }
+                }
+        }
+        box[2 * pr] = as_f4(lo[0], lo[1], lo[2], 0.0f);
+        box[2 * pr + 1] = as_f4(hi[0], hi[1], hi[2], 0.0f);
+        const int b = body_of_tri(src.x);
+        if (b >= 1) by_body[b].push_back((int)pr);
+    }
+    std::vector<float4> rest_v, rest_n;
+    bd->entry_start.assign(B + 1, 0);
+    for (int b = 1; b < B; ++b) {
+        bd->entry_start[b] = (int)(rest_v.size() / 5);
+        for (int pr : by_body[b]) {
+            const int2 src = rep.pair_src[pr];
+            float v[20] = {0}, nrm[20] = {0};
+            for (int w = 0; w < 2; ++w) {
+                const int t = w ? src.y : src.x;
+                if (t < 0) continue;
+                const float* r = &hs.rest[((size_t)t - first_movable) * 18];
+                std::memcpy(v + 9 * w, r, 9 * sizeof(float));
+                std::memcpy(nrm + 9 * w, r + 9, 9 * sizeof(float));
+            }
+            v[18] = bits(pr);
+            v[19] = bits(b | (src.y >= 0 ? 256 : 0));
+            for (int q = 0; q < 5; ++q) { rest_v.push_back(as_f4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3])); rest_n.push_back(as_f4(nrm[4 * q], nrm[4 * q + 1], nrm[4 * q + 2], nrm[4 * q + 3])); }
+        }
+    }
+    bd->entry_start[B] = (int)(rest_v.size() / 5);
+    if (B > 1) bd->entry_start[0] = bd->entry_start[1];
+    // the internal records of the movable subtrees, deepest first; where the chain's nodes went
+    std::vector<int> record_of(M, -1);
+    int deepest = 0;
+    for (size_t r = 0; r < rep.record_node.size(); ++r) { record_of[rep.record_node[r]] = (int)r; deepest = std::max(deepest, rep.record_depth[r]); }
+    std::vector<int2> refit;
+    for (int d = deepest; d >= 0; --d) {
+        const int first = (int)refit.size();
+        for (size_t r = 0; r < rep.record_node.size(); ++r)
+            if (rep.record_depth[r] == d && node_body[rep.record_node[r]] >= 1) refit.push_back(make_int2((int)r, node_body[rep.record_node[r]]));
+        if ((int)refit.size() > first) bd->depth_range.push_back(make_int2(first, (int)refit.size() - first));
+    }
+    std::vector<int4> chain;
+    for (int c : hs.chain) {
+        const GPUBVHNode& n = hs.nodes[c];
+        chain.push_back(make_int4(record_of[c], root_body_of[n.left], std::max(root_body_of[n.right], 0), 0));
+    }
+    std::vector<float> pads(kMaxBodies, 0.0f), poses(kMaxBodies * 12, 0.0f);
+    for (int b = 0; b < B; ++b) pads[b] = hs.body_pad[b];
+    for (int b = 0; b < kMaxBodies; ++b) poses[12 * b] = poses[12 * b + 5] = poses[12 * b + 10] = 1.0f;
+    int rc;
+    if ((rc = bd->rest_v.upload(rest_v)) || (rc = bd->rest_n.upload(rest_n)) || (rc = bd->pair_box.upload(box)) || (rc = bd->poses.upload(poses)) || (rc = bd->pads.upload(pads)) ||
+        (rc = bd->refit.upload(refit)) || (rc = bd->chain.upload(chain)) || (rc = bd->root_box.alloc(6))) return rc;
+    for (hipEvent_t& e : bd->ev) HIP_TRY(hipEventCreate(&e));
+    BodiesView& v = bd->view;
+    v.pairs = sc.pairs.p; v.tri_pairs = sc.tri_pairs.p; v.tri_shade = sc.tri_shade.p; v.big_leaves = sc.big_leaves.p;
+    v.rest_v = bd->rest_v.p; v.rest_n = bd->rest_n.p; v.pair_box = bd->pair_box.p; v.poses = bd->poses.p; v.pads = bd->pads.p;
+    v.refit = bd->refit.p; v.chain = bd->chain.p; v.root_box = bd->root_box.p;
+    v.n_chain = (int)chain.size();
+    v.root_ref = sc.view.root_ref;
+    v.root_body = 0;
+    if (chain.empty()) for (int b = 0; b < B; ++b) if (hs.body_root[b] >= 0) v.root_body = b;
+    v.num_pairs = sc.view.num_pairs; v.num_tri_pairs = sc.view.num_tri_pairs; v.num_big_leaves = sc.view.num_big_leaves;
+    sc.bodies = std::move(bd);
     return DSRT_OK;
 }
 
@@ -724,6 +847,67 @@ int dsrt_scene_set_camera_sun(DsrtContext* ctx, const GPUCamera* cam, const floa
     if (!resident_scene(ctx, "dsrt_scene_set_camera_sun")) return DSRT_ERR_NO_SCENE;
     ctx->frame.camera = *cam;
     if (sun_dir_model) ctx->frame.sun_dir = DsrtF3{sun_dir_model[0], sun_dir_model[1], sun_dir_model[2]};
+    return DSRT_OK;
+}
+
+int dsrt_scene_upload_bodies(DsrtContext* ctx, const DsrtHostScene* hs, const GPUScene* frame) {
+    return dsrt::guarded("dsrt_scene_upload_bodies", [&]() -> int {
+    if (!ctx || !hs || !frame) { set_error("dsrt_scene_upload_bodies: null argument"); return DSRT_ERR_INVALID; }
+    if (!hs->bvh_valid || !hs->bodies_tree) { set_error("dsrt_scene_upload_bodies: the scene's tree is not the bodies tree (dsrt_host_scene_build_bvh_bodies)"); return DSRT_ERR_INVALID; }
+    GPUScene s = *frame, g;                        // camera, params, Sun (and sky, seed) from `frame`, every array from the host scene
+    int rc = dsrt_host_scene_view(hs, &g);
+    if (rc) return rc;
+    s.spheres = g.spheres; s.num_spheres = g.num_spheres;
+    s.triangles = g.triangles; s.tri_indices = g.tri_indices; s.num_triangles = g.num_triangles;
+    s.bvh_nodes = g.bvh_nodes; s.num_bvh_nodes = g.num_bvh_nodes; s.bvh_tri_indices = g.bvh_tri_indices;
+    s.materials = g.materials; s.num_materials = g.num_materials;
+    s.textures = g.textures; s.num_textures = g.num_textures;
+    s.texture_pool = g.texture_pool; s.texture_pool_floats = g.texture_pool_floats;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return install_scene(ctx, s, hs);
+    });
+}
+
+int dsrt_ctx_body_count(const DsrtContext* ctx) { const PackedScene* sc = scene_of(ctx); return sc && sc->bodies ? sc->bodies->n_bodies : 0; }
+
+int dsrt_ctx_body_update_ms(const DsrtContext* ctx, float ms[3]) {
+    const PackedScene* sc = scene_of(ctx);
+    if (!sc || !sc->bodies || !ms) { set_error("dsrt_ctx_body_update_ms: no scene with bodies, or null argument"); return DSRT_ERR_INVALID; }
+    for (int i = 0; i < 3; ++i) ms[i] = sc->bodies->last_ms[i];
+    return DSRT_OK;
+}
+
+int dsrt_scene_set_body_poses(DsrtContext* ctx, int first_body, int count, const float* poses, void* stream_v, float* ms) {
+    if (!ctx) { set_error("dsrt_scene_set_body_poses: null context"); return DSRT_ERR_INVALID; }
+    if (!resident_scene(ctx, "dsrt_scene_set_body_poses")) return DSRT_ERR_NO_SCENE;
+    PackedScene& sc = *ctx->scene;
+    if (!sc.bodies) { set_error("dsrt_scene_set_body_poses: the resident scene has no bodies (dsrt_scene_upload_bodies)"); return DSRT_ERR_INVALID; }
+    BodiesResident& bd = *sc.bodies;
+    const int rc = check_body_poses(bd.n_bodies, first_body, count, poses, "dsrt_scene_set_body_poses");
+    if (rc) return rc;
+    if (ms) *ms = 0.0f;
+    if (!count) return DSRT_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->done_valid) HIP_TRY(hipStreamWaitEvent(stream, ctx->done, 0));
+    HIP_TRY(hipMemcpyAsync(bd.poses.p + 12 * (size_t)first_body, poses, 12 * (size_t)count * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (ms) HIP_TRY(hipEventRecord(bd.ev[0], stream));
+    const int e0 = bd.entry_start[first_body], e1 = bd.entry_start[first_body + count];
+    HIP_TRY(launch_bodies_transform(bd.view, e0, e1 - e0, stream));
+    if (ms) HIP_TRY(hipEventRecord(bd.ev[1], stream));
+    for (const int2& r : bd.depth_range) HIP_TRY(launch_bodies_refit(bd.view, r.x, r.y, stream));
+    if (ms) HIP_TRY(hipEventRecord(bd.ev[2], stream));
+    HIP_TRY(launch_bodies_chain(bd.view, stream));
+    if (ms) HIP_TRY(hipEventRecord(bd.ev[3], stream));
+    float root[6];
+    HIP_TRY(hipMemcpyAsync(root, bd.root_box.p, sizeof root, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int a = 0; a < 3; ++a) { sc.view.root_lo[a] = root[a]; sc.view.root_hi[a] = root[3 + a]; }
+    ctx->tp_valid = false;                         // the temporal history assumed the scene as it was
+    if (ms) {
+        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&bd.last_ms[i], bd.ev[i], bd.ev[i + 1]));
+        HIP_TRY(hipEventElapsedTime(ms, bd.ev[0], bd.ev[3]));
+    }
     return DSRT_OK;
 }
 
@@ -1914,6 +2098,20 @@ int dsrt_selftest_poke_node_word(DsrtContext* ctx, size_t word_index, uint32_t v
     uint32_t* w = reinterpret_cast<uint32_t*>(ctx->scene->pairs.p) + word_index;
     if (old_value) HIP_TRY(hipMemcpy(old_value, w, 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(w, &value, 4, hipMemcpyHostToDevice));
+    return DSRT_OK;
+}
+
+int dsrt_selftest_read_scene_words(DsrtContext* ctx, int array, size_t first_word, size_t n_words, uint32_t* out) {
+    if (!resident_scene(ctx, "dsrt_selftest_read_scene_words")) return DSRT_ERR_NO_SCENE;
+    const PackedScene& sc = *ctx->scene;
+    if (array < 0 || array > 2) { set_error("dsrt_selftest_read_scene_words: no such array"); return DSRT_ERR_INVALID; }
+    const DevBuf<float4>& buf = array == 0 ? sc.pairs : array == 1 ? sc.tri_pairs : sc.tri_shade;
+    const size_t words = buf.n * 4;
+    if (first_word > words || n_words > words - first_word) { set_error("dsrt_selftest_read_scene_words: range beyond the array"); return DSRT_ERR_INVALID; }
+    if (!out || !n_words) return DSRT_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, reinterpret_cast<const uint32_t*>(buf.p) + first_word, n_words * 4, hipMemcpyDeviceToHost));
     return DSRT_OK;
 }
 

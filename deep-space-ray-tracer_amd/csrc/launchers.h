@@ -91,4 +91,25 @@ hipError_t launch_upscale_pack(const float* linear, const float* var, const floa
                                const uint8_t* flags, size_t n_pixels, const UpscaleRecords& r, hipStream_t stream);
 hipError_t launch_upscale(const UpscaleArgs& a, bool device_libm, hipStream_t stream);
 
+// bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES).  What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
+// dsrt_scene_upload_bodies made resident beside them.  A movable ENTRY is a pair record of tri_pairs that holds triangles of a body >= 1; entries are sorted by body.
+constexpr int kMaxBodies = 16;             // DSRT_MAX_BODIES
+struct BodiesView {
+    float4* pairs; float4* tri_pairs; float4* tri_shade;     // the resident scene's (device_layout.h)
+    const int2* big_leaves;
+    const float4* rest_v;      // per entry, 5 x float4: A's v0 v1 v2 (9 floats), B's (9 floats), the pair record's index, body | (has a B triangle) << 8 -- as int bits
+    const float4* rest_n;      // per entry, 5 x float4: A's n0 n1 n2, B's, two unused
+    float4* pair_box;          // per pair record of the WHOLE scene, 2 x float4: (lo.xyz, -) (hi.xyz, -) of its one or two triangles, unpadded; the static ones are filled at upload
+    const float* poses;        // kMaxBodies x 12
+    const float* pads;         // kMaxBodies
+    const int2* refit;         // {node record, body} of every internal node of a movable subtree, deepest depth first
+    const int4* chain;         // {node record, body of the left child, body of the right child or 0 where that is the next top node, -}, T0 first
+    float* root_box;           // 6 floats: lo, hi of the scene
+    int n_chain, root_ref, root_body;
+    int num_pairs, num_tri_pairs, num_big_leaves;
+};
+hipError_t launch_bodies_transform(const BodiesView& b, int first_entry, int entries, hipStream_t stream);
+hipError_t launch_bodies_refit(const BodiesView& b, int first, int count, hipStream_t stream);       // a range of BodiesView::refit: one depth
+hipError_t launch_bodies_chain(const BodiesView& b, hipStream_t stream);
+
 }  // namespace dsrt

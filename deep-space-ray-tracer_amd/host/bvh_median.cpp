@@ -28,7 +28,7 @@
 
 namespace {
 
-struct Box { float lo[3], hi[3]; };
+using Box = dsrt::TriBox;
 
 constexpr int kParallelMin = 1 << 15;       // ranges smaller than this are not worth a thread
 
@@ -115,29 +115,36 @@ struct Builder {
 
 }  // namespace
 
+void dsrt::median_tri_box(const GPUTriangle& t, TriBox& b, float centroid[3]) {
+    const float vx[3] = {t.v0.x, t.v1.x, t.v2.x}, vy[3] = {t.v0.y, t.v1.y, t.v2.y}, vz[3] = {t.v0.z, t.v1.z, t.v2.z};
+    b.lo[0] = fminf(fminf(vx[0], vx[1]), vx[2]); b.hi[0] = fmaxf(fmaxf(vx[0], vx[1]), vx[2]);
+    b.lo[1] = fminf(fminf(vy[0], vy[1]), vy[2]); b.hi[1] = fmaxf(fmaxf(vy[0], vy[1]), vy[2]);
+    b.lo[2] = fminf(fminf(vz[0], vz[1]), vz[2]); b.hi[2] = fmaxf(fmaxf(vz[0], vz[1]), vz[2]);
+    centroid[0] = (vx[0] + vx[1] + vx[2]) / 3.f;
+    centroid[1] = (vy[0] + vy[1] + vy[2]) / 3.f;
+    centroid[2] = (vz[0] + vz[1] + vz[2]) / 3.f;
+}
+
+int dsrt::median_subtree(const std::vector<TriBox>& tri_box, const std::vector<float>& centroid, std::vector<int>& order, int start, int end, int level,
+                         std::vector<GPUBVHNode>& nodes, int& height) {
+    Builder b{tri_box, centroid, order};
+    return b.build(start, end, level, nodes, height, 0);
+}
+
 extern "C" int dsrt_host_scene_build_bvh(DsrtHostScene* hs) {
     return dsrt::guarded("dsrt_host_scene_build_bvh", [&]() -> int {
     if (!hs) { dsrt::set_error("dsrt_host_scene_build_bvh: null scene"); return DSRT_ERR_INVALID; }
     hs->tri_indices.clear();
     hs->nodes.clear();
     hs->bvh_height = 0;
+    hs->bodies_tree = false;
     const size_t n = hs->tris.size();
     if (n == 0) { hs->bvh_valid = true; return DSRT_OK; }
     if (n > (size_t)1 << 28) { dsrt::set_error("more than 2^28 triangles"); return DSRT_ERR_INVALID; }
 
     std::vector<Box> tri_box(n);
     std::vector<float> centroid(3 * n);
-    for (size_t i = 0; i < n; ++i) {
-        const GPUTriangle& t = hs->tris[i];
-        const float vx[3] = {t.v0.x, t.v1.x, t.v2.x}, vy[3] = {t.v0.y, t.v1.y, t.v2.y}, vz[3] = {t.v0.z, t.v1.z, t.v2.z};
-        Box& b = tri_box[i];
-        b.lo[0] = fminf(fminf(vx[0], vx[1]), vx[2]); b.hi[0] = fmaxf(fmaxf(vx[0], vx[1]), vx[2]);
-        b.lo[1] = fminf(fminf(vy[0], vy[1]), vy[2]); b.hi[1] = fmaxf(fmaxf(vy[0], vy[1]), vy[2]);
-        b.lo[2] = fminf(fminf(vz[0], vz[1]), vz[2]); b.hi[2] = fmaxf(fmaxf(vz[0], vz[1]), vz[2]);
-        centroid[3 * i + 0] = (vx[0] + vx[1] + vx[2]) / 3.f;
-        centroid[3 * i + 1] = (vy[0] + vy[1] + vy[2]) / 3.f;
-        centroid[3 * i + 2] = (vz[0] + vz[1] + vz[2]) / 3.f;
-    }
+    for (size_t i = 0; i < n; ++i) dsrt::median_tri_box(hs->tris[i], tri_box[i], &centroid[3 * i]);
     hs->tri_indices.resize(n);
     for (size_t i = 0; i < n; ++i) hs->tri_indices[i] = (int)i;
     hs->nodes.reserve(n * 2);

@@ -301,6 +301,7 @@ extern "C" int dsrt_host_scene_build_bvh_sah(DsrtHostScene* hs) {
     hs->tri_indices.clear();
     hs->nodes.clear();
     hs->bvh_height = 0;
+    hs->bodies_tree = false;
     const int rc = dsrt::build_sah_tree(hs->tris.data(), hs->tris.size(), 0.0f, nullptr, hs->nodes, hs->tri_indices, hs->bvh_height, 4);
     if (rc != DSRT_OK) return rc;
     hs->bvh_valid = true;

@@ -64,6 +64,17 @@ struct SecondTree {
 };
 int prepare_second_tree(const GPUScene& h, int leaf_max, SecondTree& out);
 
+// bvh_median.cpp: the median-split builder on one range of `order` (triangle numbers), for bvh_bodies.cpp.  box / centroid are indexed by triangle number and
+// need to be filled only for the triangles of the range.  Appends the subtree to `nodes` in pre-order with absolute child indices and tri_offset = position in
+// `order`; `level` is the level of the subtree's root (the tree's root has 1), `height` is raised to the deepest level reached.  Returns the root's index.
+struct TriBox { float lo[3], hi[3]; };
+void median_tri_box(const GPUTriangle& t, TriBox& box, float centroid[3]);
+int median_subtree(const std::vector<TriBox>& tri_box, const std::vector<float>& centroid, std::vector<int>& order, int start, int end, int level,
+                   std::vector<GPUBVHNode>& nodes, int& height);
+
+// bvh_bodies.cpp: what dsrt_host_scene_set_body_poses and dsrt_scene_set_body_poses refuse alike -- a body outside 1 .. n_bodies - 1, null or non-finite poses
+int check_body_poses(int n_bodies, int first_body, int count, const float* poses, const char* fn);
+
 bool texture_flip_latch();
 void texture_flip_latch_set(bool v);
 
@@ -85,4 +96,15 @@ struct DsrtHostScene {
     std::vector<std::shared_ptr<dsrt::material>> keep_alive;       // keeps mat_index keys unique for the scene's lifetime
     bool bvh_valid = false;
     int bvh_height = 0;                                            // levels; the traversal stack needs height - 1 entries
+
+    // Movable rigid bodies (bvh_bodies.cpp; include/dsrt.h, MOVABLE RIGID BODIES).  Body b owns the triangles [body_start[b], body_start[b + 1]) -- the last one
+    // up to tris.size(); body 0 is the static part.  The rest is what dsrt_host_scene_build_bvh_bodies leaves and dsrt_host_scene_set_body_poses reads; it is
+    // current only while bodies_tree is set (every other builder and every add clears it).
+    std::vector<int> body_start{0};
+    bool bodies_tree = false;
+    std::vector<float> rest;                                       // 18 floats per triangle from body_start[1] on: v0 v1 v2 n0 n1 n2 at rest
+    std::vector<float> body_pad;                                   // per body: flat_box_pad(largest edge of its unpadded root box at rest)
+    std::vector<int> body_root;                                    // per body: node of its subtree's root, -1 for an empty body
+    std::vector<int> body_nodes;                                   // per body: nodes in its subtree (they follow the root: pre-order)
+    std::vector<int> chain;                                        // the top nodes T0, T1, ... in that order (empty with one non-empty body)
 };

@@ -132,6 +132,7 @@ int flatten_world(const hittable_list& world, DsrtHostScene* into) {
     if (!into) { set_error("flatten_world: null scene"); return DSRT_ERR_INVALID; }
     for (const auto& obj : world.objects) collect(*into, obj);
     into->bvh_valid = false;
+    into->bodies_tree = false;
     return DSRT_OK;
 }
 
@@ -251,6 +252,7 @@ int dsrt_host_scene_add_arrays(DsrtHostScene* hs, const GPUTriangle* tris, int n
     for (int i = 0; i < num_tris; ++i) { GPUTriangle t = tris[i]; t.material_id += base; hs->tris.push_back(t); }
     for (int i = 0; i < num_spheres; ++i) { GPUSphere s = spheres[i]; s.material_id += base; hs->spheres.push_back(s); }
     hs->bvh_valid = false;
+    hs->bodies_tree = false;
     return DSRT_OK;
     });
 }

@@ -33,10 +33,16 @@
 //     full-resolution G-buffer of the same camera keeps silhouettes, creases, material edges and sun-shadow edges at the output resolution.  Writes <frame> at the
 //     output size and <frame>_lowres, byte for byte the frame the same command writes without --upscale.  With --denoise [ITER] the denoiser runs between the two
 //     steps; --variance writes the upscaled variance as <frame>_var.pfm.  Does not combine with --temporal, --adaptive, --passes or --gbuffer.
+//   * --body OBJ [--body-scale S] (repeatable, up to 15) adds a MOVABLE RIGID BODY (include/dsrt.h, MOVABLE RIGID BODIES) and --body-poses FILE poses them: one
+//     line per RENDERED frame, 12 numbers per body (row-major 3x4 [R | t] in the model frame, applied to the body's rest pose; '#' lines are comments; frames past
+//     the last line keep the last poses).  The scene is uploaded once with dsrt_scene_upload_bodies and posed on the device before each frame; a batch launch has
+//     one set of poses, so such a run renders one launch per frame.  Does not combine with --bvh sah|lbvh, --fast or --certified-tree.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <sys/stat.h>
 #include <vector>
@@ -67,6 +73,8 @@ int main(int argc, char** argv) {
     int denoise_iterations = -1;                                    // -1: the library's default
     bool upscale = false;
     int upscale_factor = 4;                                         // the reference's scale (src/main.cpp:444)
+    std::vector<std::pair<std::string, double>> bodies;             // --body OBJ [--body-scale S], repeatable: movable rigid bodies 1, 2, ... (include/dsrt.h, MOVABLE RIGID BODIES)
+    std::string body_poses_file;                                    // --body-poses FILE: one line per rendered frame, 12 numbers per body (row-major 3x4 [R | t], model frame)
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -103,13 +111,23 @@ int main(int argc, char** argv) {
         }
         else if (a == "--temporal") temporal = true;                // with --denoise: reprojected frame history (include/dsrt.h, TEMPORAL ACCUMULATION)
         else if (a == "--flow") flow = true;                        // with --temporal: <frame>_flow.pfm, every pixel's displacement from the previous frame
+        else if (a == "--body") bodies.emplace_back(next("--body"), 1.0);
+        else if (a == "--body-scale") {
+            const double sc = std::atof(next("--body-scale"));
+            if (bodies.empty()) { std::fprintf(stderr, "dsrt_render: --body-scale follows the --body it scales\n"); return 2; }
+            bodies.back().second = sc;
+        }
+        else if (a == "--body-poses") body_poses_file = next("--body-poses");
         else if (a == "--upscale") {                                // rng_mode 1: G-buffer-guided upscaling by the optional factor (include/dsrt.h, UPSCALER)
             upscale = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') upscale_factor = std::atoi(argv[++i]);
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
+    if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
+    if ((int)bodies.size() > DSRT_MAX_BODIES - 1) { std::fprintf(stderr, "dsrt_render: at most %d --body\n", DSRT_MAX_BODIES - 1); return 2; }
+    if (!body_poses_file.empty() && bodies.empty()) { std::fprintf(stderr, "dsrt_render: --body-poses needs --body\n"); return 2; }
     if (upscale && rng_mode != 1) {                                 // the reference's bytes are not upscaled here: the flag is announced and ignored, as it always was
         std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
         upscale = false;
@@ -164,7 +182,28 @@ int main(int argc, char** argv) {
             if (strict_textures) return 3;
         }
     }
-    {
+    for (const auto& b : bodies) {
+        if (dsrt_host_scene_begin_body(hs) < 0) return fail("starting a body");
+        if (dsrt_host_scene_add_obj(hs, b.first.c_str(), b.second) != DSRT_OK) return fail("loading a body's mesh");
+    }
+    // one line of 12 numbers per body for every RENDERED frame, in order; frames past the last line keep the last poses
+    std::vector<std::vector<float>> body_poses;
+    if (!body_poses_file.empty()) {
+        std::ifstream in(body_poses_file);
+        if (!in) { std::fprintf(stderr, "dsrt_render: cannot open %s\n", body_poses_file.c_str()); return 1; }
+        std::string line;
+        while (std::getline(in, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            std::istringstream is(line);
+            std::vector<float> v;
+            for (double x; is >> x;) v.push_back((float)x);
+            if (v.size() != 12 * bodies.size()) { std::fprintf(stderr, "dsrt_render: %s: a line needs 12 numbers for each of the %zu bodies\n", body_poses_file.c_str(), bodies.size()); return 2; }
+            body_poses.push_back(v);
+        }
+    }
+    if (!bodies.empty()) {
+        if (dsrt_host_scene_build_bvh_bodies(hs) != DSRT_OK) return fail("building the bodies tree");
+    } else {
         float build_ms = 0.0f, total_ms = 0.0f;
         const int rc = lbvh ? dsrt_host_scene_build_bvh_gpu(hs, 0, &build_ms, &total_ms) : (sah ? dsrt_host_scene_build_bvh_sah(hs) : dsrt_host_scene_build_bvh(hs));
         if (rc != DSRT_OK) return fail("building the BVH");
@@ -194,7 +233,7 @@ int main(int argc, char** argv) {
         if (dsrt_camera_look_at(&cam, fr.cam_in_model, origin, 40.0f, width, height, spp, depth) != DSRT_OK) return fail("camera");
         if (ids.empty()) {
             dsrt_scene_set_frame(&scene, &cam, fr.sun_dir_model);
-            if (dsrt_scene_upload(ctx, &scene) != DSRT_OK) return fail("uploading the scene");
+            if ((bodies.empty() ? dsrt_scene_upload(ctx, &scene) : dsrt_scene_upload_bodies(ctx, hs, &scene)) != DSRT_OK) return fail("uploading the scene");
         }
         ids.push_back(i); cams.push_back(cam);
         suns.insert(suns.end(), fr.sun_dir_model, fr.sun_dir_model + 3);
@@ -330,7 +369,40 @@ int main(int argc, char** argv) {
         return 0;
     };
 
+    // --gbuffer: the ground truth of the frame the context's camera, sun and body poses are set to
+    auto write_gbuffer = [&](const std::string& base) -> int {
+        std::vector<float> range(px), normal(px * 3);
+        std::vector<uint8_t> flags(px);
+        DsrtGBuffer g;
+        std::memset(&g, 0, sizeof g);
+        g.range = range.data(); g.normal = normal.data(); g.flags = flags.data();
+        if (dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK) return fail("rendering the G-buffer");
+        if (dsrt_write_pfm((base + "_range.pfm").c_str(), range.data(), width, height, 1) != DSRT_OK ||
+            dsrt_write_pfm((base + "_normal.pfm").c_str(), normal.data(), width, height, 3) != DSRT_OK) return fail("writing the G-buffer");
+        if (!write_mask_pgm(base + "_mask.pgm", flags, width, height, DSRT_GB_HIT) || !write_mask_pgm(base + "_sunlit.pgm", flags, width, height, DSRT_GB_SUN_VISIBLE)) {
+            std::fprintf(stderr, "dsrt_render: cannot write the masks of %s\n", base.c_str());
+            return 1;
+        }
+        std::printf("Saved %s_{range,normal}.pfm, %s_{mask,sunlit}.pgm\n", base.c_str(), base.c_str());
+        return 0;
+    };
+
+    // --body: a batch launch has one scene and therefore one set of poses (include/dsrt.h), so a run with bodies renders one launch per frame
+    if (!bodies.empty() && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
+        DsrtStats st;
+        if (dsrt_render_to_host(ctx, &d, img.data(), nullptr, &st) != DSRT_OK) return fail("rendering");
+        const std::string path = base + ext;
+        if (!write_image(path, img.data())) return fail("writing the frame");
+        std::printf("kernel %.3f ms\nSaved %s\n", st.kernel_ms, path.c_str());
+        return gbuffer ? write_gbuffer(base) : 0;
+    };
+
     for (size_t q = 0; frame_step && q < ids.size(); ++q) {
+        if (q < body_poses.size()) {
+            float ms = 0.0f;
+            if (dsrt_scene_set_body_poses(ctx, 1, (int)bodies.size(), body_poses[q].data(), nullptr, &ms) != DSRT_OK) return fail("posing the bodies");
+            std::printf("bodies posed on the device in %.3f ms\n", ms);
+        }
         if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
         if (const int rc = frame_step(q, frame_base(ids[q]))) return rc;
     }
@@ -347,21 +419,9 @@ int main(int argc, char** argv) {
             if (!write_image(path, fb.data() + q * image_bytes)) return fail("writing the frame");
             std::printf("Saved %s\n", path.c_str());
             if (gbuffer) {
-                // the frame's ground truth: the context's camera and sun are set to this frame's (the batch launch above took them as arguments)
-                std::vector<float> range(px), normal(px * 3);
-                std::vector<uint8_t> flags(px);
-                DsrtGBuffer g;
-                std::memset(&g, 0, sizeof g);
-                g.range = range.data(); g.normal = normal.data(); g.flags = flags.data();
-                if (dsrt_scene_set_camera_sun(ctx, &cams[k + q], suns.data() + 3 * (k + q)) != DSRT_OK || dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK)
-                    return fail("rendering the G-buffer");
-                if (dsrt_write_pfm((base + "_range.pfm").c_str(), range.data(), width, height, 1) != DSRT_OK ||
-                    dsrt_write_pfm((base + "_normal.pfm").c_str(), normal.data(), width, height, 3) != DSRT_OK) return fail("writing the G-buffer");
-                if (!write_mask_pgm(base + "_mask.pgm", flags, width, height, DSRT_GB_HIT) || !write_mask_pgm(base + "_sunlit.pgm", flags, width, height, DSRT_GB_SUN_VISIBLE)) {
-                    std::fprintf(stderr, "dsrt_render: cannot write the masks of %s\n", base.c_str());
-                    return 1;
-                }
-                std::printf("Saved %s_{range,normal}.pfm, %s_{mask,sunlit}.pgm\n", base.c_str(), base.c_str());
+                // (the batch launch above took camera and sun as arguments: the context's are set to this frame's)
+                if (dsrt_scene_set_camera_sun(ctx, &cams[k + q], suns.data() + 3 * (k + q)) != DSRT_OK) return fail("setting the camera");
+                if (const int rc = write_gbuffer(base)) return rc;
             }
         }
     }
