@@ -888,7 +888,7 @@ int  dsrt_multi_uses_rccl(const DsrtMulti* m);
  * path that can run on a single GPU. */
 int  dsrt_selftest_rccl_gather(int device, size_t bytes);
 
-/* Development switches (scheduling experiments of the A/B tools under tools/; the bits are listed in csrc/device_api.hip).  One process-wide word; its initial
+/* Development switches (scheduling experiments of the A/B tools under tools/; the bits are listed in csrc/api_context.hip).  One process-wide word; its initial
  * value is the environment variable DSRT_EXPERIMENT, read ONCE in the first dsrt_device_count / dsrt_ctx_create call -- never per render.  Undefined bits are
  * refused (DSRT_ERR_INVALID) and a non-zero word is announced on stderr.  None changes an image byte; bit 27 replaces the optional FLOAT image of a counting
  * build by timing words.  Not for production hosts. */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B of render settings in ONE process on ONE box (development aid): each configuration `rng:switches[:loop knobs]` (the low six bits
 of `switches` are DsrtRenderDesc.tune[3], the DSRT_TUNE_* flags of include/dsrt.h; the rest goes to dsrt_dev_set_experiment, the
-library's development switches, csrc/device_api.hip) is rendered
+library's development switches, csrc/api_context.hip) is rendered
 --reps times, round-robin, and the medians of the kernel times (HIP events) are printed.  Devices differ by a few per cent, so
 settings are only ever compared inside one run of this tool."""
 import argparse
