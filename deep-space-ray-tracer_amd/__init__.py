@@ -348,6 +348,30 @@ def microbench_valu(kind=0, waves_per_simd=8, iters=20000, lane_mask=(1 << 64) -
             "cycles_per_instruction_per_simd": simds * ghz.value / gips}
 
 
+def _body_motion(first_tri, num_tris, poses_prev, poses_cur, prim_id_ptr):
+    """(DsrtBodyMotion, the arrays that keep its HOST pointers alive) of the bodies' triangle ranges (HostScene.body_range) and two sets of poses, (bodies, 12) or
+    (bodies, 3, 4) each, entry 0 ignored; prim_id_ptr: the G-buffer channel, wherever the form has its buffers."""
+    first, num = np.ascontiguousarray(first_tri, np.int32).reshape(-1), np.ascontiguousarray(num_tris, np.int32).reshape(-1)
+    pp, pc = (np.ascontiguousarray(x, np.float32).reshape(-1) for x in (poses_prev, poses_cur))
+    if not (len(first) == len(num) and pp.size == pc.size == 12 * len(first)):
+        raise ValueError(f"body motion: {len(first)} first_tri, {len(num)} num_tris, {pp.size} and {pc.size} pose floats do not describe one set of bodies")
+    m = capi.DsrtBodyMotion(len(first), first.ctypes.data, num.ctypes.data, pp.ctypes.data, pc.ctypes.data, prim_id_ptr)
+    return m, (first, num, pp, pc)
+
+
+def body_motion_host(first_tri, num_tris, poses_prev, poses_cur, prim_id, normal, position):
+    """dsrt_body_motion_host: the CPU statement of the motion rule (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES) over n points: prim_id int32 (n,), normal and
+    position float32 (n, 3).  Returns (prev_normal, prev_position) = (N', X'), float32 (n, 3)."""
+    prim = np.ascontiguousarray(prim_id, np.int32).reshape(-1)
+    N, X = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (normal, position))
+    if not len(prim) == len(N) == len(X):
+        raise ValueError("prim_id, normal and position must describe the same points")
+    m, keep = _body_motion(first_tri, num_tris, poses_prev, poses_cur, prim.ctypes.data)
+    n2, x2 = np.zeros_like(N), np.zeros_like(X)
+    _check(lib.dsrt_body_motion_host(C.byref(m), len(prim), _array_ptr(N), _array_ptr(X), _array_ptr(n2), _array_ptr(x2)), "dsrt_body_motion_host")
+    return n2, x2
+
+
 def stats_dict(st):
     return {name: getattr(st, name) for name, _ in DsrtStats._fields_}
 
@@ -361,7 +385,7 @@ def _array_ptr(a):
 
 
 _OUTPUTS = {"rgb8": (np.uint8, (3,)), "f32": (np.float32, (3,)), "linear": (np.float32, (3,)), "var": (np.float32, (3,)), "prev_xy": (np.float32, (2,)),
-            "weight": (np.float32, ()), "support": (np.float32, ())}
+            "weight": (np.float32, ()), "support": (np.float32, ()), "prev_position": (np.float32, (3,))}
 
 
 def _outputs(desc, wants, device=None):
@@ -709,8 +733,9 @@ class Context:
             out[k] = self._device_tensor(x, _torch.float32, (desc.width * desc.height * comps, f"width*height*{comps}"), f"guide {k}")
         return out
 
-    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None):
-        """denoise_accumulated and, with temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None), denoise_temporal: the outputs `wants` names."""
+    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None, motion=None):
+        """denoise_accumulated and, with temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None), denoise_temporal: the outputs `wants` names.
+        motion = (first_tri, num_tris, poses_prev, poses_cur, prim_id tensor): denoise_temporal_bodies."""
         acc = self._accum(desc, sums, sum_sq)
         n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
         if n is None and samples_done is None:
@@ -731,12 +756,17 @@ class Context:
         tail = (C.byref(params), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream)))
         if temporal is None:
             _check(lib.dsrt_denoise_accumulated(*head, *tail), "dsrt_denoise_accumulated")
+        elif motion is not None:
+            prim = self._pixel_tensor(desc, motion[4], _torch.int32, "prim_id")
+            m, keep = _body_motion(*motion[:4], prim.data_ptr())
+            _check(lib.dsrt_denoise_temporal_bodies(*head, C.byref(m), C.byref(prev_camera) if prev_camera is not None else None, _tensor_ptr(history_prev),
+                                                    _tensor_ptr(history_next), C.byref(tp), *tail), "dsrt_denoise_temporal_bodies")
         else:
             _check(lib.dsrt_denoise_temporal(*head, C.byref(prev_camera) if prev_camera is not None else None, _tensor_ptr(history_prev), _tensor_ptr(history_next),
                                              C.byref(tp), *tail), "dsrt_denoise_temporal")
         return tuple(out)
 
-    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None):
+    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None, motion=None):
         """The same from numpy arrays into numpy arrays (temporal: (prev_camera, history_prev or None, DsrtTemporal or None); the next history is returned last)."""
         H, W = desc.height, desc.width
         S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
@@ -762,6 +792,12 @@ class Context:
         if temporal is None:
             _check(lib.dsrt_denoise_accumulated_to_host(*head, *tail), "dsrt_denoise_accumulated_to_host")
             return tuple(out)
+        if motion is not None:
+            prim = np.ascontiguousarray(motion[4], np.int32).reshape(H, W)
+            m, keep = _body_motion(*motion[:4], prim.ctypes.data)
+            _check(lib.dsrt_denoise_temporal_bodies_to_host(*head, C.byref(m), C.byref(prev_camera) if prev_camera is not None else None, _array_ptr(prev), _array_ptr(nxt),
+                                                            C.byref(tp), *tail), "dsrt_denoise_temporal_bodies_to_host")
+            return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
         _check(lib.dsrt_denoise_temporal_to_host(*head, C.byref(prev_camera) if prev_camera is not None else None, _array_ptr(prev), _array_ptr(nxt), C.byref(tp), *tail),
                "dsrt_denoise_temporal_to_host")
         return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
@@ -804,6 +840,35 @@ class Context:
         return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
                                      dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight),
                                      temporal=(prev_camera, history_prev, temporal))
+
+    def denoise_temporal_bodies(self, desc, sums, sum_sq, guides, motion, history_next, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None,
+                                params=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False, want_weight=False,
+                                want_prev_position=False, stream=None):
+        """dsrt_denoise_temporal_bodies: denoise_temporal with the motion stage (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES).  motion = (first_tri, num_tris,
+        poses_prev, poses_cur, prim_id): the bodies' triangle ranges, the poses of the frame history_prev was written under and of this one ((bodies, 12) each), and
+        the current G-buffer's prim_id (int32 device tensor).  Returns denoise_temporal's tuple and prev_position (height, width, 3) after it."""
+        return self._denoise("denoise_temporal_bodies", desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
+                                  prev_position=want_prev_position), stream, temporal=(prev_camera, history_prev, history_next, temporal), motion=motion)
+
+    def denoise_temporal_bodies_to_host(self, desc, sums, sum_sq, guides, motion, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None,
+                                        params=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=True, want_weight=True,
+                                        want_prev_position=True):
+        """dsrt_denoise_temporal_bodies_to_host: the same from numpy arrays into numpy arrays (prim_id int32 (H, W)).  Returns
+        (rgb8, f32, linear, var, prev_xy, weight, prev_position, history_next)."""
+        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
+                                     dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
+                                          prev_position=want_prev_position), temporal=(prev_camera, history_prev, temporal), motion=motion)
+
+    def set_temporal_bodies(self, on=True):
+        """dsrt_ctx_set_temporal_bodies: render_denoised_temporal_to_host follows the resident scene's bodies -- a pose update no longer ends the sequence; the
+        motion stage runs with the poses of this frame and of the context's last one.  Off by default."""
+        _check(lib.dsrt_ctx_set_temporal_bodies(self._h, 1 if on else 0), "dsrt_ctx_set_temporal_bodies")
+        return self
+
+    @property
+    def temporal_bodies(self):
+        return bool(lib.dsrt_ctx_temporal_bodies(self._h))
 
     def render_denoised_temporal_to_host(self, desc, params=None, temporal=None, reset=False, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False):
         """dsrt_render_denoised_temporal_to_host: render_denoised_to_host with the history the CONTEXT keeps from call to call (reset=True starts a new sequence;

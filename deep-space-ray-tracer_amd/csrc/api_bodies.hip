@@ -85,6 +85,11 @@ int dsrt::build_bodies(const DsrtHostScene& hs, const PackReport& rep, PackedSce
     std::vector<float> pads(kMaxBodies, 0.0f), poses(kMaxBodies * 12, 0.0f);
     for (int b = 0; b < B; ++b) pads[b] = hs.body_pad[b];
     for (int b = 0; b < kMaxBodies; ++b) poses[12 * b] = poses[12 * b + 5] = poses[12 * b + 10] = 1.0f;
+    std::memcpy(bd->host_poses, poses.data(), sizeof bd->host_poses);
+    for (int b = 0; b < B; ++b) {
+        bd->first_tri.push_back(hs.body_start[b]);
+        bd->num_tris.push_back((b + 1 < B ? hs.body_start[b + 1] : N) - hs.body_start[b]);
+    }
     int rc;
     if ((rc = bd->rest_v.upload(rest_v)) || (rc = bd->rest_n.upload(rest_n)) || (rc = bd->pair_box.upload(box)) || (rc = bd->poses.upload(poses)) || (rc = bd->pads.upload(pads)) ||
         (rc = bd->refit.upload(refit)) || (rc = bd->chain.upload(chain)) || (rc = bd->root_box.alloc(6))) return rc;
@@ -157,7 +162,8 @@ int dsrt_scene_set_body_poses(DsrtContext* ctx, int first_body, int count, const
     HIP_TRY(hipMemcpyAsync(root, bd.root_box.p, sizeof root, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (int a = 0; a < 3; ++a) { sc.view.root_lo[a] = root[a]; sc.view.root_hi[a] = root[3 + a]; }
-    ctx->tp_valid = false;                         // the temporal history assumed the scene as it was
+    std::memcpy(bd.host_poses + 12 * (size_t)first_body, poses, 12 * (size_t)count * sizeof(float));
+    if (!ctx->tp_bodies) ctx->tp_valid = false;    // the temporal history assumed the scene as it was, unless the sequence follows the bodies (dsrt_ctx_set_temporal_bodies)
     if (ms) {
         for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&bd.last_ms[i], bd.ev[i], bd.ev[i + 1]));
         HIP_TRY(hipEventElapsedTime(ms, bd.ev[0], bd.ev[3]));

@@ -73,6 +73,8 @@ struct BodiesResident {
     std::vector<int> entry_start;                  // n_bodies + 1: body b's movable entries are [entry_start[b], entry_start[b + 1])
     std::vector<int2> depth_range;                 // {first, count} into `refit`, one per depth that has movable records, deepest first
     BodiesView view{};
+    std::vector<int> first_tri, num_tris;          // n_bodies each: the bodies' triangle ranges (dsrt_host_scene_body_range)
+    float host_poses[kMaxBodies * 12] = {};        // the poses the resident scene has now (identity after the upload): what a temporal frame with bodies calls `cur`
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float last_ms[3] = {0, 0, 0};
     ~BodiesResident() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -139,8 +141,10 @@ struct DsrtContext {
     // dsrt_render_denoised_temporal_to_host: the sequence the context keeps -- two histories (tp_hist[tp_cur] holds the last frame's), that frame's camera and size
     dsrt::DevBuf<float4> tp_hist[2];
     GPUCamera tp_camera{};
+    float tp_poses[dsrt::kMaxBodies * 12] = {};   // ... and, with tp_bodies, the poses the resident scene's bodies had in that frame
     int tp_cur = 0, tp_width = 0, tp_height = 0;
     bool tp_valid = false;
+    bool tp_bodies = false;         // dsrt_ctx_set_temporal_bodies: the sequence follows the bodies instead of ending with a pose update
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t done = nullptr;      // recorded behind every render: the next render on ANY stream waits for it (queue words, spill strip,
     bool done_valid = false;        // pre-pass arrays and partial sums are per context, so a context has one render in flight)
@@ -233,7 +237,8 @@ struct FrameBuffers {
     const void *sum, *sum_sq, *n;                                      // DsrtAccum, then the per-pixel counts
     const void *normal, *position, *albedo, *range;                    // DsrtDenoiseGuides
     const void *rgb8, *f32, *linear, *var;                             // the image outputs
-    const void *history_prev, *history_next, *prev_xy, *weight;        // the temporal stage's
+    const void *history_prev, *history_next, *prev_xy, *weight;        // the temporal stage's ...
+    const void *prim_id, *prev_position;                               // ... and its motion stage's (dsrt_denoise_temporal_bodies)
     const void *lo_linear, *lo_var, *lo_normal, *lo_position, *lo_albedo, *lo_range, *lo_flags, *lo_rgb8;      // the upscaler's, low resolution ...
     const void *flags, *support;                                       // ... and output resolution
 };
@@ -244,6 +249,7 @@ inline constexpr FrameBufferKind kFrameBuffers[] = {
     {12, Dir::In, 4}, {12, Dir::In, 4}, {12, Dir::In, 4}, {4, Dir::In, 4},                                // a row of this table per row of the struct
     {3, Dir::Out, 1}, {12, Dir::Out, 4}, {12, Dir::Out, 4}, {12, Dir::Out, 4},
     {kHistoryBytes, Dir::In, 16}, {kHistoryBytes, Dir::Out, 16}, {8, Dir::Out, 4}, {4, Dir::Out, 4},
+    {4, Dir::In, 4}, {12, Dir::Out, 4},
     {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {4, Dir::In, 4, true}, {1, Dir::In, 1, true},
     {3, Dir::Out, 1, true}, {1, Dir::In, 1}, {4, Dir::Out, 4}};
 constexpr size_t kFrameBufferCount = sizeof(FrameBuffers) / sizeof(void*);
@@ -276,9 +282,11 @@ struct FrameScratch {
     DevBuf<float> normal, position, albedo, range;
     DsrtAccum acc{};
     DsrtDenoiseGuides guides{};
-    DsrtGBuffer gb{};                                                  // the guides' four channels and no other
-    int init(size_t px, bool counts, bool with_guides) {
+    DevBuf<int32_t> prim_id;
+    DsrtGBuffer gb{};                                                  // the guides' four channels and, `with_prim_id`, that one
+    int init(size_t px, bool counts, bool with_guides, bool with_prim_id = false) {
         int rc;
+        if (with_prim_id) { if ((rc = prim_id.alloc(px))) return rc; gb.prim_id = prim_id.p; }
         if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (counts && (rc = n.alloc(px)))) return rc;
         if (with_guides && ((rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px)))) return rc;
         HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));

@@ -74,6 +74,17 @@ struct TemporalArgs {
     float alpha_min, normal_cos_min, plane_tol, min_support;
 };
 hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
+// The same with the motion stage (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES), a second kernel argument beside TemporalArgs, which stays as it is: the
+// G-buffer's prim_id, the optional X' output, per body >= 1 its triangle range [first, first + count) (zero for a body not given: an empty range), bit b of `moved`
+// set where body b's poses differ, and per body six float4 -- the cur pose's three rows {r0 r1 r2 t}, then the prev pose's (host/body_motion.cpp, BodyMotionTable).
+constexpr int kMaxBodies = 16;             // DSRT_MAX_BODIES
+struct BodyMotionArgs {
+    const int* prim_id; float* prev_position;
+    int first[kMaxBodies], count[kMaxBodies];
+    uint32_t moved;
+    float4 poses[kMaxBodies * 6];
+};
+hipError_t launch_temporal_bodies(const TemporalArgs& a, const BodyMotionArgs& mo, hipStream_t stream);
 
 // upscale_kernel.hip (include/dsrt.h, UPSCALER).  The LOW-resolution frame packed for the taps, one 16-byte record per low-resolution pixel each: {c.rgb, range},
 // {v.rgb, flags as a bit pattern}, {N, 0}, {X, 0}, {A, 0}.  pack fills them (var and flags may be null: zeros); the upscale launch reads them and the OUTPUT
@@ -93,7 +104,6 @@ hipError_t launch_upscale(const UpscaleArgs& a, bool device_libm, hipStream_t st
 
 // bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES).  What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
 // dsrt_scene_upload_bodies made resident beside them.  A movable ENTRY is a pair record of tri_pairs that holds triangles of a body >= 1; entries are sorted by body.
-constexpr int kMaxBodies = 16;             // DSRT_MAX_BODIES
 struct BodiesView {
     float4* pairs; float4* tri_pairs; float4* tri_shade;     // the resident scene's (device_layout.h)
     const int2* big_leaves;

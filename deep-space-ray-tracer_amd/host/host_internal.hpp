@@ -75,6 +75,12 @@ int median_subtree(const std::vector<TriBox>& tri_box, const std::vector<float>&
 // bvh_bodies.cpp: what dsrt_host_scene_set_body_poses and dsrt_scene_set_body_poses refuse alike -- a body outside 1 .. n_bodies - 1, null or non-finite poses
 int check_body_poses(int n_bodies, int first_body, int count, const float* poses, const char* fn);
 
+// body_motion.cpp (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES): what every form refuses of a DsrtBodyMotion but for where prim_id points, and the motion as the
+// device kernel takes it -- per body >= 1 its triangle range, a `moved` bit, and 24 floats: the cur pose, then the prev pose.  Entry 0 and bodies not given stay zero.
+struct BodyMotionTable { int first[DSRT_MAX_BODIES], count[DSRT_MAX_BODIES]; uint32_t moved; float poses[DSRT_MAX_BODIES * 24]; };
+int check_body_motion(const char* fn, const DsrtBodyMotion* m);
+void pack_body_motion(const DsrtBodyMotion& m, BodyMotionTable& t);
+
 bool texture_flip_latch();
 void texture_flip_latch_set(bool v);
 

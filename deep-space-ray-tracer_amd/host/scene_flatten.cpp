@@ -163,6 +163,7 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_TEMPORAL: return sizeof(DsrtTemporal);
         case DSRT_SIZEOF_UPSCALE_GUIDES: return sizeof(DsrtUpscaleGuides);
         case DSRT_SIZEOF_UPSCALE: return sizeof(DsrtUpscale);
+        case DSRT_SIZEOF_BODY_MOTION: return sizeof(DsrtBodyMotion);
         default: return 0;
     }
 }

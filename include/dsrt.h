@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -58,6 +58,7 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_TEMPORAL    14
 #define DSRT_SIZEOF_UPSCALE_GUIDES 15
 #define DSRT_SIZEOF_UPSCALE     16
+#define DSRT_SIZEOF_BODY_MOTION 18   /* (17 is left unassigned and answers 0: tests/test_upscale_host.py holds it to that as the first unknown index of its day) */
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -280,7 +281,8 @@ int dsrt_scene_upload_bodies(DsrtContext* ctx, const DsrtHostScene* hs, const GP
  * 0.05 / 0.07 / 0.12 ms for a body of 10^4 / 10^5 / 10^6 triangles beside a 10^6-triangle static part on an MI355X, against 98 / 111 / 283 ms
  * for host posing + dsrt_host_scene_build_bvh_gpu + dsrt_scene_upload.
  * The resident scene is shared with the context's clones (dsrt_ctx_clone): they see the new poses, and the caller must have NO LAUNCH OF A CLONE IN FLIGHT during
- * this call.  The convenience temporal sequence of the calling context (dsrt_render_denoised_temporal_to_host) starts afresh: its history assumes a static scene.
+ * this call.  The convenience temporal sequence of the calling context (dsrt_render_denoised_temporal_to_host) starts afresh: its history assumes a static scene -- unless
+ * dsrt_ctx_set_temporal_bodies is on for it (TEMPORAL ACCUMULATION WITH BODIES below).
  * A dsrt_render_batch launch has one scene and therefore one set of poses: a sequence with moving bodies renders one launch per frame.
  * Refusals: those of the host form, DSRT_ERR_NO_SCENE, and DSRT_ERR_INVALID when the resident scene has no bodies; a refused call touches no buffer. */
 int dsrt_scene_set_body_poses(DsrtContext* ctx, int first_body, int count, const float* poses, void* stream, float* ms);
@@ -760,6 +762,73 @@ int  dsrt_denoise_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc,
                                    uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, float* h_weight);
 int  dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* params, const DsrtTemporal* temporal, int reset, uint8_t* h_rgb8,
                                            float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, DsrtStats* stats);
+
+/*
+ * TEMPORAL ACCUMULATION WITH BODIES (on top of TEMPORAL ACCUMULATION and MOVABLE RIGID BODIES): the stage above assumes a scene that is static in the model frame,
+ * and a sequence with movable bodies is the one that most needs accumulated samples and flow ground truth.  The G-buffer gives every pixel's triangle, the host scene
+ * every body's triangle range, and the caller owns the poses of both frames: the MOTION STAGE takes a pixel's surface point and normal back to where that material
+ * point was in the previous frame, and the stage above -- projection, tap tests, occluder guard -- works on that.  tests/_motion_model.py reproduces every bit.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written.
+ *   Motion description (DsrtBodyMotion): bodies in 1 .. DSRT_MAX_BODIES; HOST arrays first_tri[bodies], num_tris[bodies] (as dsrt_host_scene_body_range gives them),
+ *     poses_prev[12*bodies], poses_cur[12*bodies] (row-major 3 x 4, applied to the rest pose, as everywhere; entry 0 is ignored: body 0 never moves); prim_id, the
+ *     G-buffer's int32 channel of the CURRENT frame (a DEVICE pointer; a HOST pointer in the _to_host form and in dsrt_body_motion_host).  poses_prev are the poses
+ *     the scene had when history_prev was written.
+ *   Body of a pixel: b(p) = the b >= 1 with first_tri[b] <= prim_id[p] < first_tri[b] + num_tris[b], otherwise 0 -- body 0's triangles, spheres (<= -2), misses (-1)
+ *     and any other value.
+ *   Moved: body b >= 1 is MOVED when any of its 12 pose floats differs (!=) between prev and cur.
+ *   A pixel whose body is 0 or not moved: N' = N_p and X' = X_p bit for bit.
+ *   A pixel on a moved body, c = the cur pose (c00 .. c22, translation ct), q = the prev pose (q00 .. q22, qt); the current rotation's transpose stands in for its
+ *     inverse (an orthonormal R stays the caller's business, as in MOVABLE RIGID BODIES):
+ *       d   = X_p - ct                                                                                   (componentwise)
+ *       r.x = (c00*d.x + c10*d.y) + c20*d.z;   r.y with c01, c11, c21;   r.z with c02, c12, c22
+ *       X'.x = ((q00*r.x + q01*r.y) + q02*r.z) + qt.x;   rows 1 and 2 likewise                            (the "point" rule of MOVABLE RIGID BODIES)
+ *       m   = the same transpose product applied to N_p;   N' = the "normal" rule applied to m            (no translation, NOT renormalised)
+ *   The stage: TEMPORAL ACCUMULATION with (N', X') in place of (N_p, X_p) wherever the pixel meets the previous frame -- D = X' - C.origin in the projection, both
+ *     tap tests, the occluder guard.  The rest is as there: range_p, F_p, c, v and n are the current frame's, the tolerance stays plane_tol * range_p, and the `next`
+ *     record stores the current N_p, X_p.
+ *   Outputs: d_prev_xy is (fx, fy) of X' -- flow ground truth that includes the bodies' motion.  d_prev_position (optional, 3 floats per pixel) receives X' for every
+ *     pixel with range_p <= FLT_MAX, whether or not a previous frame is given, and +0 otherwise.
+ * With all poses equal the stage is the static one, bit for bit.  A body that enters or leaves the view, or that uncovers the station behind it, needs nothing of its
+ * own: the record at the projected place shows another surface, and the tap tests and the guard reject it.
+ * WHAT IS NOT FOLLOWED: SHADING.  A moving body's shadow moves across static pixels, and a body's own radiance changes as it turns to the Sun: the history lags there,
+ * and alpha_min is the only guard.  OUT OF SCOPE HERE: carrying the G-buffer's sun-visibility bit in a spare word of the history record, to reject taps across a moved
+ * shadow edge -- it changes the history record.
+ *
+ * dsrt_body_motion_host: the CPU statement of the motion rule over n points, no GPU involved: prim_id (HOST, n entries), normal and position (3 floats per point)
+ *   give prev_normal = N' and prev_position = X' (either may be NULL; they may not overlap the inputs).  DSRT_ERR_INVALID: what is refused of a DsrtBodyMotion below,
+ *   n < 0, a NULL input, a pointer not 4-byte aligned.
+ * dsrt_denoise_temporal_bodies: dsrt_denoise_temporal with the motion stage: `motion` after `guides`, d_prev_position after d_weight.  Stream order, waiting, working
+ *   memory and "needs no scene" are unchanged; the motion's HOST arrays are read before the call returns.  DSRT_ERR_INVALID: what dsrt_denoise_temporal refuses; a
+ *   NULL motion or a NULL member of it; bodies outside 1 .. 16; a negative first_tri or num_tris; ranges of bodies >= 1 that overlap; a pose entry of a body >= 1
+ *   that is not finite; prim_id not 4-byte aligned, or overlapping an output; d_prev_position misaligned, or overlapping anything.  `motion` is validated on the first
+ *   frame (prev NULL) too.  A refused call touches no buffer.
+ * dsrt_denoise_temporal_bodies_to_host: the same from HOST buffers into HOST buffers, synchronously.
+ * dsrt_ctx_set_temporal_bodies / dsrt_ctx_temporal_bodies: the switch of the convenience form, per context (a clone has its own, off), OFF by default; off
+ *   is the behaviour described above: a pose update voids the context's sequence.  ON, and the resident scene has bodies: dsrt_scene_set_body_poses does not void the
+ *   sequence, and dsrt_render_denoised_temporal_to_host asks its G-buffer for prim_id as well, runs the stage above with cur = the resident scene's current poses
+ *   (a host copy kept with the shared scene; identity after dsrt_scene_upload_bodies) and prev = the poses of this context's last temporal frame, and records cur
+ *   afterwards.  reset, a size change and an upload still start afresh.  The result is exactly the explicit chain of dsrt_denoise_temporal_bodies calls.
+ */
+typedef struct DsrtBodyMotion {
+    int bodies;
+    const int* first_tri;       /* HOST, [bodies] */
+    const int* num_tris;        /* HOST, [bodies] */
+    const float* poses_prev;    /* HOST, [12*bodies] */
+    const float* poses_cur;     /* HOST, [12*bodies] */
+    const int32_t* prim_id;     /* DEVICE (HOST in the host forms), one per pixel */
+} DsrtBodyMotion;
+int  dsrt_body_motion_host(const DsrtBodyMotion* motion, int n, const float* normal, const float* position, float* prev_normal, float* prev_position);
+int  dsrt_denoise_temporal_bodies(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                                  const DsrtBodyMotion* motion, const GPUCamera* prev_camera /* HOST */, const float* d_history_prev, float* d_history_next,
+                                  const DsrtTemporal* temporal, const DsrtDenoise* params, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, float* d_prev_xy,
+                                  float* d_weight, float* d_prev_position, void* stream);
+int  dsrt_denoise_temporal_bodies_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n,
+                                          const DsrtDenoiseGuides* h_guides, const DsrtBodyMotion* motion, const GPUCamera* prev_camera, const float* h_history_prev,
+                                          float* h_history_next, const DsrtTemporal* temporal, const DsrtDenoise* params, uint8_t* h_rgb8, float* h_f32, float* h_linear,
+                                          float* h_var, float* h_prev_xy, float* h_weight, float* h_prev_position);
+int  dsrt_ctx_set_temporal_bodies(DsrtContext* ctx, int on);
+int  dsrt_ctx_temporal_bodies(const DsrtContext* ctx);
 
 /*
  * UPSCALER (on top of the DENOISER and the G-BUFFER): a full-resolution frame out of a low-resolution render.  Joint bilateral upsampling (Kopf et al. 2007) whose

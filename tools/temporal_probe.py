@@ -3,7 +3,13 @@
 two frames of a moving camera at 8 spp, and -- HIP events around the calls, 3 warm-ups + 30 reps, medians --
     dsrt_denoise_accumulated with 0 and 1 iterations   (their difference: one a-trous iteration, step 1)
     dsrt_denoise_temporal    with 0 iterations         (its difference to the first: the temporal kernel)
-One JSON line on stdout."""
+One JSON line on stdout.
+
+--bodies: the same station with a visitor -- a cube of 8 m as movable body 1, halfway between the camera and the station, about a sixth of the picture -- that turns
+and shifts between the two frames (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES), and on the second frame, in the same run,
+    dsrt_denoise_temporal         with 0 iterations    (dsrt_temporal_kernel: the static stage on the same inputs)
+    dsrt_denoise_temporal_bodies  with 0 iterations    (dsrt_temporal_bodies_kernel), without and with d_prev_position
+each less dsrt_denoise_accumulated with 0 iterations, and the ratio of the two kernels."""
 import json
 import os
 import statistics
@@ -12,6 +18,86 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def _timed(torch, calls, warm=3, reps=30):
+    """{name: [ms]} of the calls, interleaved, HIP events around each; the last call's result."""
+    ms = {k: [] for k in calls}
+    out = None
+    for rep in range(warm + reps):
+        for k, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = call()
+            e1.record()
+            e1.synchronize()
+            if rep >= warm:
+                ms[k].append(e0.elapsed_time(e1))
+    return ms, out
+
+
+def main_bodies():
+    import numpy as np
+    import torch
+    import dsrt_amd as d
+    from conftest import load_world
+    from _bodies_model import _pose, _rot
+    W, H, spp, seed = 1920, 1080, 8, 0xDEADBEEF00001337
+    sun = (0.32780463, -0.7564221, 0.5660121)
+    eyes = ((12.4, 9.0, 37.8), (12.0, 9.0, 38.0))
+    cams = [d.camera_look_at(p, (0, 0, 0), 40.0, W, H, spp, 50) for p in eyes]
+    hs = load_world(d, "station_3k")
+    assert hs.begin_body() == 1
+    v = np.array([(x, y, z) for x in (-4, 4) for y in (-4, 4) for z in (-4, 4)], np.float32)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    t = np.zeros(12, d.capi.TRI_DTYPE)
+    t["v"] = np.array([[v[a], v[b], v[c]] for q in quads for a, b, c in ((q[0], q[1], q[2]), (q[0], q[2], q[3]))], np.float32)
+    fn = np.cross(t["v"][:, 1] - t["v"][:, 0], t["v"][:, 2] - t["v"][:, 0])
+    t["n"] = np.repeat((fn / np.linalg.norm(fn, axis=1, keepdims=True))[:, None, :], 3, axis=1)
+    t["albedo_tex"] = -1
+    mats = np.zeros(1, d.capi.MAT_DTYPE)
+    mats["albedo_tex"], mats["albedo"], mats["ref_idx"] = -1, (0.7, 0.6, 0.5), 1.5
+    hs.add_arrays(tris=t, mats=mats)
+    hs.build_bvh_bodies()
+    first, num = (np.array(x, np.int32) for x in zip(*[hs.body_range(b) for b in range(2)]))
+    poses = [np.stack([np.zeros(12, np.float32), _pose(_rot((1, 2, 3), 0.5 + 0.03 * k), 0.5 * np.array(eyes[k]) + (0.3 * k, 0.2 * k, 0.0))]) for k in range(2)]
+    ctx = d.Context(0)
+    ctx.upload_bodies(hs, hs.view(cams[0], sun))
+    hist = [torch.zeros(W * H * 16, dtype=torch.float32, device="cuda:0") for _ in range(2)]
+    p0 = d.denoise_defaults(iterations=0)
+    for f, cam in enumerate(cams):
+        ctx.set_body_poses(1, poses[f][1:])
+        ctx.set_camera_sun(cam, sun)
+        desc = d.make_desc(W, H, spp, seed=seed + f, rng_mode=1)
+        acc = d.Accumulator(ctx, desc, moments=True)
+        acc.render(0)
+        g = acc.guides()
+        prim = torch.empty((H, W), dtype=torch.int32, device="cuda:0")
+        ctx.render_gbuffer(desc, {"prim_id": prim.data_ptr()}, stream=ctx._raw_stream(None))
+        if f == 0:
+            ctx.denoise_temporal_bodies(desc, acc.sum, acc.sum_sq, g, (first, num, poses[0], poses[0], prim), hist[0], samples_done=spp, params=p0)
+    torch.cuda.synchronize()
+    mo = (first, num, poses[0], poses[1], prim)
+    calls = {
+        "denoise_0_iterations": lambda: ctx.denoise_accumulated(desc, acc.sum, acc.sum_sq, g, samples_done=spp, params=p0),
+        "temporal_0_iterations": lambda: ctx.denoise_temporal(desc, acc.sum, acc.sum_sq, g, hist[1], cams[0], hist[0], samples_done=spp, params=p0, want_weight=True),
+        "temporal_bodies_0_iterations": lambda: ctx.denoise_temporal_bodies(desc, acc.sum, acc.sum_sq, g, mo, hist[1], cams[0], hist[0], samples_done=spp, params=p0, want_weight=True),
+        "temporal_bodies_prev_position_0_iterations": lambda: ctx.denoise_temporal_bodies(desc, acc.sum, acc.sum_sq, g, mo, hist[1], cams[0], hist[0], samples_done=spp, params=p0,
+                                                                                          want_weight=True, want_prev_position=True),
+    }
+    ms, _ = _timed(torch, calls)
+    med = {k: statistics.median(x) for k, x in ms.items()}
+    w_static = calls["temporal_0_iterations"]()[5]
+    w_bodies = calls["temporal_bodies_0_iterations"]()[5]
+    torch.cuda.synchronize()
+    on_body = prim >= int(first[1])
+    k_static, k_bodies, k_pos = (med[k] - med["denoise_0_iterations"] for k in ("temporal_0_iterations", "temporal_bodies_0_iterations", "temporal_bodies_prev_position_0_iterations"))
+    res = {"width": W, "height": H, "spp": spp, "body_share_of_pixels": float(on_body.float().mean()),
+           "history_share_on_the_body": {"static": float((w_static[on_body] > spp).float().mean()), "bodies": float((w_bodies[on_body] > spp).float().mean())},
+           "ms_median": med, "ms_min": {k: min(x) for k, x in ms.items()}, "temporal_kernel_ms": k_static, "temporal_bodies_kernel_ms": k_bodies,
+           "temporal_bodies_kernel_with_prev_position_ms": k_pos, "ratio_bodies_to_static": k_bodies / k_static, "ratio_with_prev_position": k_pos / k_static}
+    print(json.dumps(res))
+    ctx.close()
 
 
 def main():
@@ -62,4 +148,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main_bodies() if "--bodies" in sys.argv[1:] else main()
