@@ -129,10 +129,12 @@ __device__ __forceinline__ void temporal_bodies_pixel(const TemporalArgs& a, con
     float hnx = np.x, hny = np.y, hnz = np.z, hxx = xp.x, hxy = xp.y, hxz = xp.z;
     {
         // the pixel's body: at most 15 wave-uniform ranges, from the kernarg (scalar registers); they do not overlap, so the order of the search does not matter
-        const uint32_t prim = (uint32_t)mo->prim_id[p];
+        // (first <= prim < first + count, whatever the sum: with prim >= first >= 0 the difference is below 2^31 and the unsigned test is exact; without that
+        // comparison a negative prim_id would wrap into a range that reaches beyond 2^31)
+        const int32_t prim = mo->prim_id[p];
         int body = 0;
 #pragma unroll
-        for (int b = 1; b < kMaxBodies; ++b) body = prim - (uint32_t)mo->first[b] < (uint32_t)mo->count[b] ? b : body;
+        for (int b = 1; b < kMaxBodies; ++b) body = ((prim >= mo->first[b]) & ((uint32_t)prim - (uint32_t)mo->first[b] < (uint32_t)mo->count[b])) ? b : body;
         if (mo->moved >> body & 1u) {                                        // (bit 0 is never set)
             const float4* t = pose_lds + body * 6;                           // cur rows 0..2, prev rows 0..2: {r0 r1 r2 t}
             const float4 c0 = t[0], c1 = t[1], c2 = t[2], q0 = t[3], q1 = t[4], q2 = t[5];

@@ -241,7 +241,8 @@ int dsrt_scene_set_camera_sun(DsrtContext* ctx, const GPUCamera* cam, const floa
  * in pre-order, tri_indices is global.  A rigid motion keeps a subtree's topology good; only boxes change (an axis-aligned box does not rotate).
  *
  * THE ARITHMETIC of a pose update -- fp32, every operation one correctly rounded operation, never contracted, in the order written; the host form, the device
- * form and tests/_bodies_model.py agree bit for bit:
+ * form and tests/_bodies_model.py agree bit for bit.  That word-for-word equality holds while every posed coordinate is finite (a finite pose can still overflow
+ * a large coordinate; the NaN that follows differs in its sign bit between host and device):
  *   pose          12 floats, row-major  r00 r01 r02 tx | r10 r11 r12 ty | r20 r21 r22 tz,  in the model frame
  *   point         x' = ((r00*x + r01*y) + r02*z) + tx,  y' and z' likewise with rows 1 and 2
  *   normal        the same without the translation; NOT renormalised (an orthonormal R is the caller's business)
@@ -800,7 +801,8 @@ int  dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDes
  *   n < 0, a NULL input, a pointer not 4-byte aligned.
  * dsrt_denoise_temporal_bodies: dsrt_denoise_temporal with the motion stage: `motion` after `guides`, d_prev_position after d_weight.  Stream order, waiting, working
  *   memory and "needs no scene" are unchanged; the motion's HOST arrays are read before the call returns.  DSRT_ERR_INVALID: what dsrt_denoise_temporal refuses; a
- *   NULL motion or a NULL member of it; bodies outside 1 .. 16; a negative first_tri or num_tris; ranges of bodies >= 1 that overlap; a pose entry of a body >= 1
+ *   NULL motion or a NULL member of it; bodies outside 1 .. 16; a negative first_tri or num_tris (first_tri + num_tris may be anything up to 2^32 - 2: the range
+ *   test is the rule above for every int32 prim_id, on the host and on the device); ranges of bodies >= 1 that overlap; a pose entry of a body >= 1
  *   that is not finite; prim_id not 4-byte aligned, or overlapping an output; d_prev_position misaligned, or overlapping anything.  `motion` is validated on the first
  *   frame (prev NULL) too.  A refused call touches no buffer.
  * dsrt_denoise_temporal_bodies_to_host: the same from HOST buffers into HOST buffers, synchronously.
