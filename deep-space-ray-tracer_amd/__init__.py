@@ -277,6 +277,12 @@ def temporal_defaults(**changes):
     return p
 
 
+def temporal_shading(flags_ptr, edge_guard=1):
+    """A DsrtTemporalShading (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING): flags_ptr the address of the current G-buffer's flags channel (a device
+    address for the device form, a host address for the host form: an int, a ctypes.c_void_p or None), edge_guard 0 or 1."""
+    return capi.DsrtTemporalShading(flags_ptr, int(edge_guard))
+
+
 UPSCALE_GUIDES = DENOISE_GUIDES + ("flags",)                         # DsrtUpscaleGuides' channels; "flags" (uint8) is the optional one
 
 
@@ -385,7 +391,7 @@ def _array_ptr(a):
 
 
 _OUTPUTS = {"rgb8": (np.uint8, (3,)), "f32": (np.float32, (3,)), "linear": (np.float32, (3,)), "var": (np.float32, (3,)), "prev_xy": (np.float32, (2,)),
-            "weight": (np.float32, ()), "support": (np.float32, ()), "prev_position": (np.float32, (3,))}
+            "weight": (np.float32, ()), "support": (np.float32, ()), "prev_position": (np.float32, (3,)), "status": (np.uint8, ())}
 
 
 def _outputs(desc, wants, device=None):
@@ -733,9 +739,10 @@ class Context:
             out[k] = self._device_tensor(x, _torch.float32, (desc.width * desc.height * comps, f"width*height*{comps}"), f"guide {k}")
         return out
 
-    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None, motion=None):
+    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None, motion=None, shading=None):
         """denoise_accumulated and, with temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None), denoise_temporal: the outputs `wants` names.
-        motion = (first_tri, num_tris, poses_prev, poses_cur, prim_id tensor): denoise_temporal_bodies."""
+        motion = (first_tri, num_tris, poses_prev, poses_cur, prim_id tensor): denoise_temporal_bodies.  shading = (flags tensor, edge_guard): denoise_temporal_shaded,
+        with or without a motion."""
         acc = self._accum(desc, sums, sum_sq)
         n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
         if n is None and samples_done is None:
@@ -756,6 +763,13 @@ class Context:
         tail = (C.byref(params), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream)))
         if temporal is None:
             _check(lib.dsrt_denoise_accumulated(*head, *tail), "dsrt_denoise_accumulated")
+        elif shading is not None:
+            m = keep = None
+            if motion is not None:
+                m, keep = _body_motion(*motion[:4], self._pixel_tensor(desc, motion[4], _torch.int32, "prim_id").data_ptr())
+            sh = temporal_shading(_tensor_ptr(self._pixel_tensor(desc, shading[0], _torch.uint8, "flags")), shading[1])
+            _check(lib.dsrt_denoise_temporal_shaded(*head, C.byref(m) if m is not None else None, C.byref(sh), C.byref(prev_camera) if prev_camera is not None else None,
+                                                    _tensor_ptr(history_prev), _tensor_ptr(history_next), C.byref(tp), *tail), "dsrt_denoise_temporal_shaded")
         elif motion is not None:
             prim = self._pixel_tensor(desc, motion[4], _torch.int32, "prim_id")
             m, keep = _body_motion(*motion[:4], prim.data_ptr())
@@ -766,7 +780,7 @@ class Context:
                                              C.byref(tp), *tail), "dsrt_denoise_temporal")
         return tuple(out)
 
-    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None, motion=None):
+    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None, motion=None, shading=None):
         """The same from numpy arrays into numpy arrays (temporal: (prev_camera, history_prev or None, DsrtTemporal or None); the next history is returned last)."""
         H, W = desc.height, desc.width
         S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
@@ -792,6 +806,16 @@ class Context:
         if temporal is None:
             _check(lib.dsrt_denoise_accumulated_to_host(*head, *tail), "dsrt_denoise_accumulated_to_host")
             return tuple(out)
+        if shading is not None:
+            m = keep = None
+            if motion is not None:
+                prim = np.ascontiguousarray(motion[4], np.int32).reshape(H, W)
+                m, keep = _body_motion(*motion[:4], prim.ctypes.data)
+            flags = np.ascontiguousarray(shading[0], np.uint8).reshape(H, W)
+            sh = temporal_shading(_array_ptr(flags), shading[1])
+            _check(lib.dsrt_denoise_temporal_shaded_to_host(*head, C.byref(m) if m is not None else None, C.byref(sh), C.byref(prev_camera) if prev_camera is not None else None,
+                                                            _array_ptr(prev), _array_ptr(nxt), C.byref(tp), *tail), "dsrt_denoise_temporal_shaded_to_host")
+            return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
         if motion is not None:
             prim = np.ascontiguousarray(motion[4], np.int32).reshape(H, W)
             m, keep = _body_motion(*motion[:4], prim.ctypes.data)
@@ -869,6 +893,38 @@ class Context:
     @property
     def temporal_bodies(self):
         return bool(lib.dsrt_ctx_temporal_bodies(self._h))
+
+    def denoise_temporal_shaded(self, desc, sums, sum_sq, guides, flags, history_next, motion=None, edge_guard=1, prev_camera=None, history_prev=None, samples_done=None,
+                                n=None, temporal=None, params=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False,
+                                want_weight=False, want_prev_position=False, want_status=False, stream=None):
+        """dsrt_denoise_temporal_shaded: denoise_temporal_bodies with the sun state (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING).  flags: the current
+        G-buffer's flags channel (uint8 device tensor); motion as denoise_temporal_bodies', or None for a static scene (then no prev_position); edge_guard 0 or 1.
+        Returns denoise_temporal_bodies' tuple and status (height, width) uint8 after it."""
+        return self._denoise("denoise_temporal_shaded", desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
+                                  prev_position=want_prev_position, status=want_status), stream, temporal=(prev_camera, history_prev, history_next, temporal),
+                             motion=motion, shading=(flags, edge_guard))
+
+    def denoise_temporal_shaded_to_host(self, desc, sums, sum_sq, guides, flags, motion=None, edge_guard=1, prev_camera=None, history_prev=None, samples_done=None, n=None,
+                                        temporal=None, params=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=True, want_weight=True,
+                                        want_prev_position=None, want_status=True):
+        """dsrt_denoise_temporal_shaded_to_host: the same from numpy arrays into numpy arrays (flags uint8 (H, W)).  Returns
+        (rgb8, f32, linear, var, prev_xy, weight, prev_position, status, history_next); prev_position is asked for by default where there is a motion."""
+        want_prev_position = motion is not None if want_prev_position is None else want_prev_position
+        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
+                                     dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
+                                          prev_position=want_prev_position, status=want_status), temporal=(prev_camera, history_prev, temporal), motion=motion,
+                                     shading=(flags, edge_guard))
+
+    def set_temporal_shading(self, mode=2):
+        """dsrt_ctx_set_temporal_shading: render_denoised_temporal_to_host keeps the sun state in its history -- 0 off (the default), 1 the tap test only, 2 with the
+        edge guards."""
+        _check(lib.dsrt_ctx_set_temporal_shading(self._h, int(mode)), "dsrt_ctx_set_temporal_shading")
+        return self
+
+    @property
+    def temporal_shading(self):
+        return int(lib.dsrt_ctx_temporal_shading(self._h))
 
     def render_denoised_temporal_to_host(self, desc, params=None, temporal=None, reset=False, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False):
         """dsrt_render_denoised_temporal_to_host: render_denoised_to_host with the history the CONTEXT keeps from call to call (reset=True starts a new sequence;

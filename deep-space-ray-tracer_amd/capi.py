@@ -146,6 +146,10 @@ class DsrtBodyMotion(C.Structure):
     _fields_ = [("bodies", C.c_int), ("first_tri", C.c_void_p), ("num_tris", C.c_void_p), ("poses_prev", C.c_void_p), ("poses_cur", C.c_void_p), ("prim_id", C.c_void_p)]
 
 
+class DsrtTemporalShading(C.Structure):
+    _fields_ = [("flags", C.c_void_p), ("edge_guard", C.c_int)]
+
+
 MAX_BODIES = 16                                                         # DSRT_MAX_BODIES of include/dsrt.h
 HISTORY_FLOATS = 16                                                     # per pixel of a temporal history buffer (include/dsrt.h, TEMPORAL ACCUMULATION)
 
@@ -184,6 +188,7 @@ EXPORTS = [
     "dsrt_host_scene_begin_body", "dsrt_host_scene_body_count", "dsrt_host_scene_body_range", "dsrt_host_scene_build_bvh_bodies", "dsrt_host_scene_set_body_poses",
     "dsrt_scene_upload_bodies", "dsrt_scene_set_body_poses", "dsrt_ctx_body_count", "dsrt_ctx_body_update_ms", "dsrt_selftest_read_scene_words",
     "dsrt_body_motion_host", "dsrt_denoise_temporal_bodies", "dsrt_denoise_temporal_bodies_to_host", "dsrt_ctx_set_temporal_bodies", "dsrt_ctx_temporal_bodies",
+    "dsrt_denoise_temporal_shaded", "dsrt_denoise_temporal_shaded_to_host", "dsrt_ctx_set_temporal_shading", "dsrt_ctx_temporal_shading",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -302,6 +307,12 @@ def load():
                                                          P(DsrtTemporal), P(DsrtDenoise), vp, vp, vp, vp, vp, vp, vp])
     sig("dsrt_ctx_set_temporal_bodies", C.c_int, [vp, C.c_int])
     sig("dsrt_ctx_temporal_bodies", C.c_int, [vp])
+    sig("dsrt_denoise_temporal_shaded", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), P(DsrtBodyMotion), P(DsrtTemporalShading), P(GPUCamera),
+                                                 vp, vp, P(DsrtTemporal), P(DsrtDenoise), vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("dsrt_denoise_temporal_shaded_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), P(DsrtBodyMotion), P(DsrtTemporalShading),
+                                                         P(GPUCamera), vp, vp, P(DsrtTemporal), P(DsrtDenoise), vp, vp, vp, vp, vp, vp, vp, vp])
+    sig("dsrt_ctx_set_temporal_shading", C.c_int, [vp, C.c_int])
+    sig("dsrt_ctx_temporal_shading", C.c_int, [vp])
     sig("dsrt_upscale_defaults", None, [P(DsrtUpscale)])
     sig("dsrt_upscale_guided", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp, vp])
     sig("dsrt_upscale_guided_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp])
@@ -331,7 +342,7 @@ def load():
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
     for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
-                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
+                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
         if struct is not None and lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

@@ -145,6 +145,7 @@ struct DsrtContext {
     int tp_cur = 0, tp_width = 0, tp_height = 0;
     bool tp_valid = false;
     bool tp_bodies = false;         // dsrt_ctx_set_temporal_bodies: the sequence follows the bodies instead of ending with a pose update
+    int tp_shading = 0;             // dsrt_ctx_set_temporal_shading: 0 off, 1 the sun-state tap test, 2 with the edge guards
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t done = nullptr;      // recorded behind every render: the next render on ANY stream waits for it (queue words, spill strip,
     bool done_valid = false;        // pre-pass arrays and partial sums are per context, so a context has one render in flight)
@@ -239,6 +240,7 @@ struct FrameBuffers {
     const void *rgb8, *f32, *linear, *var;                             // the image outputs
     const void *history_prev, *history_next, *prev_xy, *weight;        // the temporal stage's ...
     const void *prim_id, *prev_position;                               // ... and its motion stage's (dsrt_denoise_temporal_bodies)
+    const void *shade_flags, *status;                                  // ... and its sun state's (dsrt_denoise_temporal_shaded): the current G-buffer's flags, the status byte
     const void *lo_linear, *lo_var, *lo_normal, *lo_position, *lo_albedo, *lo_range, *lo_flags, *lo_rgb8;      // the upscaler's, low resolution ...
     const void *flags, *support;                                       // ... and output resolution
 };
@@ -250,6 +252,7 @@ inline constexpr FrameBufferKind kFrameBuffers[] = {
     {3, Dir::Out, 1}, {12, Dir::Out, 4}, {12, Dir::Out, 4}, {12, Dir::Out, 4},
     {kHistoryBytes, Dir::In, 16}, {kHistoryBytes, Dir::Out, 16}, {8, Dir::Out, 4}, {4, Dir::Out, 4},
     {4, Dir::In, 4}, {12, Dir::Out, 4},
+    {1, Dir::In, 1}, {1, Dir::Out, 1},
     {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {4, Dir::In, 4, true}, {1, Dir::In, 1, true},
     {3, Dir::Out, 1, true}, {1, Dir::In, 1}, {4, Dir::Out, 4}};
 constexpr size_t kFrameBufferCount = sizeof(FrameBuffers) / sizeof(void*);
@@ -283,10 +286,12 @@ struct FrameScratch {
     DsrtAccum acc{};
     DsrtDenoiseGuides guides{};
     DevBuf<int32_t> prim_id;
-    DsrtGBuffer gb{};                                                  // the guides' four channels and, `with_prim_id`, that one
-    int init(size_t px, bool counts, bool with_guides, bool with_prim_id = false) {
+    DevBuf<uint8_t> flags;
+    DsrtGBuffer gb{};                                                  // the guides' four channels and, `with_prim_id` / `with_flags`, those
+    int init(size_t px, bool counts, bool with_guides, bool with_prim_id = false, bool with_flags = false) {
         int rc;
         if (with_prim_id) { if ((rc = prim_id.alloc(px))) return rc; gb.prim_id = prim_id.p; }
+        if (with_flags) { if ((rc = flags.alloc(px))) return rc; gb.flags = flags.p; }
         if ((rc = sum.alloc(px * 3)) || (rc = sq.alloc(px * 3)) || (counts && (rc = n.alloc(px)))) return rc;
         if (with_guides && ((rc = normal.alloc(px * 3)) || (rc = position.alloc(px * 3)) || (rc = albedo.alloc(px * 3)) || (rc = range.alloc(px)))) return rc;
         HIP_TRY(hipMemset(sum.p, 0, px * 3 * sizeof(unsigned long long)));

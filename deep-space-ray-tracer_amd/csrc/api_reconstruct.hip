@@ -35,6 +35,9 @@ int check_frame_table(const char* fn, const Staged (&s)[kFrameBufferCount], size
 struct TemporalInput {
     const GPUCamera* prev_camera; const float* prev; float* next; const DsrtTemporal* tp; float* prev_xy; float* weight;
     bool bodies = false; const DsrtBodyMotion* motion = nullptr; float* prev_position = nullptr;
+    // `shaded`: the call is dsrt_denoise_temporal_shaded, with its shading (required then; flags where the form has its buffers), its optional status output, and
+    // a motion that may be null (`bodies` says whether it is given)
+    bool shaded = false; const DsrtTemporalShading* shading = nullptr; uint8_t* status = nullptr;
 };
 
 int check_denoise_params(const char* fn, const DsrtDenoise* dn) {
@@ -58,7 +61,8 @@ int check_temporal_params(const char* fn, const DsrtTemporal* tp) {
 FrameBuffers denoise_buffers(const DsrtAccum& acc, const uint32_t* n, const DsrtDenoiseGuides& g, const TemporalInput* t, const void* rgb8, const void* f32, const void* linear, const void* var) {
     return FrameBuffers{acc.sum, acc.sum_sq, n, g.normal, g.position, g.albedo, g.range, rgb8, f32, linear, var,
                         t ? t->prev : nullptr, t ? t->next : nullptr, t ? t->prev_xy : nullptr, t ? t->weight : nullptr,
-                        t && t->motion ? t->motion->prim_id : nullptr, t ? t->prev_position : nullptr};
+                        t && t->motion ? t->motion->prim_id : nullptr, t ? t->prev_position : nullptr,
+                        t && t->shading ? t->shading->flags : nullptr, t ? t->status : nullptr};
 }
 
 // Everything dsrt_denoise_accumulated and (with `t`) dsrt_denoise_temporal refuse, before anything is launched or written; the same for the host forms' host pointers.
@@ -66,6 +70,11 @@ int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* 
                   const TemporalInput* t, const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
     if (!ctx || !desc || !acc || !guides || !dn) return accum_fail(fn, "null argument");
     if (t && t->bodies) if (int rc = check_body_motion(fn, t->motion)) return rc;
+    if (t && t->shaded) {
+        if (!t->shading || !t->shading->flags) return accum_fail(fn, "null argument (DsrtTemporalShading or its flags)");
+        if (t->shading->edge_guard != 0 && t->shading->edge_guard != 1) return accum_fail(fn, "edge_guard must be 0 or 1");
+        if (t->prev_position && !t->motion) return accum_fail(fn, "prev_position needs a motion");
+    }
     if (!acc->sum || !acc->sum_sq) return accum_fail(fn, "DsrtAccum.sum or sum_sq is NULL (the filter is guided by the variance: both are required)");
     if (!guides->normal || !guides->position || !guides->albedo || !guides->range) return accum_fail(fn, "a guide channel is NULL (normal, position, albedo and range are required)");
     if (int rc = check_frame_desc(fn, desc, false, true)) return rc;
@@ -79,8 +88,9 @@ int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* 
     if ((t->prev_camera != nullptr) != (t->prev != nullptr)) return accum_fail(fn, "the previous camera and the previous history go together: both NULL (first frame) or both given");
     if (!t->next) return accum_fail(fn, "the next history is NULL (it is required)");
     if (int rc = check_temporal_params(fn, t->tp)) return rc;
-    return check_frame_table(fn, s, kFrameTemporal, kFrameUpscale, "the next history, prev_xy, weight or prev_position overlaps an input or the previous history",
-                             "the next history, prev_xy, weight or prev_position overlaps another output", "an output range overlaps the previous history or prim_id");
+    return check_frame_table(fn, s, kFrameTemporal, kFrameUpscale, "the next history, prev_xy, weight, prev_position or status overlaps an input or the previous history",
+                             "the next history, prev_xy, weight, prev_position or status overlaps another output",
+                             "an output range overlaps the previous history, prim_id or flags");
 }
 
 // dsrt_denoise_accumulated and dsrt_denoise_temporal: the checks, then prepare, the temporal stage if there is one, the iterations, output.
@@ -110,15 +120,18 @@ int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, c
             for (int k = 0; k < 7; ++k) { a.cam[3 * k] = v[k].x; a.cam[3 * k + 1] = v[k].y; a.cam[3 * k + 2] = v[k].z; }
         }
         a.alpha_min = t->tp->alpha_min; a.normal_cos_min = t->tp->normal_cos_min; a.plane_tol = t->tp->plane_tol; a.min_support = t->tp->min_support;
-        if (t->bodies) {
-            BodyMotionTable tab;                                                      // (the motion's host arrays are read here, before the call returns)
-            pack_body_motion(*t->motion, tab);
-            BodyMotionArgs mo;
+        if (t->bodies || t->shaded) {
+            BodyMotionArgs mo;                                                        // (all zero without a motion: no prim_id, no body moved)
             std::memset(&mo, 0, sizeof mo);
-            mo.prim_id = t->motion->prim_id; mo.prev_position = t->prev_position; mo.moved = tab.moved;
-            static_assert(sizeof mo.first == sizeof tab.first && sizeof mo.count == sizeof tab.count && sizeof mo.poses == sizeof tab.poses, "BodyMotionArgs carries BodyMotionTable");
-            std::memcpy(mo.first, tab.first, sizeof mo.first); std::memcpy(mo.count, tab.count, sizeof mo.count); std::memcpy(mo.poses, tab.poses, sizeof mo.poses);
-            HIP_TRY(launch_temporal_bodies(a, mo, stream));
+            if (t->bodies) {
+                BodyMotionTable tab;                                                  // (the motion's host arrays are read here, before the call returns)
+                pack_body_motion(*t->motion, tab);
+                mo.prim_id = t->motion->prim_id; mo.prev_position = t->prev_position; mo.moved = tab.moved;
+                static_assert(sizeof mo.first == sizeof tab.first && sizeof mo.count == sizeof tab.count && sizeof mo.poses == sizeof tab.poses, "BodyMotionArgs carries BodyMotionTable");
+                std::memcpy(mo.first, tab.first, sizeof mo.first); std::memcpy(mo.count, tab.count, sizeof mo.count); std::memcpy(mo.poses, tab.poses, sizeof mo.poses);
+            }
+            if (t->shaded) HIP_TRY(launch_temporal_shaded(a, mo, ShadingArgs{t->shading->flags, t->status, t->shading->edge_guard}, stream));
+            else HIP_TRY(launch_temporal_bodies(a, mo, stream));
         } else {
             HIP_TRY(launch_temporal(a, stream));
         }
@@ -140,8 +153,11 @@ int denoise_to_host(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc
         const DsrtDenoiseGuides g{(const float*)m.normal, (const float*)m.position, (const float*)m.albedo, (const float*)m.range};
         DsrtBodyMotion motion{};                                                      // the caller's, with prim_id's mirror
         if (ht && ht->bodies) { motion = *ht->motion; motion.prim_id = (const int32_t*)m.prim_id; }
+        DsrtTemporalShading shading{};                                                // ... and with flags' mirror
+        if (ht && ht->shaded) { shading = *ht->shading; shading.flags = (const uint8_t*)m.shade_flags; }
         const TemporalInput t{ht ? ht->prev_camera : nullptr, (const float*)m.history_prev, (float*)m.history_next, ht ? ht->tp : nullptr, (float*)m.prev_xy, (float*)m.weight,
-                              ht && ht->bodies, ht && ht->bodies ? &motion : nullptr, (float*)m.prev_position};
+                              ht && ht->bodies, ht && ht->bodies ? &motion : nullptr, (float*)m.prev_position,
+                              ht && ht->shaded, ht && ht->shaded ? &shading : nullptr, (uint8_t*)m.status};
         return denoise_impl(fn, ctx, desc, &acc, samples_done, (const uint32_t*)m.n, &g, ht ? &t : nullptr, dn, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
                             (float*)m.var, nullptr);
     });
@@ -170,6 +186,9 @@ int render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int sp
         int r;
         if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &f.acc, nullptr, stats ? stats : &local))) return r;
         if ((r = dsrt_render_gbuffer(ctx, desc, &f.gb, nullptr, nullptr))) return r;
+        if (t && t->shaded)
+            return dsrt_denoise_temporal_shaded(ctx, desc, &f.acc, spp, nullptr, &f.guides, t->motion, t->shading, t->prev_camera, t->prev, t->next, t->tp, dn, (uint8_t*)m.rgb8,
+                                                (float*)m.f32, (float*)m.linear, (float*)m.var, (float*)m.prev_xy, nullptr, nullptr, nullptr, nullptr);
         if (t && t->bodies)
             return dsrt_denoise_temporal_bodies(ctx, desc, &f.acc, spp, nullptr, &f.guides, t->motion, t->prev_camera, t->prev, t->next, t->tp, dn, (uint8_t*)m.rgb8,
                                                 (float*)m.f32, (float*)m.linear, (float*)m.var, (float*)m.prev_xy, nullptr, nullptr, nullptr);
@@ -317,6 +336,35 @@ int dsrt_denoise_temporal_bodies_to_host(DsrtContext* ctx, const DsrtRenderDesc*
     });
 }
 
+int dsrt_denoise_temporal_shaded(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                                 const DsrtBodyMotion* motion, const DsrtTemporalShading* shading, const GPUCamera* prev_camera, const float* d_history_prev,
+                                 float* d_history_next, const DsrtTemporal* tp, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var,
+                                 float* d_prev_xy, float* d_weight, float* d_prev_position, uint8_t* d_status, void* stream_v) {
+    return dsrt::guarded("dsrt_denoise_temporal_shaded", [&]() -> int {
+    const TemporalInput t{prev_camera, d_history_prev, d_history_next, tp, d_prev_xy, d_weight, motion != nullptr, motion, d_prev_position, true, shading, d_status};
+    return denoise_impl("dsrt_denoise_temporal_shaded", ctx, desc, acc, samples_done, d_n, guides, &t, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v);
+    });
+}
+
+int dsrt_denoise_temporal_shaded_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n,
+                                         const DsrtDenoiseGuides* h_guides, const DsrtBodyMotion* motion, const DsrtTemporalShading* shading, const GPUCamera* prev_camera,
+                                         const float* h_history_prev, float* h_history_next, const DsrtTemporal* tp, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32,
+                                         float* h_linear, float* h_var, float* h_prev_xy, float* h_weight, float* h_prev_position, uint8_t* h_status) {
+    return dsrt::guarded("dsrt_denoise_temporal_shaded_to_host", [&]() -> int {
+    const TemporalInput ht{prev_camera, h_history_prev, h_history_next, tp, h_prev_xy, h_weight, motion != nullptr, motion, h_prev_position, true, shading, h_status};
+    return denoise_to_host("dsrt_denoise_temporal_shaded_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, &ht, dn, h_rgb8, h_f32, h_linear, h_var);
+    });
+}
+
+int dsrt_ctx_set_temporal_shading(DsrtContext* ctx, int mode) {
+    if (!ctx) { set_error("dsrt_ctx_set_temporal_shading: null context"); return DSRT_ERR_INVALID; }
+    if (mode < 0 || mode > 2) { set_error("dsrt_ctx_set_temporal_shading: mode must be 0 (off), 1 (the tap test) or 2 (with the edge guards)"); return DSRT_ERR_INVALID; }
+    ctx->tp_shading = mode;
+    return DSRT_OK;
+}
+
+int dsrt_ctx_temporal_shading(const DsrtContext* ctx) { return ctx ? ctx->tp_shading : 0; }
+
 int dsrt_ctx_set_temporal_bodies(DsrtContext* ctx, int on) {
     if (!ctx) { set_error("dsrt_ctx_set_temporal_bodies: null context"); return DSRT_ERR_INVALID; }
     ctx->tp_bodies = on != 0;
@@ -349,7 +397,8 @@ int dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc
     // with dsrt_ctx_set_temporal_bodies and a scene that has bodies: the motion stage, cur = the resident scene's poses, prev = this context's last temporal frame's
     BodiesResident* bd = ctx->tp_bodies && ctx->scene->bodies ? ctx->scene->bodies.get() : nullptr;
     FrameScratch f;
-    if ((rc = f.init(px, false, true, bd != nullptr))) return rc;
+    const int shading_mode = ctx->tp_shading;                                         // with dsrt_ctx_set_temporal_shading: the G-buffer's flags as well, and the stage that follows shading
+    if ((rc = f.init(px, false, true, bd != nullptr, shading_mode != 0))) return rc;
     if (fresh) ctx->tp_valid = false;                                                 // (growing does not keep the contents: a sequence of another size is over either way)
     for (DevBuf<float4>& h : ctx->tp_hist) if ((rc = h.grow(px * 4))) return rc;      // (only this call, which is synchronous, uses them: nothing in flight reads them)
     const GPUCamera camera = ctx->frame.camera, prev_camera = ctx->tp_camera;
@@ -359,8 +408,9 @@ int dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDesc
         std::memcpy(poses_cur, bd->host_poses, sizeof poses_cur);
         motion = DsrtBodyMotion{bd->n_bodies, bd->first_tri.data(), bd->num_tris.data(), fresh ? poses_cur : ctx->tp_poses, poses_cur, f.prim_id.p};
     }
+    const DsrtTemporalShading shading{f.flags.p, shading_mode == 2 ? 1 : 0};
     const TemporalInput t{fresh ? nullptr : &prev_camera, fresh ? nullptr : (const float*)ctx->tp_hist[ctx->tp_cur].p, (float*)ctx->tp_hist[fresh ? 0 : ctx->tp_cur ^ 1].p, tp,
-                          nullptr, nullptr, bd != nullptr, bd ? &motion : nullptr, nullptr};
+                          nullptr, nullptr, bd != nullptr, bd ? &motion : nullptr, nullptr, shading_mode != 0, shading_mode ? &shading : nullptr, nullptr};
     if ((rc = render_denoised_to_host(ctx, desc, spp, f, &t, dn, h_rgb8, h_f32, h_linear, h_var, h_prev_xy, stats))) return rc;
     ctx->tp_cur = fresh ? 0 : ctx->tp_cur ^ 1;
     if (ctx->scene->bodies) std::memcpy(ctx->tp_poses, ctx->scene->bodies->host_poses, sizeof ctx->tp_poses);      // (whatever the switch says now: it may be set before the next frame)

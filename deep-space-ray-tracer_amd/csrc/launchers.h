@@ -85,6 +85,11 @@ struct BodyMotionArgs {
     float4 poses[kMaxBodies * 6];
 };
 hipError_t launch_temporal_bodies(const TemporalArgs& a, const BodyMotionArgs& mo, hipStream_t stream);
+// ... and with the sun state (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING), a third kernel argument; the other two stay as they are.  flags: the
+// current G-buffer's u8 channel; status: the optional byte per pixel; edge_guard 0 or 1.  mo.prim_id null: a static scene (every pixel body 0; moved = 0, and
+// prev_position null).
+struct ShadingArgs { const uint8_t* flags; uint8_t* status; int edge_guard; };
+hipError_t launch_temporal_shaded(const TemporalArgs& a, const BodyMotionArgs& mo, const ShadingArgs& sh, hipStream_t stream);
 
 // upscale_kernel.hip (include/dsrt.h, UPSCALER).  The LOW-resolution frame packed for the taps, one 16-byte record per low-resolution pixel each: {c.rgb, range},
 // {v.rgb, flags as a bit pattern}, {N, 0}, {X, 0}, {A, 0}.  pack fills them (var and flags may be null: zeros); the upscale launch reads them and the OUTPUT

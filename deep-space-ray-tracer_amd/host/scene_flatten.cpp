@@ -164,6 +164,7 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_UPSCALE_GUIDES: return sizeof(DsrtUpscaleGuides);
         case DSRT_SIZEOF_UPSCALE: return sizeof(DsrtUpscale);
         case DSRT_SIZEOF_BODY_MOTION: return sizeof(DsrtBodyMotion);
+        case DSRT_SIZEOF_TEMPORAL_SHADING: return sizeof(DsrtTemporalShading);
         default: return 0;
     }
 }

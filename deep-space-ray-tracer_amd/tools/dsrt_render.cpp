@@ -39,6 +39,8 @@
 //     one set of poses, so such a run renders one launch per frame.  Does not combine with --bvh sah|lbvh, --fast or --certified-tree.
 //     With --denoise --temporal a pose update starts the history afresh unless --follow-bodies is given: then the history follows the bodies (include/dsrt.h,
 //     TEMPORAL ACCUMULATION WITH BODIES: dsrt_ctx_set_temporal_bodies), and --flow is flow ground truth that includes their motion.
+//   * --follow-shading (with --denoise --temporal, with or without --follow-bodies): the history keeps every surface point's sun state and gives up what lies across
+//     or next to a moved shadow edge (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING: dsrt_ctx_set_temporal_shading, mode 2).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,7 +73,7 @@ int main(int argc, char** argv) {
     int width = 800, height = 450, spp = 1000, depth = 50, first = 0, count = -1, rng_mode = 0, math_mode = 0, passes = 0;
     int adaptive_passes = 8, adaptive_min = 2;
     float adaptive_tol = 0.0f, adaptive_floor = 0.0f;
-    bool adaptive = false, adaptive_detail = false, denoise = false, temporal = false, flow = false, follow_bodies = false;
+    bool adaptive = false, adaptive_detail = false, denoise = false, temporal = false, flow = false, follow_bodies = false, follow_shading = false;
     int denoise_iterations = -1;                                    // -1: the library's default
     bool upscale = false;
     int upscale_factor = 4;                                         // the reference's scale (src/main.cpp:444)
@@ -114,6 +116,7 @@ int main(int argc, char** argv) {
         else if (a == "--temporal") temporal = true;                // with --denoise: reprojected frame history (include/dsrt.h, TEMPORAL ACCUMULATION)
         else if (a == "--flow") flow = true;                        // with --temporal: <frame>_flow.pfm, every pixel's displacement from the previous frame
         else if (a == "--follow-bodies") follow_bodies = true;      // with --body, --denoise and --temporal: the history follows the bodies (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES)
+        else if (a == "--follow-shading") follow_shading = true;    // with --denoise and --temporal: the history follows the sun state (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING)
         else if (a == "--body") bodies.emplace_back(next("--body"), 1.0);
         else if (a == "--body-scale") {
             const double sc = std::atof(next("--body-scale"));
@@ -125,7 +128,7 @@ int main(int argc, char** argv) {
             upscale = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') upscale_factor = std::atoi(argv[++i]);
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
@@ -150,6 +153,7 @@ int main(int argc, char** argv) {
     if (denoise && spp < 2) { std::fprintf(stderr, "dsrt_render: --denoise needs --spp 2 or more\n"); return 2; }
     if (temporal && !denoise) { std::fprintf(stderr, "dsrt_render: --temporal needs --denoise\n"); return 2; }
     if (flow && !temporal) { std::fprintf(stderr, "dsrt_render: --flow needs --temporal\n"); return 2; }
+    if (follow_shading && (!denoise || !temporal)) { std::fprintf(stderr, "dsrt_render: --follow-shading needs --denoise and --temporal\n"); return 2; }
     if (follow_bodies && (bodies.empty() || !denoise || !temporal)) { std::fprintf(stderr, "dsrt_render: --follow-bodies needs --body, --denoise and --temporal\n"); return 2; }
     if ((passes != 0 || variance) && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --passes and --variance need --rng-mode 1 (or --fast)\n"); return 2; }
     if (passes < 0 || passes > std::max(spp, 1)) { std::fprintf(stderr, "dsrt_render: --passes must be between 1 and --spp\n"); return 2; }
@@ -220,6 +224,7 @@ int main(int argc, char** argv) {
     DsrtContext* ctx = nullptr;
     if (dsrt_ctx_create(0, &ctx) != DSRT_OK) return fail("creating the device context");
     if (follow_bodies && dsrt_ctx_set_temporal_bodies(ctx, 1) != DSRT_OK) return fail("setting the context to follow the bodies");
+    if (follow_shading && dsrt_ctx_set_temporal_shading(ctx, 2) != DSRT_OK) return fail("setting the context to follow the shading");
     if (certified && dsrt_ctx_set_certified_tree(ctx, 1) != DSRT_OK) return fail("asking for the certified second tree");
     // The reference's loop renders frame after frame (src/main.cpp:310-431).  Here the poses of a run are rendered as batch launches
     // (dsrt_render_batch_to_host: up to 32 frames as ONE pool of work, include/dsrt.h) and written out in pose order afterwards: each

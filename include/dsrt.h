@@ -58,6 +58,7 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_TEMPORAL    14
 #define DSRT_SIZEOF_UPSCALE_GUIDES 15
 #define DSRT_SIZEOF_UPSCALE     16
+#define DSRT_SIZEOF_TEMPORAL_SHADING 19
 #define DSRT_SIZEOF_BODY_MOTION 18   /* (17 is left unassigned and answers 0: tests/test_upscale_host.py holds it to that as the first unknown index of its day) */
 size_t dsrt_sizeof(int which);
 
@@ -793,8 +794,8 @@ int  dsrt_render_denoised_temporal_to_host(DsrtContext* ctx, const DsrtRenderDes
  * With all poses equal the stage is the static one, bit for bit.  A body that enters or leaves the view, or that uncovers the station behind it, needs nothing of its
  * own: the record at the projected place shows another surface, and the tap tests and the guard reject it.
  * WHAT IS NOT FOLLOWED: SHADING.  A moving body's shadow moves across static pixels, and a body's own radiance changes as it turns to the Sun: the history lags there,
- * and alpha_min is the only guard.  OUT OF SCOPE HERE: carrying the G-buffer's sun-visibility bit in a spare word of the history record, to reject taps across a moved
- * shadow edge -- it changes the history record.
+ * and alpha_min is the only guard of THIS stage.  TEMPORAL ACCUMULATION THAT FOLLOWS SHADING below carries the G-buffer's sun-visibility bit in the spare word of
+ * the history record and rejects taps across a changed bit.
  *
  * dsrt_body_motion_host: the CPU statement of the motion rule over n points, no GPU involved: prim_id (HOST, n entries), normal and position (3 floats per point)
  *   give prev_normal = N' and prev_position = X' (either may be NULL; they may not overlap the inputs).  DSRT_ERR_INVALID: what is refused of a DsrtBodyMotion below,
@@ -831,6 +832,60 @@ int  dsrt_denoise_temporal_bodies_to_host(DsrtContext* ctx, const DsrtRenderDesc
                                           float* h_var, float* h_prev_xy, float* h_weight, float* h_prev_position);
 int  dsrt_ctx_set_temporal_bodies(DsrtContext* ctx, int on);
 int  dsrt_ctx_temporal_bodies(const DsrtContext* ctx);
+
+/*
+ * TEMPORAL ACCUMULATION THAT FOLLOWS SHADING (on top of TEMPORAL ACCUMULATION WITH BODIES and the G-BUFFER): the two stages above follow geometry.  When a body's
+ * shadow crosses the station, or a body turns through its terminator, the history of a surface point holds radiance under the other sun state, and blending it in
+ * is worse than the frame's own samples.  This stage keeps every record's SUN STATE -- the G-buffer's sun-visibility bit of the frame that wrote it -- in the spare
+ * word after X, rejects taps of the other state, and (edge_guard) voids the history next to a shadow edge of either frame: a pixel that straddles the edge keeps its
+ * pixel-centre bit while the edge moves by a fraction of a pixel.  tests/_shading_model.py reproduces every bit.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written.  The stage is TEMPORAL ACCUMULATION WITH
+ * BODIES with the additions below; a NULL `motion` means every pixel is body 0 (N' = N_p, X' = X_p): the static stage.
+ *   Input: flags, the G-buffer's u8 channel of the CURRENT frame (DSRT_GB_HIT = 1, DSRT_GB_SUN_VISIBLE = 8), one byte per pixel.
+ *   Sun state of a pixel:  s_p = range_p <= FLT_MAX ? ((flags_p & 8) ? 2.0f : 1.0f) : +0.0f              (2 lit, 1 in shadow, 0 unknown)
+ *   Record: next[p] = {c', m', v', 0, N_p, 0, X_p, s_p}: word 15 holds the state, words 7 and 11 stay +0.  A record whose word 15 is 0 (-0 too) is UNKNOWN and matches
+ *     every state: a record written by dsrt_denoise_temporal or dsrt_denoise_temporal_bodies is one, so a sequence may switch this stage on between two frames.
+ *   State mismatch of a record q:  mis(q) = !(s_q == 0.0f || s_q == s_p)                                    (a NaN in the word mismatches; so does any stray value)
+ *   Taps: after the plane test a tap is also skipped when mis(q).  Two more sums run over the taps that pass the three tests above it, whatever their state:
+ *       swg += bq;   seen_g |= bq >= 0.99f
+ *     found_geometry = swg >= min_support && (seen_g || !guarded): the decision of the stage above.  sw and seen count the taps that pass all four tests.
+ *   Previous-frame edge, over the occluder guard's 4 x 4 block (the part of it inside the image):  edge_prev = any record with m_q > 0 and mis(q).
+ *   Current-frame edge, over the 3 x 3 block around p (the part of it inside the image):  edge_cur = any r with (flags_r & 1) and (flags_r & 8) != (flags_p & 8).
+ *   Decision:  found = sw >= min_support && (seen || !guarded) && !(edge_guard && (edge_prev || edge_cur)).  The blend is unchanged, over the taps of sw.
+ *   d_status (optional, one u8 per pixel): bit 0 projected; bit 1 found; bit 2 found_geometry; bit 3 edge_prev; bit 4 edge_cur.  Bits 1 .. 4 are 0 for a pixel that
+ *     is not both projected and filterable; bits 3 and 4 are reported whatever edge_guard says (edge_guard 0 only keeps them out of the decision).  "Lost to shading"
+ *     is bit 2 without bit 1; of those, "lost to an edge guard" are the ones whose taps alone (the same call with edge_guard 0) would have found history.
+ *   d_prev_xy, d_weight and d_prev_position are as in the stage above (d_prev_position needs a motion).
+ * With flags of one sun state throughout and a history whose word 15 is 0, the stage is the one above bit for bit (word 15 of `next` aside).
+ * WHAT IS STILL NOT FOLLOWED: a Sun that moves in the model frame (every surface's radiance changes with the cosine while no bit flips); indirect light from a moved
+ * body (a lit body brightens the station next to it); view-dependent materials (metal, glass).  alpha_min remains the guard against those.  A silhouette pixel's
+ * bilinear footprint still mixes partial background coverage, as in TEMPORAL ACCUMULATION.
+ *
+ * dsrt_denoise_temporal_shaded: dsrt_denoise_temporal_bodies with `shading` after `motion` and d_status after d_prev_position; `motion` may be NULL.  Stream order,
+ *   waiting, working memory and "needs no scene" are unchanged.  DSRT_ERR_INVALID: what dsrt_denoise_temporal_bodies refuses (a NULL motion excepted); a NULL shading
+ *   or NULL flags; edge_guard outside {0, 1}; d_prev_position without a motion; flags or d_status overlapping an output or each other, d_status overlapping an input
+ *   or the previous history.  A refused call touches no buffer.
+ * dsrt_denoise_temporal_shaded_to_host: the same from HOST buffers into HOST buffers (flags and status too), synchronously.
+ * dsrt_ctx_set_temporal_shading / dsrt_ctx_temporal_shading: the switch of the convenience form, per context (a clone has its own, off): 0 off (the default), 1 the
+ *   tap test only (edge_guard 0), 2 with the edge guards; another mode is DSRT_ERR_INVALID.  On: dsrt_render_denoised_temporal_to_host asks its G-buffer for flags as
+ *   well (that channel traces the shadow rays) and runs the stage above, with the motion when dsrt_ctx_set_temporal_bodies is on and the scene has bodies, without one
+ *   otherwise.  The result is exactly the explicit chain of dsrt_denoise_temporal_shaded calls.  The switch may change between two frames of a sequence.
+ */
+typedef struct DsrtTemporalShading {
+    const uint8_t* flags;       /* DEVICE (HOST in the host form), one per pixel: the current G-buffer's flags channel */
+    int edge_guard;             /* 0: the tap test only; 1: history next to a sun-state edge of either frame is voided too */
+} DsrtTemporalShading;
+int  dsrt_denoise_temporal_shaded(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                                  const DsrtBodyMotion* motion /* NULL: static scene */, const DsrtTemporalShading* shading, const GPUCamera* prev_camera /* HOST */,
+                                  const float* d_history_prev, float* d_history_next, const DsrtTemporal* temporal, const DsrtDenoise* params, uint8_t* d_rgb8, float* d_f32,
+                                  float* d_linear, float* d_var, float* d_prev_xy, float* d_weight, float* d_prev_position, uint8_t* d_status, void* stream);
+int  dsrt_denoise_temporal_shaded_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n,
+                                          const DsrtDenoiseGuides* h_guides, const DsrtBodyMotion* motion, const DsrtTemporalShading* shading, const GPUCamera* prev_camera,
+                                          const float* h_history_prev, float* h_history_next, const DsrtTemporal* temporal, const DsrtDenoise* params, uint8_t* h_rgb8,
+                                          float* h_f32, float* h_linear, float* h_var, float* h_prev_xy, float* h_weight, float* h_prev_position, uint8_t* h_status);
+int  dsrt_ctx_set_temporal_shading(DsrtContext* ctx, int mode);
+int  dsrt_ctx_temporal_shading(const DsrtContext* ctx);
 
 /*
  * UPSCALER (on top of the DENOISER and the G-BUFFER): a full-resolution frame out of a low-resolution render.  Joint bilateral upsampling (Kopf et al. 2007) whose

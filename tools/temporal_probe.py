@@ -9,7 +9,12 @@ One JSON line on stdout.
 and shifts between the two frames (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES), and on the second frame, in the same run,
     dsrt_denoise_temporal         with 0 iterations    (dsrt_temporal_kernel: the static stage on the same inputs)
     dsrt_denoise_temporal_bodies  with 0 iterations    (dsrt_temporal_bodies_kernel), without and with d_prev_position
-each less dsrt_denoise_accumulated with 0 iterations, and the ratio of the two kernels."""
+each less dsrt_denoise_accumulated with 0 iterations, and the ratio of the two kernels.
+
+--shading: the --bodies measurement as it stands, and in the same run, interleaved rep by rep (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING),
+    dsrt_denoise_temporal_shaded  with 0 iterations    (dsrt_temporal_shaded_kernel) at edge_guard 0 and 1, without and with d_status
+as ratios to dsrt_temporal_bodies_kernel; the shares of the pixels with geometric history that the status byte says are lost to the tap test and to the edge guards;
+and what the flags channel -- it traces the shadow rays -- adds to the G-buffer call of the convenience form (normal, position, albedo, range, prim_id)."""
 import json
 import os
 import statistics
@@ -36,7 +41,7 @@ def _timed(torch, calls, warm=3, reps=30):
     return ms, out
 
 
-def main_bodies():
+def main_bodies(shading=False):
     import numpy as np
     import torch
     import dsrt_amd as d
@@ -73,8 +78,11 @@ def main_bodies():
         acc.render(0)
         g = acc.guides()
         prim = torch.empty((H, W), dtype=torch.int32, device="cuda:0")
-        ctx.render_gbuffer(desc, {"prim_id": prim.data_ptr()}, stream=ctx._raw_stream(None))
-        if f == 0:
+        flags = torch.empty((H, W), dtype=torch.uint8, device="cuda:0")
+        ctx.render_gbuffer(desc, {"prim_id": prim.data_ptr(), "flags": flags.data_ptr()}, stream=ctx._raw_stream(None))
+        if f == 0 and shading:                                             # (the first frame's records carry their sun state; the two older kernels do not look at it)
+            ctx.denoise_temporal_shaded(desc, acc.sum, acc.sum_sq, g, flags, hist[0], (first, num, poses[0], poses[0], prim), 1, samples_done=spp, params=p0)
+        elif f == 0:
             ctx.denoise_temporal_bodies(desc, acc.sum, acc.sum_sq, g, (first, num, poses[0], poses[0], prim), hist[0], samples_done=spp, params=p0)
     torch.cuda.synchronize()
     mo = (first, num, poses[0], poses[1], prim)
@@ -85,6 +93,10 @@ def main_bodies():
         "temporal_bodies_prev_position_0_iterations": lambda: ctx.denoise_temporal_bodies(desc, acc.sum, acc.sum_sq, g, mo, hist[1], cams[0], hist[0], samples_done=spp, params=p0,
                                                                                           want_weight=True, want_prev_position=True),
     }
+    shaded = lambda guard, status: lambda: ctx.denoise_temporal_shaded(desc, acc.sum, acc.sum_sq, g, flags, hist[1], mo, guard, cams[0], hist[0], samples_done=spp,   # noqa: E731
+                                                                       params=p0, want_weight=True, want_status=status)
+    if shading:
+        calls.update({f"temporal_shaded_guard{guard}{'_status' if status else ''}_0_iterations": shaded(guard, status) for guard in (0, 1) for status in (False, True)})
     ms, _ = _timed(torch, calls)
     med = {k: statistics.median(x) for k, x in ms.items()}
     w_static = calls["temporal_0_iterations"]()[5]
@@ -96,6 +108,22 @@ def main_bodies():
            "history_share_on_the_body": {"static": float((w_static[on_body] > spp).float().mean()), "bodies": float((w_bodies[on_body] > spp).float().mean())},
            "ms_median": med, "ms_min": {k: min(x) for k, x in ms.items()}, "temporal_kernel_ms": k_static, "temporal_bodies_kernel_ms": k_bodies,
            "temporal_bodies_kernel_with_prev_position_ms": k_pos, "ratio_bodies_to_static": k_bodies / k_static, "ratio_with_prev_position": k_pos / k_static}
+    if shading:
+        res["ratio_shaded_to_bodies"] = {k[len("temporal_shaded_"):-len("_0_iterations")]: (med[k] - med["denoise_0_iterations"]) / k_bodies for k in calls if k.startswith("temporal_shaded_")}
+        st0, st1 = shaded(0, True)()[7], shaded(1, True)()[7]
+        torch.cuda.synchronize()
+        geo = (st1 & 4) != 0
+        res["status_shares_of_pixels_with_geometric_history"] = {
+            "pixels": int(geo.sum()), "share_of_image": float(geo.float().mean()), "keep_history": float(((st1 & 2) != 0)[geo].float().mean()),
+            "lost_to_shading": float(((st1 & 2) == 0)[geo].float().mean()), "lost_to_the_tap_test": float(((st0 & 2) == 0)[geo].float().mean()),
+            "lost_to_an_edge_guard": float((((st0 & 2) != 0) & ((st1 & 2) == 0))[geo].float().mean())}
+        # the G-buffer call of the convenience form, without and with the flags channel
+        chan = {k: torch.empty((H, W, 3) if k != "range" else (H, W), dtype=torch.float32, device="cuda:0") for k in ("normal", "position", "albedo", "range")}
+        base = {**{k: t.data_ptr() for k, t in chan.items()}, "prim_id": prim.data_ptr()}
+        gms, _ = _timed(torch, {"gbuffer_without_flags": lambda: ctx.render_gbuffer(desc, base, stream=ctx._raw_stream(None)),
+                                "gbuffer_with_flags": lambda: ctx.render_gbuffer(desc, {**base, "flags": flags.data_ptr()}, stream=ctx._raw_stream(None))})
+        res["gbuffer_ms_median"] = {k: statistics.median(x) for k, x in gms.items()}
+        res["gbuffer_flags_adds_ms"] = res["gbuffer_ms_median"]["gbuffer_with_flags"] - res["gbuffer_ms_median"]["gbuffer_without_flags"]
     print(json.dumps(res))
     ctx.close()
 
@@ -148,4 +176,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main_bodies() if "--bodies" in sys.argv[1:] else main()
+    main_bodies("--shading" in sys.argv[1:]) if {"--bodies", "--shading"} & set(sys.argv[1:]) else main()
