@@ -266,6 +266,40 @@ def denoise_defaults(**changes):
     return p
 
 
+def coverage_desc(pattern=None, samples=None):
+    """A DsrtCoverageDesc (include/dsrt.h, COVERAGE): dsrt_coverage_defaults' (DIAGONAL, 64) with `pattern` ("grid" / "diag" or capi.COVERAGE_*) and `samples`
+    (S of an S x S grid, or the n of the diagonal) applied.  A string "grid:S" / "diag:N" sets both."""
+    d = capi.DsrtCoverageDesc()
+    lib.dsrt_coverage_defaults(C.byref(d))
+    if isinstance(pattern, str) and ":" in pattern:
+        pattern, samples = pattern.split(":", 1)
+    if pattern is not None:
+        names = {"grid": capi.COVERAGE_GRID, "diag": capi.COVERAGE_DIAGONAL, "diagonal": capi.COVERAGE_DIAGONAL}
+        if isinstance(pattern, str) and pattern not in names:
+            raise ValueError(f"unknown coverage pattern {pattern!r}; known: {sorted(names)}")
+        d.pattern = names[pattern] if isinstance(pattern, str) else int(pattern)
+    if samples is not None:
+        d.samples = int(samples)
+    return d
+
+
+def coverage_classes(ranges):
+    """A DsrtCoverageClasses of up to 16 triangle ranges [(first, num), ...], e.g. HostScene.body_range(b) per body."""
+    ranges = list(ranges)
+    if len(ranges) > 16:
+        raise ValueError("at most 16 classes")
+    cl = capi.DsrtCoverageClasses()
+    cl.count = len(ranges)
+    for c, (first, num) in enumerate(ranges):
+        cl.first[c], cl.num[c] = int(first), int(num)
+    return cl
+
+
+def coverage_alpha_min():
+    """dsrt_denoise_coverage_alpha_min: the default alpha_min of the coverage-aware denoiser."""
+    return float(lib.dsrt_denoise_coverage_alpha_min())
+
+
 def temporal_defaults(**changes):
     """dsrt_temporal_defaults: the DsrtTemporal the library fills (alpha_min, normal_cos_min, plane_tol, min_support), with `changes` applied."""
     p = capi.DsrtTemporal()
@@ -546,6 +580,44 @@ class Context:
         _check(lib.dsrt_render_gbuffer_to_host(self._h, C.byref(desc), C.byref(gb), None), "dsrt_render_gbuffer_to_host")
         return out
 
+    def _coverage_struct(self, ptrs, rep):
+        unknown = (set(ptrs) - set(capi.COVERAGE_CHANNELS)) | (set(rep or {}) - set(capi.GBUFFER_CHANNELS))
+        if unknown:
+            raise ValueError(f"unknown coverage channel(s) {sorted(unknown)}; known: {list(capi.COVERAGE_CHANNELS)} and, in rep, {list(capi.GBUFFER_CHANNELS)}")
+        cov = capi.DsrtCoverage(**{k: C.c_void_p(int(v)) for k, v in ptrs.items() if v})
+        cov.rep = DsrtGBuffer(**{k: C.c_void_p(int(v)) for k, v in (rep or {}).items() if v})
+        return cov
+
+    def render_coverage(self, desc, cov_desc=None, ptrs=None, rep=None, classes=None, stream=None, want_stats=False):
+        """dsrt_render_coverage: the sub-pixel coverage of the current camera into DEVICE buffers.  `ptrs` maps names of capi.COVERAGE_CHANNELS to device pointers
+        (e.g. torch tensors' data_ptr()), `rep` names of capi.GBUFFER_CHANNELS to those of the representative's record; what is not named is not written.
+        cov_desc: coverage_desc() (default DIAGONAL 64); classes: coverage_classes([...]), needed for class_hits.  Asynchronous on `stream` unless want_stats."""
+        cd = coverage_desc() if cov_desc is None else cov_desc
+        cov = self._coverage_struct(ptrs or {}, rep)
+        st = DsrtStats() if want_stats else None
+        _check(lib.dsrt_render_coverage(self._h, C.byref(desc), C.byref(cd), C.byref(classes) if classes is not None else None, C.byref(cov),
+                                        C.c_void_p(stream) if stream else None, C.byref(st) if st is not None else None), "dsrt_render_coverage")
+        return st
+
+    def coverage_to_host(self, desc, cov_desc=None, channels=None, rep=(), classes=None):
+        """dsrt_render_coverage_to_host: {channel: numpy array (H, W)} for `channels` (default: all of capi.COVERAGE_CHANNELS; class_hits, shape (H, W, count), only
+        with `classes`), and under "rep" the dict of the representative's G-buffer channels named in `rep` (True: all of them)."""
+        cd = coverage_desc() if cov_desc is None else cov_desc
+        names = [n for n in capi.COVERAGE_CHANNELS if n != "class_hits" or classes is not None] if channels is None else list(channels)
+        rep_names = list(capi.GBUFFER_CHANNELS) if rep is True else list(rep or ())
+        H, W = desc.height, desc.width
+        out = {n: np.zeros((H, W) + ((classes.count,) if n == "class_hits" and classes is not None else ()), capi.COVERAGE_CHANNELS[n]) for n in names}
+        out_rep = {}
+        for n in rep_names:
+            dt, comps = capi.GBUFFER_CHANNELS[n]
+            out_rep[n] = np.zeros((H, W) + ((comps,) if comps > 1 else ()), dt)
+        cov = self._coverage_struct({n: a.ctypes.data for n, a in out.items()}, {n: a.ctypes.data for n, a in out_rep.items()})
+        _check(lib.dsrt_render_coverage_to_host(self._h, C.byref(desc), C.byref(cd), C.byref(classes) if classes is not None else None, C.byref(cov), None),
+               "dsrt_render_coverage_to_host")
+        if rep_names:
+            out["rep"] = out_rep
+        return out
+
     def trace_rays(self, origins, dirs, t_min=None, t_max=None, any_hit=False, channels=None, stream=None, want_stats=False):
         """Ray queries on the resident scene (include/dsrt.h, dsrt_trace_rays): {channel: array} for `channels` (capi.RAY_HIT_CHANNELS; default all of
         them, or `flags` alone with any_hit=True), of shape (N,) or (N, comps).  origins / dirs are float32 (N, 3), t_min / t_max float32 (N,) or None, all
@@ -739,7 +811,7 @@ class Context:
             out[k] = self._device_tensor(x, _torch.float32, (desc.width * desc.height * comps, f"width*height*{comps}"), f"guide {k}")
         return out
 
-    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None, motion=None, shading=None):
+    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None, motion=None, shading=None, coverage=None):
         """denoise_accumulated and, with temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None), denoise_temporal: the outputs `wants` names.
         motion = (first_tri, num_tris, poses_prev, poses_cur, prim_id tensor): denoise_temporal_bodies.  shading = (flags tensor, edge_guard): denoise_temporal_shaded,
         with or without a motion."""
@@ -761,7 +833,10 @@ class Context:
         out = _outputs(desc, wants, sums.device)
         head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), _tensor_ptr(n), C.byref(gd))
         tail = (C.byref(params), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream)))
-        if temporal is None:
+        if coverage is not None:                                                           # (alpha tensor or None, alpha_min): denoise_accumulated_coverage
+            alpha = self._pixel_tensor(desc, coverage[0], _torch.float32, "alpha", required=False)
+            _check(lib.dsrt_denoise_accumulated_coverage(*head, _tensor_ptr(alpha), C.c_float(coverage[1]), *tail), "dsrt_denoise_accumulated_coverage")
+        elif temporal is None:
             _check(lib.dsrt_denoise_accumulated(*head, *tail), "dsrt_denoise_accumulated")
         elif shading is not None:
             m = keep = None
@@ -780,7 +855,7 @@ class Context:
                                              C.byref(tp), *tail), "dsrt_denoise_temporal")
         return tuple(out)
 
-    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None, motion=None, shading=None):
+    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None, motion=None, shading=None, coverage=None):
         """The same from numpy arrays into numpy arrays (temporal: (prev_camera, history_prev or None, DsrtTemporal or None); the next history is returned last)."""
         H, W = desc.height, desc.width
         S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
@@ -803,6 +878,10 @@ class Context:
         out = _outputs(desc, wants)
         head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), _array_ptr(cnt), C.byref(gd))
         tail = (C.byref(params), *map(_array_ptr, out))
+        if coverage is not None:
+            alpha = np.ascontiguousarray(coverage[0], np.float32).reshape(H, W) if coverage[0] is not None else None
+            _check(lib.dsrt_denoise_accumulated_coverage_to_host(*head, _array_ptr(alpha), C.c_float(coverage[1]), *tail), "dsrt_denoise_accumulated_coverage_to_host")
+            return tuple(out)
         if temporal is None:
             _check(lib.dsrt_denoise_accumulated_to_host(*head, *tail), "dsrt_denoise_accumulated_to_host")
             return tuple(out)
@@ -838,6 +917,32 @@ class Context:
                                     want_var=False):
         """dsrt_denoise_accumulated_to_host: the same from numpy arrays (uint64 sums (H, W, 3), uint32 counts (H, W), float32 guides) into numpy arrays."""
         return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var))
+
+    def denoise_accumulated_coverage(self, desc, sums, sum_sq, guides, alpha, alpha_min=None, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False,
+                                     want_linear=True, want_var=False, stream=None):
+        """dsrt_denoise_accumulated_coverage: denoise_accumulated with COVERAGE DEMODULATION -- `alpha` a float32 device tensor of width*height elements (the alpha of a
+        DIAGONAL render_coverage; None = the plain denoiser), `guides` usually that pass's rep channels.  alpha_min: default coverage_alpha_min()."""
+        alpha_min = coverage_alpha_min() if alpha_min is None else alpha_min
+        return self._denoise("denoise_accumulated_coverage", desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var), stream, coverage=(alpha, alpha_min))
+
+    def denoise_accumulated_coverage_to_host(self, desc, sums, sum_sq, guides, alpha, alpha_min=None, samples_done=None, n=None, params=None, want_rgb8=True,
+                                             want_f32=False, want_linear=True, want_var=False):
+        """dsrt_denoise_accumulated_coverage_to_host: the same from numpy arrays into numpy arrays."""
+        alpha_min = coverage_alpha_min() if alpha_min is None else alpha_min
+        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var),
+                                     coverage=(alpha, alpha_min))
+
+    def render_denoised_coverage_to_host(self, desc, cov_desc=None, alpha_min=None, params=None, want_f32=False, want_linear=True, want_var=False, want_alpha=False):
+        """dsrt_render_denoised_coverage_to_host: desc.spp samples, a DIAGONAL coverage pass and the coverage-aware filter: (rgb8, f32, linear, var, alpha, DsrtStats)."""
+        params = denoise_defaults() if params is None else params
+        alpha_min = coverage_alpha_min() if alpha_min is None else alpha_min
+        out = _outputs(desc, dict(rgb8=True, f32=want_f32, linear=want_linear, var=want_var))
+        alpha = np.zeros((desc.height, desc.width), np.float32) if want_alpha else None
+        st = DsrtStats()
+        _check(lib.dsrt_render_denoised_coverage_to_host(self._h, C.byref(desc), C.byref(cov_desc) if cov_desc is not None else None, C.c_float(alpha_min), C.byref(params),
+                                                         *map(_array_ptr, out), _array_ptr(alpha), C.byref(st)), "dsrt_render_denoised_coverage_to_host")
+        return (*out, alpha, st)
 
     def render_denoised_to_host(self, desc, params=None, want_f32=False, want_linear=True, want_var=False):
         """dsrt_render_denoised_to_host: desc.spp samples, the G-buffer of the current camera and the filter, into numpy arrays: (rgb8, f32, linear, var, DsrtStats)."""
@@ -1104,11 +1209,30 @@ class Accumulator:
         ctx.render_gbuffer(self.desc, {k: x.data_ptr() for k, x in g.items()}, stream=ctx._raw_stream(stream))
         return g
 
-    def denoise(self, params=None, guides=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, stream=None):
+    def coverage(self, cov_desc=None, ctx=None, stream=None):
+        """(alpha, guides) of a coverage pass over the context's current camera (Context.render_coverage; default DIAGONAL 64): alpha a float32 device tensor
+        (H, W), guides the representative's {"normal", "position", "albedo", "range"} -- what denoise(alpha=..., guides=...) takes."""
+        ctx = ctx or self.ctx
+        H, W, dev = self.desc.height, self.desc.width, self.sum.device
+        g = {k: _torch.empty((H, W, 3) if capi.GBUFFER_CHANNELS[k][1] == 3 else (H, W), dtype=_torch.float32, device=dev) for k in DENOISE_GUIDES}
+        alpha = _torch.empty((H, W), dtype=_torch.float32, device=dev)
+        ctx.render_coverage(self.desc, cov_desc, {"alpha": alpha.data_ptr()}, {k: x.data_ptr() for k, x in g.items()}, stream=ctx._raw_stream(stream))
+        return alpha, g
+
+    def denoise(self, params=None, guides=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, stream=None, alpha=None, alpha_min=None):
         """(rgb8, f32, linear, var) of the current sums through the variance-guided filter (Context.denoise_accumulated); needs moments=True.  Without
-        `guides` the G-buffer of the context's current camera is rendered first."""
+        `guides` the G-buffer of the context's current camera is rendered first.  alpha (a float32 device tensor, or True = a DIAGONAL 64 coverage pass of the
+        current camera, whose representatives then are the guides unless `guides` is given) / alpha_min: the coverage-aware filter (Context.denoise_accumulated_coverage)."""
         if self.sum_sq is None:
             raise ValueError("the denoiser is guided by the variance: Accumulator(..., moments=True)")
+        if alpha is not None:
+            if alpha is True:
+                alpha, rep_guides = self.coverage(stream=stream)
+                guides = rep_guides if guides is None else guides
+            guides = self.guides(stream=stream) if guides is None else guides
+            return self.ctx.denoise_accumulated_coverage(self.desc, self.sum, self.sum_sq, guides, alpha, alpha_min, samples_done=self.samples_done,
+                                                         n=self.n if self.samples_done is None else None, params=params, want_rgb8=want_rgb8, want_f32=want_f32,
+                                                         want_linear=want_linear, want_var=want_var, stream=stream)
         guides = self.guides(stream=stream) if guides is None else guides
         return self.ctx.denoise_accumulated(self.desc, self.sum, self.sum_sq, guides, samples_done=self.samples_done, n=self.n if self.samples_done is None else None,
                                             params=params, want_rgb8=want_rgb8, want_f32=want_f32, want_linear=want_linear, want_var=want_var, stream=stream)

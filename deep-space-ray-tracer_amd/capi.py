@@ -150,6 +150,22 @@ class DsrtTemporalShading(C.Structure):
     _fields_ = [("flags", C.c_void_p), ("edge_guard", C.c_int)]
 
 
+class DsrtCoverageDesc(C.Structure):
+    _fields_ = [("pattern", C.c_int), ("samples", C.c_int)]
+
+
+class DsrtCoverageClasses(C.Structure):
+    _fields_ = [("count", C.c_int), ("first", C.c_int * 16), ("num", C.c_int * 16)]
+
+
+class DsrtCoverage(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("hits", "alpha", "mask", "sun_hits", "sun_alpha", "sun_mask", "class_hits")] + [("rep", DsrtGBuffer)]
+
+
+# The coverage pass's own outputs (include/dsrt.h, COVERAGE): name -> numpy dtype, one element per pixel (class_hits: one per pixel and class).
+COVERAGE_CHANNELS = {"hits": "u1", "alpha": "<f4", "mask": "<u8", "sun_hits": "u1", "sun_alpha": "<f4", "sun_mask": "<u8", "class_hits": "u1"}
+COVERAGE_GRID, COVERAGE_DIAGONAL = 0, 1                                 # DSRT_COVERAGE_* of include/dsrt.h
+
 MAX_BODIES = 16                                                         # DSRT_MAX_BODIES of include/dsrt.h
 HISTORY_FLOATS = 16                                                     # per pixel of a temporal history buffer (include/dsrt.h, TEMPORAL ACCUMULATION)
 
@@ -189,6 +205,8 @@ EXPORTS = [
     "dsrt_scene_upload_bodies", "dsrt_scene_set_body_poses", "dsrt_ctx_body_count", "dsrt_ctx_body_update_ms", "dsrt_selftest_read_scene_words",
     "dsrt_body_motion_host", "dsrt_denoise_temporal_bodies", "dsrt_denoise_temporal_bodies_to_host", "dsrt_ctx_set_temporal_bodies", "dsrt_ctx_temporal_bodies",
     "dsrt_denoise_temporal_shaded", "dsrt_denoise_temporal_shaded_to_host", "dsrt_ctx_set_temporal_shading", "dsrt_ctx_temporal_shading",
+    "dsrt_coverage_defaults", "dsrt_render_coverage", "dsrt_render_coverage_to_host", "dsrt_denoise_coverage_alpha_min", "dsrt_denoise_accumulated_coverage",
+    "dsrt_denoise_accumulated_coverage_to_host", "dsrt_render_denoised_coverage_to_host",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -294,6 +312,13 @@ def load():
     sig("dsrt_denoise_accumulated", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), P(DsrtDenoise), vp, vp, vp, vp, vp])
     sig("dsrt_denoise_accumulated_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), P(DsrtDenoise), vp, vp, vp, vp])
     sig("dsrt_render_denoised_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtDenoise), vp, vp, vp, vp, P(DsrtStats)])
+    sig("dsrt_coverage_defaults", None, [P(DsrtCoverageDesc)])
+    sig("dsrt_render_coverage", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtCoverageDesc), P(DsrtCoverageClasses), P(DsrtCoverage), vp, P(DsrtStats)])
+    sig("dsrt_render_coverage_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtCoverageDesc), P(DsrtCoverageClasses), P(DsrtCoverage), P(DsrtStats)])
+    sig("dsrt_denoise_coverage_alpha_min", C.c_float, [])
+    sig("dsrt_denoise_accumulated_coverage", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), vp, C.c_float, P(DsrtDenoise), vp, vp, vp, vp, vp])
+    sig("dsrt_denoise_accumulated_coverage_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), vp, C.c_float, P(DsrtDenoise), vp, vp, vp, vp])
+    sig("dsrt_render_denoised_coverage_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtCoverageDesc), C.c_float, P(DsrtDenoise), vp, vp, vp, vp, vp, P(DsrtStats)])
     sig("dsrt_temporal_defaults", None, [P(DsrtTemporal)])
     sig("dsrt_denoise_temporal", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtAccum), C.c_int, vp, P(DsrtDenoiseGuides), P(GPUCamera), vp, vp, P(DsrtTemporal), P(DsrtDenoise),
                                           vp, vp, vp, vp, vp, vp, vp])
@@ -342,7 +367,7 @@ def load():
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
     for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
-                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
+                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
         if struct is not None and lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

@@ -237,6 +237,7 @@ inline bool ranges_overlap(const Staged& a, const Staged& b) {
 struct FrameBuffers {
     const void *sum, *sum_sq, *n;                                      // DsrtAccum, then the per-pixel counts
     const void *normal, *position, *albedo, *range;                    // DsrtDenoiseGuides
+    const void *alpha;                                                 // dsrt_denoise_accumulated_coverage's per-pixel coverage
     const void *rgb8, *f32, *linear, *var;                             // the image outputs
     const void *history_prev, *history_next, *prev_xy, *weight;        // the temporal stage's ...
     const void *prim_id, *prev_position;                               // ... and its motion stage's (dsrt_denoise_temporal_bodies)
@@ -249,6 +250,7 @@ constexpr size_t kHistoryBytes = 64;                                   // per pi
 inline constexpr FrameBufferKind kFrameBuffers[] = {
     {24, Dir::In, 8}, {24, Dir::In, 8}, {4, Dir::In, 4},                                                  // (bytes per pixel, direction, alignment) in FrameBuffers' order,
     {12, Dir::In, 4}, {12, Dir::In, 4}, {12, Dir::In, 4}, {4, Dir::In, 4},                                // a row of this table per row of the struct
+    {4, Dir::In, 4},
     {3, Dir::Out, 1}, {12, Dir::Out, 4}, {12, Dir::Out, 4}, {12, Dir::Out, 4},
     {kHistoryBytes, Dir::In, 16}, {kHistoryBytes, Dir::Out, 16}, {8, Dir::Out, 4}, {4, Dir::Out, 4},
     {4, Dir::In, 4}, {12, Dir::Out, 4},

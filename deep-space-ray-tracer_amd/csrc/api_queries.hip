@@ -1,5 +1,6 @@
-// api_queries.hip -- what asks the resident scene a question without rendering it: the G-buffer pass and the batched ray queries, device and host forms.
-// Calls the launchers of gbuffer_kernel.hip and raycast_kernel.hip; api_reconstruct.hip's convenience forms call dsrt_render_gbuffer.
+// api_queries.hip -- what asks the resident scene a question without rendering it: the G-buffer pass, the coverage pass and the batched ray queries, device and
+// host forms.  Calls the launchers of gbuffer_kernel.hip, coverage_kernel.hip and raycast_kernel.hip; api_reconstruct.hip's convenience forms call
+// dsrt_render_gbuffer and dsrt_render_coverage.
 #include <algorithm>
 
 #include "api_internal.h"
@@ -61,9 +62,111 @@ int check_trace_args(const char* fn, const DsrtContext* ctx, int count, const Ds
     return DSRT_OK;
 }
 
+// The coverage pass (coverage_kernel.hip).  DsrtCoverage's 7 + 11 channels: bytes per pixel (class_hits: per class) and the alignment each element needs.
+constexpr size_t kCoverageOwn = 7, kCoverageChannels = kCoverageOwn + 11, kCoverageClassHits = 6;
+constexpr size_t kCoverageBytes[kCoverageChannels] = {1, 4, 8, 1, 4, 8, 1, 4, 4, 4, 12, 12, 8, 12, 4, 4, 4, 1};     // hits, alpha, mask, sun_*, class_hits, then DsrtGBuffer's
+constexpr size_t kCoverageAlign[kCoverageChannels] = {1, 4, 8, 1, 4, 8, 1, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 1};
+static_assert(sizeof(DsrtCoverage) == kCoverageChannels * sizeof(void*) && offsetof(DsrtCoverage, rep) == kCoverageOwn * sizeof(void*), "kCoverageBytes has one entry per pointer of DsrtCoverage");
+static_assert(offsetof(DsrtCoverage, class_hits) == kCoverageClassHits * sizeof(void*), "kCoverageClassHits is the place of DsrtCoverage.class_hits");
+
+int coverage_samples(const DsrtCoverageDesc& cd) {                                // n, or 0 for what is refused
+    if (cd.pattern == DSRT_COVERAGE_GRID) return cd.samples >= 1 && cd.samples <= 8 ? cd.samples * cd.samples : 0;
+    if (cd.pattern == DSRT_COVERAGE_DIAGONAL) return cd.samples >= 1 && cd.samples <= 64 ? cd.samples : 0;
+    return 0;
+}
+
+// Everything dsrt_render_coverage refuses short of the missing scene, device and host form alike; `out` receives the channels as Staged entries.
+int check_coverage_args(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cd, const DsrtCoverageClasses* classes,
+                        const DsrtCoverage* cov, Staged (&out)[kCoverageChannels]) {
+    auto fail = [&](const char* why) { set_error(std::string(fn) + ": " + why); return DSRT_ERR_INVALID; };
+    if (!ctx || !desc || !cd || !cov) return fail("null argument");
+    if (desc->width < 2 || desc->height < 2) return fail("width and height must be at least 2 (the camera divides by W-1 and H-1)");
+    if (desc->shard_count > 1) return fail("whole images only (shard_count <= 1)");
+    if ((unsigned long long)desc->width * (unsigned long long)desc->height >= (1ull << 31)) return fail("image too large (2^31 pixels)");
+    if (!coverage_samples(*cd)) return fail("pattern must be DSRT_COVERAGE_GRID with samples in 1..8 or DSRT_COVERAGE_DIAGONAL with samples in 1..64");
+    if (classes) {
+        if (classes->count < 0 || classes->count > 16) return fail("classes->count must be between 0 and 16");
+        for (int c = 0; c < classes->count; ++c) if (classes->num[c] < 0) return fail("a class has a negative num");
+    }
+    if (cov->class_hits && (!classes || classes->count == 0)) return fail("class_hits needs classes");
+    const void* p[kCoverageChannels];
+    std::memcpy(p, cov, sizeof p);
+    const size_t px = (size_t)desc->width * desc->height;
+    bool any = false;
+    for (size_t k = 0; k < kCoverageChannels; ++k) {
+        out[k] = Staged{p[k], px * kCoverageBytes[k] * (k == kCoverageClassHits && classes ? (size_t)classes->count : 1), Dir::Out};
+        any = any || p[k];
+        if ((uintptr_t)p[k] & (kCoverageAlign[k] - 1)) return fail("a pointer is not aligned to its element");
+    }
+    if (!any) return fail("no output");
+    return DSRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void dsrt_coverage_defaults(DsrtCoverageDesc* out) {
+    if (!out) return;
+    out->pattern = DSRT_COVERAGE_DIAGONAL; out->samples = 64;
+}
+
+// The coverage pass (coverage_kernel.hip): dsrt_render_gbuffer's envelope around n rays per pixel, one wave per 64 / n pixels.
+int dsrt_render_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cd, const DsrtCoverageClasses* classes, const DsrtCoverage* cov,
+                         void* stream_v, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_coverage", [&]() -> int {
+    Staged ch[kCoverageChannels];
+    if (int rc = check_coverage_args("dsrt_render_coverage", ctx, desc, cd, classes, cov, ch)) return rc;
+    const PackedScene* sc = resident_scene(ctx, "dsrt_render_coverage");
+    if (!sc) return DSRT_ERR_NO_SCENE;
+    HIP_TRY(hipSetDevice(ctx->device));
+    CoverageArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.scene = sc->view;
+    const GPUCamera& c = ctx->frame.camera;
+    pack_camera(c, a.cam);
+    a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
+    a.sun_dir[0] = ctx->frame.sun_dir.x; a.sun_dir[1] = ctx->frame.sun_dir.y; a.sun_dir[2] = ctx->frame.sun_dir.z;
+    a.sun_enabled = ctx->frame.sun_enabled;
+    a.width = desc->width; a.height = desc->height;
+    a.pattern = cd->pattern; a.samples = cd->samples;
+    a.n = coverage_samples(*cd);
+    a.per_wave = 64 / a.n;
+    a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
+    const DsrtGBuffer& gb = cov->rep;
+    a.hits = cov->hits; a.alpha = cov->alpha; a.mask = (unsigned long long*)cov->mask;
+    a.sun_hits = cov->sun_hits; a.sun_alpha = cov->sun_alpha; a.sun_mask = (unsigned long long*)cov->sun_mask;
+    a.class_hits = cov->class_hits;
+    if (classes && cov->class_hits) {
+        a.n_classes = classes->count;
+        std::memcpy(a.class_first, classes->first, sizeof a.class_first); std::memcpy(a.class_num, classes->num, sizeof a.class_num);
+    }
+    a.t = gb.t; a.range = gb.range; a.depth = gb.depth; a.position = gb.position; a.normal = gb.normal; a.uv = gb.uv; a.albedo = gb.albedo;
+    a.prim_id = gb.prim_id; a.material_id = gb.material_id; a.sun_cos = gb.sun_cos; a.flags = gb.flags;
+    a.want_sun = cov->sun_hits || cov->sun_alpha || cov->sun_mask || gb.flags;
+    for (size_t k = kCoverageOwn; k < kCoverageChannels; ++k) a.want_rep = a.want_rep || ch[k].host;
+    if (int rc = ctx->gb_status.grow(1)) return rc;                          // (one launch at a time per context: the G-buffer pass's word serves)
+    a.status = ctx->gb_status.p;
+    const size_t px = (size_t)desc->width * desc->height;
+    const int blocks = (int)((px + (size_t)a.per_wave - 1) / (size_t)a.per_wave);
+    return launch_enveloped(ctx, (hipStream_t)stream_v, a.status, stats, "coverage", blocks, [&](hipStream_t s) { return launch_coverage(a, blocks, s); });
+    });
+}
+
+int dsrt_render_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cd, const DsrtCoverageClasses* classes, const DsrtCoverage* cov,
+                                 DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_coverage_to_host", [&]() -> int {
+    Staged s[kCoverageChannels];
+    if (int rc = check_coverage_args("dsrt_render_coverage_to_host", ctx, desc, cd, classes, cov, s)) return rc;
+    if (!resident_scene(ctx, "dsrt_render_coverage_to_host")) return DSRT_ERR_NO_SCENE;
+    HIP_TRY(hipSetDevice(ctx->device));
+    DsrtStats local;
+    return staged_call(s, [&](void* const* d) {
+        const DsrtCoverage dc = pointers_as<DsrtCoverage>(d);
+        return dsrt_render_coverage(ctx, desc, cd, classes, &dc, nullptr, stats ? stats : &local);
+    });
+    });
+}
 
 // The G-buffer pass (gbuffer_kernel.hip): the context's camera and sun, the reference tree, one launch.  It reads the resident scene and writes the
 // caller's buffers and one status word of its own; the context's working buffers, camera and sun are not touched.

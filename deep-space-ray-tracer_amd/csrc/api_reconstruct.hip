@@ -1,6 +1,6 @@
 // api_reconstruct.hip -- what turns a sample-set frame into an image: the denoiser, its temporal stage and the upscaler, with their _to_host and convenience forms.
 // Calls the launchers of denoise_kernel.hip, temporal_kernel.hip and upscale_kernel.hip, the checks of api_sample_sets.hip, and, in the convenience forms, the entry
-// points of api_sample_sets.hip (dsrt_render_accumulate) and api_queries.hip (dsrt_render_gbuffer).
+// points of api_sample_sets.hip (dsrt_render_accumulate) and api_queries.hip (dsrt_render_gbuffer, dsrt_render_coverage).
 #include "api_internal.h"
 
 using namespace dsrt;
@@ -9,6 +9,7 @@ namespace {
 
 constexpr size_t kFrameTemporal = offsetof(FrameBuffers, history_prev) / sizeof(void*);
 constexpr size_t kFrameUpscale = offsetof(FrameBuffers, lo_linear) / sizeof(void*);
+constexpr float kCoverageAlphaMin = 0.0625f;                                          // dsrt_denoise_coverage_alpha_min: DESIGN.md section 4 says how it was chosen
 
 // The table's entries [from, to) against those before them and among themselves: alignment; then each of their outputs against every input up to `to` (over_input) and
 // against every other output not checked against it yet (over_output); then the outputs before `from` against their inputs (old_over_input; nothing to do for from = 0).
@@ -40,6 +41,9 @@ struct TemporalInput {
     bool shaded = false; const DsrtTemporalShading* shading = nullptr; uint8_t* status = nullptr;
 };
 
+// The coverage part of a call (dsrt_denoise_accumulated_coverage; include/dsrt.h, COVERAGE DEMODULATION): null for the other forms.  A null alpha is the plain denoiser.
+struct CoverageInput { const float* alpha; float alpha_min; };
+
 int check_denoise_params(const char* fn, const DsrtDenoise* dn) {
     if (!dn) return accum_fail(fn, "null argument");
     if (dn->iterations < 0 || dn->iterations > 6) return accum_fail(fn, "iterations must be between 0 and 6");
@@ -58,8 +62,9 @@ int check_temporal_params(const char* fn, const DsrtTemporal* tp) {
 }
 
 // The buffers of a denoiser call, device or host form alike (the outputs as the caller gave them: an output not asked for is null).
-FrameBuffers denoise_buffers(const DsrtAccum& acc, const uint32_t* n, const DsrtDenoiseGuides& g, const TemporalInput* t, const void* rgb8, const void* f32, const void* linear, const void* var) {
-    return FrameBuffers{acc.sum, acc.sum_sq, n, g.normal, g.position, g.albedo, g.range, rgb8, f32, linear, var,
+FrameBuffers denoise_buffers(const DsrtAccum& acc, const uint32_t* n, const DsrtDenoiseGuides& g, const TemporalInput* t, const void* rgb8, const void* f32, const void* linear, const void* var,
+                             const float* alpha = nullptr) {
+    return FrameBuffers{acc.sum, acc.sum_sq, n, g.normal, g.position, g.albedo, g.range, alpha, rgb8, f32, linear, var,
                         t ? t->prev : nullptr, t ? t->next : nullptr, t ? t->prev_xy : nullptr, t ? t->weight : nullptr,
                         t && t->motion ? t->motion->prim_id : nullptr, t ? t->prev_position : nullptr,
                         t && t->shading ? t->shading->flags : nullptr, t ? t->status : nullptr};
@@ -67,8 +72,9 @@ FrameBuffers denoise_buffers(const DsrtAccum& acc, const uint32_t* n, const Dsrt
 
 // Everything dsrt_denoise_accumulated and (with `t`) dsrt_denoise_temporal refuse, before anything is launched or written; the same for the host forms' host pointers.
 int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* n, const DsrtDenoiseGuides* guides,
-                  const TemporalInput* t, const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var) {
+                  const TemporalInput* t, const DsrtDenoise* dn, const uint8_t* rgb8, const float* f32, const float* linear, const float* var, const CoverageInput* cv = nullptr) {
     if (!ctx || !desc || !acc || !guides || !dn) return accum_fail(fn, "null argument");
+    if (cv && !(cv->alpha_min > 0.0f && cv->alpha_min <= 1.0f)) return accum_fail(fn, "alpha_min must be > 0 and <= 1");
     if (t && t->bodies) if (int rc = check_body_motion(fn, t->motion)) return rc;
     if (t && t->shaded) {
         if (!t->shading || !t->shading->flags) return accum_fail(fn, "null argument (DsrtTemporalShading or its flags)");
@@ -82,7 +88,7 @@ int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* 
     if (int rc = check_denoise_params(fn, dn)) return rc;
     if (!rgb8 && !f32 && !linear && !var) return accum_fail(fn, "no output");
     Staged s[kFrameBufferCount];
-    frame_table(denoise_buffers(*acc, n, *guides, t, rgb8, f32, linear, var), (size_t)desc->width * desc->height, s);
+    frame_table(denoise_buffers(*acc, n, *guides, t, rgb8, f32, linear, var, cv ? cv->alpha : nullptr), (size_t)desc->width * desc->height, s);
     if (int rc = check_frame_table(fn, s, 0, kFrameTemporal, "an output range overlaps an input range", "two output ranges overlap", nullptr)) return rc;
     if (!t) return DSRT_OK;
     if ((t->prev_camera != nullptr) != (t->prev != nullptr)) return accum_fail(fn, "the previous camera and the previous history go together: both NULL (first frame) or both given");
@@ -95,9 +101,10 @@ int check_denoise(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* 
 
 // dsrt_denoise_accumulated and dsrt_denoise_temporal: the checks, then prepare, the temporal stage if there is one, the iterations, output.
 int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
-                 const TemporalInput* t, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, hipStream_t stream) {
+                 const TemporalInput* t, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, hipStream_t stream, const CoverageInput* cv = nullptr) {
     int rc;
-    if ((rc = check_denoise(fn, ctx, desc, acc, samples_done, d_n, guides, t, dn, d_rgb8, d_f32, d_linear, d_var))) return rc;
+    if ((rc = check_denoise(fn, ctx, desc, acc, samples_done, d_n, guides, t, dn, d_rgb8, d_f32, d_linear, d_var, cv))) return rc;
+    const float* alpha = cv ? cv->alpha : nullptr;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px = (size_t)desc->width * desc->height;
     // (growing frees the old records: the launch that may still read them has to be over first)
@@ -106,8 +113,10 @@ int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, c
     if ((rc = ctx->dn_nr.grow(px)) || (rc = ctx->dn_xf.grow(px)) || (rc = ctx->dn_al.grow(px))) return rc;
     const DenoiseBuffers b{{ctx->dn_cl[0].p, ctx->dn_cl[1].p}, {ctx->dn_vl[0].p, ctx->dn_vl[1].p}, ctx->dn_nr.p, ctx->dn_xf.p, ctx->dn_al.p};
     if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, the G-buffer) comes first
-    HIP_TRY(launch_denoise_prepare((const unsigned long long*)acc->sum, (const unsigned long long*)acc->sum_sq, samples_done, d_n, guides->normal, guides->position,
-                                   guides->albedo, guides->range, px, b, stream));
+    if (alpha) HIP_TRY(launch_denoise_prepare_coverage((const unsigned long long*)acc->sum, (const unsigned long long*)acc->sum_sq, samples_done, d_n, guides->normal,
+                                                       guides->position, guides->albedo, guides->range, alpha, cv->alpha_min, px, b, stream));
+    else HIP_TRY(launch_denoise_prepare((const unsigned long long*)acc->sum, (const unsigned long long*)acc->sum_sq, samples_done, d_n, guides->normal, guides->position,
+                                        guides->albedo, guides->range, px, b, stream));
     if (t) {
         TemporalArgs a;
         std::memset(&a, 0, sizeof a);
@@ -138,16 +147,17 @@ int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, c
     }
     for (int i = 0; i < dn->iterations; ++i)
         HIP_TRY(launch_denoise_atrous(b, i & 1, desc->width, desc->height, 1 << i, dn->normal_power_log2, dn->sigma_l, dn->sigma_z, dn->sigma_a, stream));
-    HIP_TRY(launch_denoise_output(b, dn->iterations & 1, px, inv_gamma_of(*desc), desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
+    if (alpha) HIP_TRY(launch_denoise_output_coverage(b, dn->iterations & 1, alpha, px, inv_gamma_of(*desc), desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
+    else HIP_TRY(launch_denoise_output(b, dn->iterations & 1, px, inv_gamma_of(*desc), desc->math_mode == 1, d_rgb8, d_f32, d_linear, d_var, stream));
     return launch_finish(ctx, stream, nullptr);                                      // the records are the context's: its next launch on any stream comes behind
 }
 
 // Their _to_host forms: the same call on device mirrors of the frame's table, the device finished before the results are copied out.
 int denoise_to_host(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n, const DsrtDenoiseGuides* h_guides,
-                    const TemporalInput* ht, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var) {
-    if (int rc = check_denoise(fn, ctx, desc, h_acc, samples_done, h_n, h_guides, ht, dn, h_rgb8, h_f32, h_linear, h_var)) return rc;
+                    const TemporalInput* ht, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, const CoverageInput* hcv = nullptr) {
+    if (int rc = check_denoise(fn, ctx, desc, h_acc, samples_done, h_n, h_guides, ht, dn, h_rgb8, h_f32, h_linear, h_var, hcv)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const FrameBuffers h = denoise_buffers(*h_acc, h_n, *h_guides, ht, h_rgb8, h_f32, h_linear, h_var);
+    const FrameBuffers h = denoise_buffers(*h_acc, h_n, *h_guides, ht, h_rgb8, h_f32, h_linear, h_var, hcv ? hcv->alpha : nullptr);
     return staged_frame_call(h, (size_t)desc->width * desc->height, true, [&](const FrameBuffers& m) {
         const DsrtAccum acc = accum_of(m);
         const DsrtDenoiseGuides g{(const float*)m.normal, (const float*)m.position, (const float*)m.albedo, (const float*)m.range};
@@ -158,8 +168,9 @@ int denoise_to_host(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc
         const TemporalInput t{ht ? ht->prev_camera : nullptr, (const float*)m.history_prev, (float*)m.history_next, ht ? ht->tp : nullptr, (float*)m.prev_xy, (float*)m.weight,
                               ht && ht->bodies, ht && ht->bodies ? &motion : nullptr, (float*)m.prev_position,
                               ht && ht->shaded, ht && ht->shaded ? &shading : nullptr, (uint8_t*)m.status};
+        const CoverageInput cv{(const float*)m.alpha, hcv ? hcv->alpha_min : 1.0f};
         return denoise_impl(fn, ctx, desc, &acc, samples_done, (const uint32_t*)m.n, &g, ht ? &t : nullptr, dn, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
-                            (float*)m.var, nullptr);
+                            (float*)m.var, nullptr, hcv ? &cv : nullptr);
     });
 }
 
@@ -295,6 +306,60 @@ int dsrt_denoise_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* des
                                      const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var) {
     return dsrt::guarded("dsrt_denoise_accumulated_to_host", [&]() -> int {
     return denoise_to_host("dsrt_denoise_accumulated_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, nullptr, dn, h_rgb8, h_f32, h_linear, h_var);
+    });
+}
+
+float dsrt_denoise_coverage_alpha_min(void) { return kCoverageAlphaMin; }
+
+int dsrt_denoise_accumulated_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                                      const float* d_alpha, float alpha_min, const DsrtDenoise* dn, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, void* stream_v) {
+    return dsrt::guarded("dsrt_denoise_accumulated_coverage", [&]() -> int {
+    const CoverageInput cv{d_alpha, alpha_min};
+    return denoise_impl("dsrt_denoise_accumulated_coverage", ctx, desc, acc, samples_done, d_n, guides, nullptr, dn, d_rgb8, d_f32, d_linear, d_var, (hipStream_t)stream_v, &cv);
+    });
+}
+
+int dsrt_denoise_accumulated_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n,
+                                              const DsrtDenoiseGuides* h_guides, const float* h_alpha, float alpha_min, const DsrtDenoise* dn, uint8_t* h_rgb8, float* h_f32,
+                                              float* h_linear, float* h_var) {
+    return dsrt::guarded("dsrt_denoise_accumulated_coverage_to_host", [&]() -> int {
+    const CoverageInput hcv{h_alpha, alpha_min};
+    return denoise_to_host("dsrt_denoise_accumulated_coverage_to_host", ctx, desc, h_acc, samples_done, h_n, h_guides, nullptr, dn, h_rgb8, h_f32, h_linear, h_var, &hcv);
+    });
+}
+
+// The convenience form with coverage: the samples, a DIAGONAL coverage pass whose alpha and rep channels are the alpha and the guides, the demodulated filter.
+int dsrt_render_denoised_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cov_desc, float alpha_min, const DsrtDenoise* dn,
+                                          uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_alpha, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_denoised_coverage_to_host", [&]() -> int {
+    const char* fn = "dsrt_render_denoised_coverage_to_host";
+    int spp, rc;
+    if ((rc = check_render_denoised(fn, ctx, desc, dn, false, nullptr, h_rgb8 || h_f32 || h_linear || h_var, &spp))) return rc;
+    DsrtCoverageDesc cd;
+    dsrt_coverage_defaults(&cd);
+    if (cov_desc) cd = *cov_desc;
+    if (cd.pattern != DSRT_COVERAGE_DIAGONAL || cd.samples < 1 || cd.samples > 64) return accum_fail(fn, "the coverage pass must be DSRT_COVERAGE_DIAGONAL with samples in 1..64");
+    if (!(alpha_min > 0.0f && alpha_min <= 1.0f)) return accum_fail(fn, "alpha_min must be > 0 and <= 1");
+    if ((uintptr_t)h_alpha & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px = (size_t)desc->width * (size_t)desc->height;
+    FrameScratch f;
+    DevBuf<float> alpha;
+    if ((rc = f.init(px, false, true)) || (rc = alpha.alloc(px))) return rc;
+    DsrtCoverage cov{};
+    cov.alpha = alpha.p; cov.rep = f.gb;
+    FrameBuffers h{};
+    h.rgb8 = h_rgb8; h.f32 = h_f32; h.linear = h_linear; h.var = h_var;
+    DsrtStats local;
+    if ((rc = staged_frame_call(h, px, true, [&](const FrameBuffers& m) -> int {
+        int r;
+        if ((r = dsrt_render_accumulate(ctx, desc, 0, spp, 1, &f.acc, nullptr, stats ? stats : &local))) return r;
+        if ((r = dsrt_render_coverage(ctx, desc, &cd, nullptr, &cov, nullptr, nullptr))) return r;
+        return dsrt_denoise_accumulated_coverage(ctx, desc, &f.acc, spp, nullptr, &f.guides, alpha.p, alpha_min, dn, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
+                                                 (float*)m.var, nullptr);
+    }))) return rc;
+    if (h_alpha) HIP_TRY(hipMemcpy(h_alpha, alpha.p, px * sizeof(float), hipMemcpyDeviceToHost));
+    return DSRT_OK;
     });
 }
 

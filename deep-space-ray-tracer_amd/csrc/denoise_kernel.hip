@@ -7,6 +7,9 @@
 //   a-trous   one launch per iteration, cl / vl ping-ponging; 16 x 16 pixels per workgroup.  The sums run in the header's order (dy outer, dx inner, one
 //             accumulator each): nothing is reassociated, a skipped tap is a branch.
 //   output    d_linear, d_var and the resolve's tone map + 8-bit store of the filtered mean; templated over where powf comes from (DsrtRenderDesc.math_mode).
+// prepare and output are bodies templated over "has alpha" (include/dsrt.h, COVERAGE DEMODULATION: dsrt_denoise_accumulated_coverage) behind two kernels each:
+// the plain denoiser's, unchanged instruction for instruction, and the _coverage ones, which divide the filterable pixels' c and v by alpha and alpha^2 at the
+// start and multiply them back at the end.
 //
 // There is no reference counterpart: the reference reconstructs its 250-spp frames outside the renderer (scripts/upsample.py).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off, no fast-math -- IEEE division and square root and the absence of contraction are the contract.
@@ -20,11 +23,13 @@ namespace dsrt {
 __device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
-__global__ __launch_bounds__(256) void dsrt_denoise_prepare_kernel(const unsigned long long* __restrict__ sums, const unsigned long long* __restrict__ sums_sq, int samples_done,
-                                                                   const uint32_t* __restrict__ counts, const float* __restrict__ normal, const float* __restrict__ position,
-                                                                   const float* __restrict__ albedo, const float* __restrict__ range, size_t n_pixels,
-                                                                   float4* __restrict__ cl, float4* __restrict__ vl, float4* __restrict__ nr, float4* __restrict__ xf,
-                                                                   float4* __restrict__ al) {
+// prepare's body, over "has alpha" (include/dsrt.h, COVERAGE DEMODULATION): HAS_ALPHA = false is the plain denoiser's kernel, instruction for instruction.
+template <bool HAS_ALPHA>
+__device__ __forceinline__ void denoise_prepare(const unsigned long long* __restrict__ sums, const unsigned long long* __restrict__ sums_sq, int samples_done,
+                                                const uint32_t* __restrict__ counts, const float* __restrict__ normal, const float* __restrict__ position,
+                                                const float* __restrict__ albedo, const float* __restrict__ range, const float* __restrict__ alpha, float alpha_min,
+                                                size_t n_pixels, float4* __restrict__ cl, float4* __restrict__ vl, float4* __restrict__ nr, float4* __restrict__ xf,
+                                                float4* __restrict__ al) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels) return;
     const uint32_t cnt = counts ? counts[i] : (uint32_t)samples_done;
@@ -43,12 +48,37 @@ __global__ __launch_bounds__(256) void dsrt_denoise_prepare_kernel(const unsigne
         }
     }
     const float r = range[i];
-    const bool filterable = r <= FLT_MAX && cnt >= 2u;                 // false for a NaN range
+    bool filterable = r <= FLT_MAX && cnt >= 2u;                       // false for a NaN range
+    if constexpr (HAS_ALPHA) {
+        const float a = alpha[i];
+        filterable = filterable && a >= alpha_min;                     // false for a NaN alpha
+        if (filterable) {
+            const float aa = a * a;
+            for (int ch = 0; ch < 3; ++ch) { c[ch] = c[ch] / a; v[ch] = v[ch] / aa; }
+        }
+    }
     cl[i] = make_float4(c[0], c[1], c[2], lum(c[0], c[1], c[2]));
     vl[i] = make_float4(v[0], v[1], v[2], lum(v[0], v[1], v[2]));
     nr[i] = make_float4(normal[i * 3 + 0], normal[i * 3 + 1], normal[i * 3 + 2], r);
     xf[i] = make_float4(position[i * 3 + 0], position[i * 3 + 1], position[i * 3 + 2], filterable ? 1.0f : 0.0f);
     al[i] = make_float4(albedo[i * 3 + 0], albedo[i * 3 + 1], albedo[i * 3 + 2], 0.0f);
+}
+
+__global__ __launch_bounds__(256) void dsrt_denoise_prepare_kernel(const unsigned long long* __restrict__ sums, const unsigned long long* __restrict__ sums_sq, int samples_done,
+                                                                   const uint32_t* __restrict__ counts, const float* __restrict__ normal, const float* __restrict__ position,
+                                                                   const float* __restrict__ albedo, const float* __restrict__ range, size_t n_pixels,
+                                                                   float4* __restrict__ cl, float4* __restrict__ vl, float4* __restrict__ nr, float4* __restrict__ xf,
+                                                                   float4* __restrict__ al) {
+    denoise_prepare<false>(sums, sums_sq, samples_done, counts, normal, position, albedo, range, nullptr, 0.0f, n_pixels, cl, vl, nr, xf, al);
+}
+
+__global__ __launch_bounds__(256) void dsrt_denoise_prepare_coverage_kernel(const unsigned long long* __restrict__ sums, const unsigned long long* __restrict__ sums_sq,
+                                                                            int samples_done, const uint32_t* __restrict__ counts, const float* __restrict__ normal,
+                                                                            const float* __restrict__ position, const float* __restrict__ albedo,
+                                                                            const float* __restrict__ range, const float* __restrict__ alpha, float alpha_min, size_t n_pixels,
+                                                                            float4* __restrict__ cl, float4* __restrict__ vl, float4* __restrict__ nr, float4* __restrict__ xf,
+                                                                            float4* __restrict__ al) {
+    denoise_prepare<true>(sums, sums_sq, samples_done, counts, normal, position, albedo, range, alpha, alpha_min, n_pixels, cl, vl, nr, xf, al);
 }
 
 __global__ __launch_bounds__(256) void dsrt_denoise_atrous_kernel(const float4* __restrict__ cl_in, const float4* __restrict__ vl_in, const float4* __restrict__ nr,
@@ -121,15 +151,26 @@ __device__ __forceinline__ float tone(float c, float inv_gamma) {       // the r
     return fminf(1.0f, fmaxf(0.0f, c));
 }
 
-template <bool DEVICE_LIBM>
-__global__ __launch_bounds__(256) void dsrt_denoise_output_kernel(const float4* __restrict__ cl, const float4* __restrict__ vl, size_t n_pixels, float inv_gamma,
-                                                                  uint8_t* __restrict__ out_rgb8, float* __restrict__ out_f32, float* __restrict__ out_linear,
-                                                                  float* __restrict__ out_var) {
+// output's body, over "has alpha": the filterable pixels' c and v multiplied back by a and a*a (xf.w is prepare's F_p, alpha_min included) before anything is written.
+template <bool DEVICE_LIBM, bool HAS_ALPHA>
+__device__ __forceinline__ void denoise_output(const float4* __restrict__ cl, const float4* __restrict__ vl, const float4* __restrict__ xf, const float* __restrict__ alpha,
+                                               size_t n_pixels, float inv_gamma, uint8_t* __restrict__ out_rgb8, float* __restrict__ out_f32, float* __restrict__ out_linear,
+                                               float* __restrict__ out_var) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels) return;
-    const float4 c = cl[i];
+    float4 c = cl[i];
+    float a = 1.0f;
+    bool scaled = false;
+    if constexpr (HAS_ALPHA) {
+        scaled = xf[i].w != 0.0f;
+        if (scaled) { a = alpha[i]; c.x = c.x * a; c.y = c.y * a; c.z = c.z * a; }
+    }
     if (out_linear) { out_linear[i * 3 + 0] = c.x; out_linear[i * 3 + 1] = c.y; out_linear[i * 3 + 2] = c.z; }
-    if (out_var) { const float4 v = vl[i]; out_var[i * 3 + 0] = v.x; out_var[i * 3 + 1] = v.y; out_var[i * 3 + 2] = v.z; }
+    if (out_var) {
+        float4 v = vl[i];
+        if constexpr (HAS_ALPHA) { if (scaled) { const float aa = a * a; v.x = v.x * aa; v.y = v.y * aa; v.z = v.z * aa; } }
+        out_var[i * 3 + 0] = v.x; out_var[i * 3 + 1] = v.y; out_var[i * 3 + 2] = v.z;
+    }
     if (!out_rgb8 && !out_f32) return;
     const float r = tone<DEVICE_LIBM>(c.x, inv_gamma), g = tone<DEVICE_LIBM>(c.y, inv_gamma), b = tone<DEVICE_LIBM>(c.z, inv_gamma);
     if (out_rgb8) {
@@ -140,10 +181,32 @@ __global__ __launch_bounds__(256) void dsrt_denoise_output_kernel(const float4* 
     if (out_f32) { out_f32[i * 3 + 0] = r; out_f32[i * 3 + 1] = g; out_f32[i * 3 + 2] = b; }
 }
 
+template <bool DEVICE_LIBM>
+__global__ __launch_bounds__(256) void dsrt_denoise_output_kernel(const float4* __restrict__ cl, const float4* __restrict__ vl, size_t n_pixels, float inv_gamma,
+                                                                  uint8_t* __restrict__ out_rgb8, float* __restrict__ out_f32, float* __restrict__ out_linear,
+                                                                  float* __restrict__ out_var) {
+    denoise_output<DEVICE_LIBM, false>(cl, vl, nullptr, nullptr, n_pixels, inv_gamma, out_rgb8, out_f32, out_linear, out_var);
+}
+
+template <bool DEVICE_LIBM>
+__global__ __launch_bounds__(256) void dsrt_denoise_output_coverage_kernel(const float4* __restrict__ cl, const float4* __restrict__ vl, const float4* __restrict__ xf,
+                                                                           const float* __restrict__ alpha, size_t n_pixels, float inv_gamma, uint8_t* __restrict__ out_rgb8,
+                                                                           float* __restrict__ out_f32, float* __restrict__ out_linear, float* __restrict__ out_var) {
+    denoise_output<DEVICE_LIBM, true>(cl, vl, xf, alpha, n_pixels, inv_gamma, out_rgb8, out_f32, out_linear, out_var);
+}
+
 hipError_t launch_denoise_prepare(const unsigned long long* sums, const unsigned long long* sums_sq, int samples_done, const uint32_t* counts, const float* normal,
                                   const float* position, const float* albedo, const float* range, size_t n_pixels, const DenoiseBuffers& b, hipStream_t stream) {
     hipLaunchKernelGGL(dsrt_denoise_prepare_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, sums_sq, samples_done, counts, normal, position,
                        albedo, range, n_pixels, b.cl[0], b.vl[0], b.nr, b.xf, b.al);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_prepare_coverage(const unsigned long long* sums, const unsigned long long* sums_sq, int samples_done, const uint32_t* counts, const float* normal,
+                                           const float* position, const float* albedo, const float* range, const float* alpha, float alpha_min, size_t n_pixels,
+                                           const DenoiseBuffers& b, hipStream_t stream) {
+    hipLaunchKernelGGL(dsrt_denoise_prepare_coverage_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, sums, sums_sq, samples_done, counts, normal,
+                       position, albedo, range, alpha, alpha_min, n_pixels, b.cl[0], b.vl[0], b.nr, b.xf, b.al);
     return hipGetLastError();
 }
 
@@ -160,6 +223,14 @@ hipError_t launch_denoise_output(const DenoiseBuffers& b, int src, size_t n_pixe
     const dim3 grid((unsigned)((n_pixels + 255) / 256)), block(256);
     if (device_libm) hipLaunchKernelGGL(dsrt_denoise_output_kernel<true>, grid, block, 0, stream, b.cl[src], b.vl[src], n_pixels, inv_gamma, out_rgb8, out_f32, out_linear, out_var);
     else hipLaunchKernelGGL(dsrt_denoise_output_kernel<false>, grid, block, 0, stream, b.cl[src], b.vl[src], n_pixels, inv_gamma, out_rgb8, out_f32, out_linear, out_var);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_output_coverage(const DenoiseBuffers& b, int src, const float* alpha, size_t n_pixels, float inv_gamma, bool device_libm, uint8_t* out_rgb8,
+                                          float* out_f32, float* out_linear, float* out_var, hipStream_t stream) {
+    const dim3 grid((unsigned)((n_pixels + 255) / 256)), block(256);
+    if (device_libm) hipLaunchKernelGGL(dsrt_denoise_output_coverage_kernel<true>, grid, block, 0, stream, b.cl[src], b.vl[src], b.xf, alpha, n_pixels, inv_gamma, out_rgb8, out_f32, out_linear, out_var);
+    else hipLaunchKernelGGL(dsrt_denoise_output_coverage_kernel<false>, grid, block, 0, stream, b.cl[src], b.vl[src], b.xf, alpha, n_pixels, inv_gamma, out_rgb8, out_f32, out_linear, out_var);
     return hipGetLastError();
 }
 

@@ -187,6 +187,29 @@ struct GBufferArgs {
     uint32_t* status;          // kFlag* bits below: a reference, slot or material out of range (never raised by a library-built scene)
 };
 
+// The argument block of the coverage pass (coverage_kernel.hip, include/dsrt.h: COVERAGE, dsrt_render_coverage).
+struct CoverageArgs {
+    DeviceScene scene;
+    float cam[12];             // as FrameParams::cam
+    float neg_w[3];            // -camera.w, for rep.depth
+    float sun_dir[3];
+    int   sun_enabled;
+    int   width, height;
+    int   pattern, samples;    // DsrtCoverageDesc
+    int   n;                   // sub-samples per pixel: samples^2 (GRID) or samples (DIAGONAL), 1 .. 64
+    int   per_wave;            // P = 64 / n pixels per wave
+    int   stack_entries;       // LDS stack entries per lane the launch provides (>= the tree's stack_need)
+    int   want_sun;            // a sun output or rep.flags is asked for: the shadow rays are traced
+    int   want_rep;            // a channel of `rep` is asked for
+    uint8_t* hits; float* alpha; unsigned long long* mask;               // DsrtCoverage's own outputs, NULL = not written
+    uint8_t* sun_hits; float* sun_alpha; unsigned long long* sun_mask;
+    uint8_t* class_hits;       // n_classes bytes per pixel
+    int   n_classes, class_first[16], class_num[16];
+    float* t; float* range; float* depth; float* position; float* normal; float* uv; float* albedo;   // DsrtCoverage.rep, as GBufferArgs' channels
+    int* prim_id; int* material_id; float* sun_cos; uint8_t* flags;
+    uint32_t* status;          // kFlag* bits below, as for the G-buffer pass
+};
+
 // The argument block of the ray queries (raycast_kernel.hip, include/dsrt.h: dsrt_trace_rays).
 struct RaycastArgs {
     DeviceScene scene;

@@ -51,6 +51,7 @@ hipError_t launch_philox(unsigned long long seed, unsigned long long sub, int n,
 
 hipError_t launch_gbuffer(const GBufferArgs& a, int tiles, hipStream_t stream);                                  // gbuffer_kernel.hip
 hipError_t launch_raycast(const RaycastArgs& a, bool any_hit, int blocks, hipStream_t stream);                   // raycast_kernel.hip
+hipError_t launch_coverage(const CoverageArgs& a, int blocks, hipStream_t stream);                               // coverage_kernel.hip: one wave per 64 / a.n pixels
 
 // denoise_kernel.hip (include/dsrt.h, DENOISER).  The filter's working memory, one 16-byte record per pixel each: {c.rgb, L(c)} and {v.rgb, L(v)} twice (the
 // iterations ping-pong between [0] and [1]), and the guides {N, range}, {X, filterable}, {A, 0}.  prepare fills cl[0], vl[0] and the guides; an a-trous launch
@@ -62,6 +63,13 @@ hipError_t launch_denoise_atrous(const DenoiseBuffers& b, int src, int W, int H,
                                  hipStream_t stream);
 hipError_t launch_denoise_output(const DenoiseBuffers& b, int src, size_t n_pixels, float inv_gamma, bool device_libm, uint8_t* out_rgb8, float* out_f32, float* out_linear,
                                  float* out_var, hipStream_t stream);
+// ... with COVERAGE DEMODULATION (include/dsrt.h): `alpha` one float per pixel, never null here (a call without one uses the two above: their kernels are the
+// HAS_ALPHA = false instantiations of the same templates).  prepare divides the filterable pixels' c and v by a and a*a, output multiplies them back.
+hipError_t launch_denoise_prepare_coverage(const unsigned long long* sums, const unsigned long long* sums_sq, int samples_done, const uint32_t* counts, const float* normal,
+                                           const float* position, const float* albedo, const float* range, const float* alpha, float alpha_min, size_t n_pixels,
+                                           const DenoiseBuffers& b, hipStream_t stream);
+hipError_t launch_denoise_output_coverage(const DenoiseBuffers& b, int src, const float* alpha, size_t n_pixels, float inv_gamma, bool device_libm, uint8_t* out_rgb8,
+                                          float* out_f32, float* out_linear, float* out_var, hipStream_t stream);
 
 // temporal_kernel.hip (include/dsrt.h, TEMPORAL ACCUMULATION): between prepare and the first a-trous launch.  cl / vl are DenoiseBuffers' [0], blended in place;
 // prev (null = no previous frame) and next are the caller's histories, four float4 per pixel; cam = the previous GPUCamera's origin, lower_left_corner,

@@ -165,6 +165,9 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_UPSCALE: return sizeof(DsrtUpscale);
         case DSRT_SIZEOF_BODY_MOTION: return sizeof(DsrtBodyMotion);
         case DSRT_SIZEOF_TEMPORAL_SHADING: return sizeof(DsrtTemporalShading);
+        case DSRT_SIZEOF_COVERAGE_DESC: return sizeof(DsrtCoverageDesc);
+        case DSRT_SIZEOF_COVERAGE: return sizeof(DsrtCoverage);
+        case DSRT_SIZEOF_COVERAGE_CLASSES: return sizeof(DsrtCoverageClasses);
         default: return 0;
     }
 }

@@ -41,6 +41,13 @@
 //     TEMPORAL ACCUMULATION WITH BODIES: dsrt_ctx_set_temporal_bodies), and --flow is flow ground truth that includes their motion.
 //   * --follow-shading (with --denoise --temporal, with or without --follow-bodies): the history keeps every surface point's sun state and gives up what lies across
 //     or next to a moved shadow edge (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING: dsrt_ctx_set_temporal_shading, mode 2).
+//   * --coverage grid:S|diag:N also writes each frame's sub-pixel coverage (include/dsrt.h, COVERAGE: dsrt_render_coverage; S x S sub-samples on a grid, S = 1 .. 8,
+//     or N = 1 .. 64 along the pixel's diagonal), in either rng_mode and beside any other mode: <frame>_alpha.pfm, the share of the sub-samples that hit (a soft mask),
+//     <frame>_sun_alpha.pfm, the share that hit and see the Sun (an antialiased shadow mask), and with --body <frame>_body_alpha.pfm: one plane per body, the static
+//     part first, stacked top to bottom in one single-channel map of height (bodies + 1) * H -- the share of the sub-samples that hit that body.
+//   * with --denoise: --coverage-aware [ALPHA_MIN] filters the covered part of every pixel (include/dsrt.h, COVERAGE DEMODULATION: a DIAGONAL 64 coverage pass gives
+//     alpha and the guides, dsrt_denoise_accumulated_coverage; ALPHA_MIN in (0, 1], default the library's), so that silhouette pixels and trusses thinner than a
+//     pixel are filtered too.  Does not combine with --temporal or --upscale.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -75,6 +82,10 @@ int main(int argc, char** argv) {
     float adaptive_tol = 0.0f, adaptive_floor = 0.0f;
     bool adaptive = false, adaptive_detail = false, denoise = false, temporal = false, flow = false, follow_bodies = false, follow_shading = false;
     int denoise_iterations = -1;                                    // -1: the library's default
+    bool coverage = false, coverage_aware = false;
+    DsrtCoverageDesc cov_desc{DSRT_COVERAGE_DIAGONAL, 64};
+    float alpha_min = dsrt_denoise_coverage_alpha_min();
+    const char* usage_coverage = "dsrt_render: --coverage takes grid:S (S = 1 .. 8) or diag:N (N = 1 .. 64)\n";
     bool upscale = false;
     int upscale_factor = 4;                                         // the reference's scale (src/main.cpp:444)
     std::vector<std::pair<std::string, double>> bodies;             // --body OBJ [--body-scale S], repeatable: movable rigid bodies 1, 2, ... (include/dsrt.h, MOVABLE RIGID BODIES)
@@ -113,6 +124,21 @@ int main(int argc, char** argv) {
             denoise = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise_iterations = std::atoi(argv[++i]);
         }
+        else if (a == "--coverage") {                               // sub-pixel coverage of every frame next to its image (include/dsrt.h, COVERAGE)
+            const std::string v = next("--coverage");
+            coverage = true;
+            if (v.rfind("grid:", 0) == 0) cov_desc.pattern = DSRT_COVERAGE_GRID;
+            else if (v.rfind("diag:", 0) == 0) cov_desc.pattern = DSRT_COVERAGE_DIAGONAL;
+            else { std::fputs(usage_coverage, stderr); return 2; }
+            char* end = nullptr;
+            const long k = std::strtol(v.c_str() + 5, &end, 10);
+            if (end == v.c_str() + 5 || *end || k < 1 || k > (cov_desc.pattern == DSRT_COVERAGE_GRID ? 8 : 64)) { std::fputs(usage_coverage, stderr); return 2; }
+            cov_desc.samples = (int)k;
+        }
+        else if (a == "--coverage-aware") {                         // with --denoise: the filter works on the covered part of every pixel; the value (alpha_min) is optional
+            coverage_aware = true;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) alpha_min = (float)std::atof(argv[++i]);
+        }
         else if (a == "--temporal") temporal = true;                // with --denoise: reprojected frame history (include/dsrt.h, TEMPORAL ACCUMULATION)
         else if (a == "--flow") flow = true;                        // with --temporal: <frame>_flow.pfm, every pixel's displacement from the previous frame
         else if (a == "--follow-bodies") follow_bodies = true;      // with --body, --denoise and --temporal: the history follows the bodies (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES)
@@ -128,7 +154,7 @@ int main(int argc, char** argv) {
             upscale = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') upscale_factor = std::atoi(argv[++i]);
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
@@ -151,6 +177,9 @@ int main(int argc, char** argv) {
     if (denoise && (passes != 0 || adaptive || gbuffer)) { std::fprintf(stderr, "dsrt_render: --denoise does not combine with --passes / --adaptive / --gbuffer\n"); return 2; }
     if (denoise && denoise_iterations > 6) { std::fprintf(stderr, "dsrt_render: --denoise ITER must be between 0 and 6\n"); return 2; }
     if (denoise && spp < 2) { std::fprintf(stderr, "dsrt_render: --denoise needs --spp 2 or more\n"); return 2; }
+    if (coverage_aware && !denoise) { std::fprintf(stderr, "dsrt_render: --coverage-aware needs --denoise\n"); return 2; }
+    if (coverage_aware && (temporal || upscale)) { std::fprintf(stderr, "dsrt_render: --coverage-aware does not combine with --temporal / --upscale\n"); return 2; }
+    if (coverage_aware && !(alpha_min > 0.0f && alpha_min <= 1.0f)) { std::fprintf(stderr, "dsrt_render: --coverage-aware ALPHA_MIN must be > 0 and <= 1\n"); return 2; }
     if (temporal && !denoise) { std::fprintf(stderr, "dsrt_render: --temporal needs --denoise\n"); return 2; }
     if (flow && !temporal) { std::fprintf(stderr, "dsrt_render: --flow needs --temporal\n"); return 2; }
     if (follow_shading && (!denoise || !temporal)) { std::fprintf(stderr, "dsrt_render: --follow-shading needs --denoise and --temporal\n"); return 2; }
@@ -316,6 +345,7 @@ int main(int argc, char** argv) {
     const bool guided = denoise && !temporal && !upscale;
     std::vector<float> normal(guided ? image_bytes : 0), position(guided ? image_bytes : 0), albedo(guided ? image_bytes : 0), range(guided ? px : 0);
     const DsrtDenoiseGuides guides{normal.data(), position.data(), albedo.data(), range.data()};
+    std::vector<float> alpha(guided && coverage_aware ? px : 0);
     DsrtGBuffer g;
     std::memset(&g, 0, sizeof g);
     g.normal = normal.data(); g.position = position.data(); g.albedo = albedo.data(); g.range = range.data();
@@ -324,11 +354,23 @@ int main(int argc, char** argv) {
         std::fill(sq.begin(), sq.end(), 0);
         if (dsrt_render_accumulate_to_host(ctx, &d, 0, spp, 1, &acc, nullptr) != DSRT_OK) return fail("rendering the samples");
         if (dsrt_resolve_accumulated_to_host(ctx, &d, &acc, spp, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("resolving the raw image");
+        if (coverage_aware) {                                       // alpha and the representatives' guides from a DIAGONAL 64 pass: the renderer's own measure
+            DsrtCoverageDesc cd;
+            dsrt_coverage_defaults(&cd);
+            DsrtCoverage cv;
+            std::memset(&cv, 0, sizeof cv);
+            cv.alpha = alpha.data(); cv.rep = g;
+            if (dsrt_render_coverage_to_host(ctx, &d, &cd, nullptr, &cv, nullptr) != DSRT_OK) return fail("rendering the coverage");
+            if (dsrt_denoise_accumulated_coverage_to_host(ctx, &d, &acc, spp, nullptr, &guides, alpha.data(), alpha_min, &dn, img.data(), nullptr, nullptr,
+                                                          variance ? var.data() : nullptr) != DSRT_OK) return fail("denoising");
+        } else {
         if (dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK) return fail("rendering the G-buffer");
         if (dsrt_denoise_accumulated_to_host(ctx, &d, &acc, spp, nullptr, &guides, &dn, img.data(), nullptr, nullptr, variance ? var.data() : nullptr) != DSRT_OK)
             return fail("denoising");
+        }
         if (!write_image(base + ext, img.data()) || !write_image(base + "_raw" + ext, raw.data())) return fail("writing the frame");
         if (!write_var(base)) return fail("writing the variance");
+        if (coverage_aware) std::printf("coverage-aware: alpha_min %g\n", (double)alpha_min);
         std::printf("denoise: %d iterations\nSaved %s, %s_raw%s%s\n", dn.iterations, (base + ext).c_str(), base.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
         return 0;
     };
@@ -397,6 +439,32 @@ int main(int argc, char** argv) {
         return 0;
     };
 
+    // --coverage: the sub-pixel coverage of the frame the context's camera, sun and body poses are set to; with --body one class per body
+    auto write_coverage = [&](const std::string& base) -> int {
+        const int nb = bodies.empty() ? 0 : (int)bodies.size() + 1;
+        std::vector<float> a(px), sa(px), planes((size_t)nb * px);
+        std::vector<uint8_t> ch((size_t)nb * px);
+        DsrtCoverageClasses cl;
+        std::memset(&cl, 0, sizeof cl);
+        cl.count = nb;
+        for (int b = 0; b < nb; ++b) if (dsrt_host_scene_body_range(hs, b, &cl.first[b], &cl.num[b]) != DSRT_OK) return fail("asking for a body's triangles");
+        DsrtCoverage cv;
+        std::memset(&cv, 0, sizeof cv);
+        cv.alpha = a.data(); cv.sun_alpha = sa.data();
+        if (nb) cv.class_hits = ch.data();
+        if (dsrt_render_coverage_to_host(ctx, &d, &cov_desc, nb ? &cl : nullptr, &cv, nullptr) != DSRT_OK) return fail("rendering the coverage");
+        if (dsrt_write_pfm((base + "_alpha.pfm").c_str(), a.data(), width, height, 1) != DSRT_OK ||
+            dsrt_write_pfm((base + "_sun_alpha.pfm").c_str(), sa.data(), width, height, 1) != DSRT_OK) return fail("writing the coverage");
+        if (nb) {
+            const float fn = (float)(cov_desc.pattern == DSRT_COVERAGE_GRID ? cov_desc.samples * cov_desc.samples : cov_desc.samples);
+            for (int b = 0; b < nb; ++b)
+                for (size_t i = 0; i < px; ++i) planes[(size_t)b * px + i] = (float)ch[i * (size_t)nb + (size_t)b] / fn;
+            if (dsrt_write_pfm((base + "_body_alpha.pfm").c_str(), planes.data(), width, height * nb, 1) != DSRT_OK) return fail("writing the bodies' coverage");
+        }
+        std::printf("Saved %s_{alpha,sun_alpha%s}.pfm\n", base.c_str(), nb ? ",body_alpha" : "");
+        return 0;
+    };
+
     // --body: a batch launch has one scene and therefore one set of poses (include/dsrt.h), so a run with bodies renders one launch per frame
     if (!bodies.empty() && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
         DsrtStats st;
@@ -415,6 +483,7 @@ int main(int argc, char** argv) {
         }
         if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
         if (const int rc = frame_step(q, frame_base(ids[q]))) return rc;
+        if (coverage) if (const int rc = write_coverage(frame_base(ids[q]))) return rc;
     }
     size_t per_launch = 32;
     while (per_launch > 1 && (unsigned long long)per_launch * width * height * (rng_mode == 1 ? 16ull : 1ull) >= (1ull << 32)) per_launch /= 2;
@@ -428,10 +497,11 @@ int main(int argc, char** argv) {
             const std::string base = frame_base(ids[k + q]), path = base + ext;
             if (!write_image(path, fb.data() + q * image_bytes)) return fail("writing the frame");
             std::printf("Saved %s\n", path.c_str());
-            if (gbuffer) {
+            if (gbuffer || coverage) {
                 // (the batch launch above took camera and sun as arguments: the context's are set to this frame's)
                 if (dsrt_scene_set_camera_sun(ctx, &cams[k + q], suns.data() + 3 * (k + q)) != DSRT_OK) return fail("setting the camera");
-                if (const int rc = write_gbuffer(base)) return rc;
+                if (gbuffer) if (const int rc = write_gbuffer(base)) return rc;
+                if (coverage) if (const int rc = write_coverage(base)) return rc;
             }
         }
     }

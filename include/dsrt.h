@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -60,6 +60,9 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_UPSCALE     16
 #define DSRT_SIZEOF_TEMPORAL_SHADING 19
 #define DSRT_SIZEOF_BODY_MOTION 18   /* (17 is left unassigned and answers 0: tests/test_upscale_host.py holds it to that as the first unknown index of its day) */
+#define DSRT_SIZEOF_COVERAGE_DESC 20
+#define DSRT_SIZEOF_COVERAGE      21
+#define DSRT_SIZEOF_COVERAGE_CLASSES 22
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -498,6 +501,69 @@ int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const Dsrt
 int dsrt_render_gbuffer_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtGBuffer* gb, DsrtStats* stats);
 
 /*
+ * COVERAGE.  Sub-pixel ground truth: n primary rays per pixel instead of one, and per pixel how many of them hit (a soft mask), which (a bit mask), how many of
+ * the hits see the Sun (an antialiased shadow mask), how many fall into each of up to 16 triangle ranges (per-body soft masks), and the whole G-buffer record of
+ * one REPRESENTATIVE hit.  Camera, sun, tree and hit are the G-BUFFER's: the context's current camera and sun, scene_hit(ray, 0.001f, 1e9f) on the REFERENCE tree.
+ * No reference counterpart.  No sinf / cosf / powf: DsrtRenderDesc.math_mode does not matter.
+ *
+ * THE ARITHMETIC.  fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written.
+ *   Sub-samples, DsrtCoverageDesc {pattern, samples}:
+ *     DSRT_COVERAGE_GRID (0)      samples = S in 1..8, n = S*S;  sub-sample k = j*S + i (0 <= i, j < S):
+ *                                   jx = ((float)i + 0.5f) / (float)S;   jy = ((float)j + 0.5f) / (float)S        -- measures the covered AREA of the pixel
+ *     DSRT_COVERAGE_DIAGONAL (1)  samples = n in 1..64;  sub-sample k:
+ *                                   jx = jy = ((float)k + 0.5f) / (float)n                                          -- measures the covered share of the pixel's DIAGONAL,
+ *                                   which is what a render converges to: the renderer takes jx and jy of sample k both from stratum k (src/gpu_render.cu:995-996)
+ *     anything else is DSRT_ERR_INVALID.
+ *   The ray of sub-sample k of pixel (x, buffer row r), W x H the image:
+ *     ky = H-1-r;   u = ((float)x + jx) / (float)(W-1);   v = ((float)ky + jy) / (float)(H-1);   rd = ((llc + h*u) + vert*v) - o
+ *     -- make_camera_ray_jittered (:941-968) as the G-buffer pass forms it; on the CPU the oracle's camera-ray function (oracle/dsrt_oracle.h) with cam, x, ky, W, H, jx, jy.
+ *   Its hit is scene_hit(ray, 0.001f, 1e9f); "sees the Sun" is DSRT_GB_SUN_VISIBLE's rule applied to that sub-sample's own hit.
+ *   The representative: among the sub-samples that hit, the one with the smallest integer key, ties to the smaller k:
+ *     GRID  key = (2i+1-S)^2 + (2j+1-S)^2          DIAGONAL  key = (2k+1-n)^2          (the squared distance from the pixel centre, in units of half a cell)
+ *   CONSEQUENCE: for an odd S (an odd n) the centre sub-sample has key 0 and jx = jy = 0.5f exactly -- (float)((S-1)/2) + 0.5f is exactly S/2, and (S/2) / S is exactly
+ *   0.5f -- so wherever the centre ray hits, `rep` is dsrt_render_gbuffer's pixel bit for bit, and samples = 1 (either pattern) IS the G-buffer.
+ *
+ * OUTPUTS.  DsrtCoverage holds DEVICE buffers of width*height elements in image order, each optional (NULL = not written):
+ *   hits        u8        number of sub-samples that hit, 0..64
+ *   alpha       f32       (float)hits / (float)n, one IEEE division
+ *   mask        u64       bit k set iff sub-sample k hit
+ *   sun_hits, sun_alpha, sun_mask    u8, f32, u64    the same for "hit and sees the Sun"; all 0 when the sun is disabled
+ *   class_hits  u8 x classes->count per pixel (pixel-major)    sub-samples whose hit is a triangle with prim_id in class c:
+ *                         prim >= first[c] && (uint32_t)(prim - first[c]) < (uint32_t)num[c] -- the range rule of TEMPORAL ACCUMULATION WITH BODIES; classes may
+ *                         overlap or leave triangles out; spheres belong to no class.  dsrt_host_scene_body_range per body gives per-body masks.
+ *   rep         a DsrtGBuffer: every G-buffer channel of the representative sub-sample (the table of GROUND-TRUTH G-BUFFER, with that sub-sample's ray);
+ *               the miss values of that table when nothing hit.
+ * The shadow rays are traced only when a sun output or rep.flags is asked for.
+ *
+ * dsrt_render_coverage: dsrt_render_gbuffer's envelope -- uses desc->width / height only; asynchronous on `stream` unless `stats` is given (then kernel_ms,
+ *   waves_launched, device_flags); waits for the context's previous launch, the next launch waits for it; camera, sun, scene and working buffers are left as they were.
+ *   DSRT_ERR_INVALID: what dsrt_render_gbuffer refuses; a NULL cov_desc or cov; no output at all; a pointer not aligned to its element (4 bytes for f32 and i32, 8 for
+ *   u64); a pattern or `samples` outside the above; classes->count outside 0..16; a negative num; class_hits given without classes (or with count 0).
+ *   DSRT_ERR_NO_SCENE before an upload.  A refused call touches no buffer.
+ * dsrt_render_coverage_to_host: the same into HOST buffers, synchronously.
+ * dsrt_coverage_defaults: DIAGONAL, 64 -- the pattern that COVERAGE DEMODULATION (DENOISER) wants.
+ */
+#define DSRT_COVERAGE_GRID     0
+#define DSRT_COVERAGE_DIAGONAL 1
+typedef struct DsrtCoverageDesc { int pattern; int samples; } DsrtCoverageDesc;
+typedef struct DsrtCoverageClasses { int count /* 0..16 */; int first[16]; int num[16]; } DsrtCoverageClasses;
+typedef struct DsrtCoverage {
+    uint8_t*  hits;
+    float*    alpha;
+    uint64_t* mask;
+    uint8_t*  sun_hits;
+    float*    sun_alpha;
+    uint64_t* sun_mask;
+    uint8_t*  class_hits;
+    DsrtGBuffer rep;
+} DsrtCoverage;
+void dsrt_coverage_defaults(DsrtCoverageDesc* out);
+int dsrt_render_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cov_desc, const DsrtCoverageClasses* classes /* NULL ok */,
+                         const DsrtCoverage* cov, void* stream, DsrtStats* stats);
+int dsrt_render_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cov_desc, const DsrtCoverageClasses* classes,
+                                 const DsrtCoverage* cov, DsrtStats* stats);
+
+/*
  * RAY QUERIES.  Caller-supplied rays against the resident scene: for ray i, the reference's scene_hit(ray_i, t_min_i, t_max_i) (src/gpu_render.cu:509-551),
  * bit for bit -- the triangle walk on the REFERENCE tree (also when the certified second tree is resident), then the spheres in order; equal t is accepted,
  * so ties resolve by the reference's visit order.  t_min reaches every place the reference uses it (box entry, the triangle test, both sphere roots); t_max is
@@ -652,7 +718,8 @@ int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, c
  * The Cauchy weights 1/(1+e^2) stand where SVGF has exp(-e): expf is in no correctly rounded set, and the filter does not need it.  The geometry term is the distance
  * of q's hit point from p's tangent plane relative to p's range: zero along a flat oblique surface, which a depth difference gets wrong.
  * BACKGROUND AND SILHOUETTE: a pixel whose centre ray misses is never touched and never contributes -- space stays black and the silhouette stays where the renderer
- * put it; so the partially covered pixels just OUTSIDE the silhouette (centre ray misses, some samples hit) stay unfiltered.
+ * put it; so the partially covered pixels just OUTSIDE the silhouette (centre ray misses, some samples hit) stay unfiltered
+ * -- unless the call is given their coverage: COVERAGE DEMODULATION below.
  * Guides must be finite wherever `range` is finite; the call does not check.
  *
  * dsrt_denoise_accumulated: at least one of d_rgb8 (bytes), d_f32, d_linear, d_var (floats), each width*height*3 elements.  Asynchronous on `stream`; like
@@ -668,6 +735,21 @@ int dsrt_render_adaptive_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, c
  * dsrt_denoise_defaults: iterations 5, normal_power_log2 5, sigma_l 1, sigma_z 0.01, sigma_a 0.1.  sigma_l was first set to SVGF's 4; on the parity scenes at 8 and
  *   16 samples per pixel that blurs the station's sun shadows until the error RISES with the iterations (1.2 times the unfiltered error after five), while with 1 --
  *   a tap's weight halves at one standard deviation of luminance -- it falls to about half and stays there (tests/test_denoise_host.py).
+ *
+ * COVERAGE DEMODULATION (dsrt_denoise_accumulated_coverage).  Space is exactly black, so a pixel's mean is alpha x (the radiance of its covered part), alpha the
+ * share of its samples that hit.  With a per-pixel alpha (d_alpha, one float per pixel: the `alpha` of a DIAGONAL coverage pass, the renderer's own measure) the
+ * filter works on the covered part and the result is multiplied by alpha again; with the `rep` channels of that pass as guides, a pixel whose centre ray misses but
+ * whose samples hit becomes filterable.  With a = alpha_p:
+ *     F_p = (range_p <= FLT_MAX) && n >= 2 && a >= alpha_min          (a NaN alpha is not filterable)
+ *   Start, for F_p:    c.k = c.k / a;   aa = a * a;   v.k = v.k / aa.   A pixel that is not F_p keeps c and v bit for bit, and is never a tap.
+ *   Iterations: the ones above, untouched.
+ *   Output, for F_p:   c.k = c'.k * a;   v.k = v'.k * aa   (aa = a * a again);  d_linear and d_var are these, and the tone map is applied to that c.
+ * alpha_min must be in (0, 1] (a NaN is refused); d_alpha is 4-byte aligned and overlaps no output.  Everything else is dsrt_denoise_accumulated's.  Two identities:
+ * d_alpha == NULL is dsrt_denoise_accumulated bit for bit (alpha_min is then not looked at beyond its check), and so is an alpha that is 1.0f everywhere with any
+ * legal alpha_min, since x / 1 and x * 1 are exact.
+ * dsrt_render_denoised_coverage_to_host: the convenience form -- desc->spp samples with second moments, a DIAGONAL coverage pass (cov_desc NULL = dsrt_coverage_defaults;
+ *   a GRID pattern is refused) whose alpha and rep channels are the alpha and the guides, and the call above.  h_alpha (optional) receives that alpha.
+ * dsrt_denoise_coverage_alpha_min: the default alpha_min (DESIGN.md section 4 says how it was chosen).
  */
 typedef struct DsrtDenoiseGuides {   /* DEVICE (HOST for _to_host) buffers, width*height elements, image order: channels of DsrtGBuffer */
     const float* normal;             /* x3 */
@@ -683,6 +765,15 @@ int  dsrt_denoise_accumulated_to_host(DsrtContext* ctx, const DsrtRenderDesc* de
                                       const DsrtDenoiseGuides* h_guides, const DsrtDenoise* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var);
 int  dsrt_render_denoised_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtDenoise* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var,
                                   DsrtStats* stats);
+float dsrt_denoise_coverage_alpha_min(void);
+int  dsrt_denoise_accumulated_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* acc, int samples_done, const uint32_t* d_n, const DsrtDenoiseGuides* guides,
+                                       const float* d_alpha /* NULL = dsrt_denoise_accumulated */, float alpha_min, const DsrtDenoise* params, uint8_t* d_rgb8, float* d_f32,
+                                       float* d_linear, float* d_var, void* stream);
+int  dsrt_denoise_accumulated_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtAccum* h_acc, int samples_done, const uint32_t* h_n,
+                                               const DsrtDenoiseGuides* h_guides, const float* h_alpha, float alpha_min, const DsrtDenoise* params, uint8_t* h_rgb8,
+                                               float* h_f32, float* h_linear, float* h_var);
+int  dsrt_render_denoised_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtCoverageDesc* cov_desc, float alpha_min, const DsrtDenoise* params,
+                                           uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_alpha, DsrtStats* stats);
 
 /*
  * TEMPORAL ACCUMULATION (rng_mode 1, on top of the DENOISER): the other half of SVGF -- a frame's mean and variance blended with the history of the frames before it,
