@@ -1109,6 +1109,41 @@ class Context:
         _check(lib.dsrt_selftest_poke_node_word(self._h, int(word_index), int(value) & 0xFFFFFFFF, C.byref(old)), "dsrt_selftest_poke_node_word")
         return old.value
 
+    SCHEDULE_ARRAYS = ("tile_cost", "tile_order", "tile_work", "batch_table", "pixel_list")
+
+    def read_schedule(self, array, first_word, n_words):
+        """Test hook (dsrt_selftest_read_schedule): n_words 32-bit words of a working buffer of the scheduling pre-pass as the context's last launch left it;
+        `array` a name of SCHEDULE_ARRAYS or its number.  include/dsrt.h says what is valid when."""
+        which = self.SCHEDULE_ARRAYS.index(array) if isinstance(array, str) else int(array)
+        out = np.zeros(int(n_words), np.uint32)
+        _check(lib.dsrt_selftest_read_schedule(self._h, which, int(first_word), int(n_words), out.ctypes.data), "dsrt_selftest_read_schedule")
+        return out
+
+    def selftest_tile_order(self, cost, tile, items_per_pixel, resident_lanes, spp):
+        """dsrt_selftest_tile_order: dsrt_tile_order_kernel on the cost words given -> (order, sched[5]); order entries the kernel did not write are 0xFFFFFFFF."""
+        cost = np.ascontiguousarray(cost, np.uint32)
+        order, sched = np.zeros(cost.size, np.uint32), np.zeros(5, np.uint32)
+        _check(lib.dsrt_selftest_tile_order(self._h, cost.ctypes.data if cost.size else None, int(cost.size), int(tile), int(items_per_pixel), int(resident_lanes), int(spp),
+                                            order.ctypes.data if cost.size else None, sched.ctypes.data), "dsrt_selftest_tile_order")
+        return order, sched
+
+    def selftest_tile_reorder(self, work, order, sched):
+        """dsrt_selftest_tile_reorder: dsrt_tile_reorder_kernel on (work, order, sched[5]) -> the order it leaves."""
+        work, out, sched = np.ascontiguousarray(work, np.uint32), np.array(order, np.uint32), np.ascontiguousarray(sched, np.uint32)
+        _check(lib.dsrt_selftest_tile_reorder(self._h, work.ctypes.data if work.size else None, int(work.size), out.ctypes.data if out.size else None, int(out.size),
+                                              sched.ctypes.data), "dsrt_selftest_tile_reorder")
+        return out
+
+    def selftest_batch_table(self, sched, tt, rng_mode, spp, light_chunk_len, order_base):
+        """dsrt_selftest_batch_table: dsrt_batch_table_kernel on `sched` (frames x >= 5 words) and the frames' order_base -> (table words (2 * frames, 24), total)."""
+        sched = np.ascontiguousarray(sched, np.uint32)
+        frames, stride = sched.shape
+        base = np.ascontiguousarray(order_base, np.uint32)
+        table, total = np.zeros((2 * frames, 24), np.uint32), np.zeros(1, np.uint32)
+        _check(lib.dsrt_selftest_batch_table(self._h, sched.ctypes.data, stride, frames, int(tt), int(rng_mode), int(spp), int(light_chunk_len), base.ctypes.data,
+                                             table.ctypes.data, total.ctypes.data), "dsrt_selftest_batch_table")
+        return table, int(total[0])
+
     def selftest_philox(self, seed, subsequence, n):
         ours, theirs = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         _check(lib.dsrt_selftest_philox(self._h, int(seed), int(subsequence), int(n), ours.ctypes.data, theirs.ctypes.data), "dsrt_selftest_philox")

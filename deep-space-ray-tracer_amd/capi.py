@@ -207,6 +207,7 @@ EXPORTS = [
     "dsrt_denoise_temporal_shaded", "dsrt_denoise_temporal_shaded_to_host", "dsrt_ctx_set_temporal_shading", "dsrt_ctx_temporal_shading",
     "dsrt_coverage_defaults", "dsrt_render_coverage", "dsrt_render_coverage_to_host", "dsrt_denoise_coverage_alpha_min", "dsrt_denoise_accumulated_coverage",
     "dsrt_denoise_accumulated_coverage_to_host", "dsrt_render_denoised_coverage_to_host",
+    "dsrt_selftest_read_schedule", "dsrt_selftest_tile_order", "dsrt_selftest_tile_reorder", "dsrt_selftest_batch_table",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
 
@@ -355,6 +356,10 @@ def load():
     sig("dsrt_selftest_math", C.c_int, [vp, C.c_int, vp, C.c_float, vp, C.c_int])
     sig("dsrt_selftest_devkat", C.c_int, [vp, C.c_int, vp, vp, C.c_int])
     sig("dsrt_selftest_philox", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, vp, vp])
+    sig("dsrt_selftest_read_schedule", C.c_int, [vp, C.c_int, C.c_size_t, C.c_size_t, vp])
+    sig("dsrt_selftest_tile_order", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, vp, vp])
+    sig("dsrt_selftest_tile_reorder", C.c_int, [vp, vp, C.c_int, vp, C.c_int, vp])
+    sig("dsrt_selftest_batch_table", C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp])
     sig("dsrt_microbench_gather", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, P(C.c_float), P(C.c_double)])
     sig("dsrt_microbench_valu", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, P(C.c_float), P(C.c_double), P(C.c_double)])
     sig("dsrt_microbench_valu_kinds", C.c_int, [])

@@ -51,7 +51,7 @@ struct RenderPlan {
     bool own_sums;                    // rng_mode 1 of dsrt_render(_batch): the sums are the context's, zeroed before and resolved behind the launch
     int frames, chunks, chunk_len, blocks;
     size_t out_pixels, pre_stride;    // pre_stride, per frame: tile costs / order, then the sched words
-    uint32_t* sched;                  // {tiles that see geometry, tiles in the order, heavy lanes per wave}: the words 32 entries past the cost array (grow_render_buffers)
+    uint32_t* sched;                  // {heavy tiles, tiles in the order, heavy lanes per wave, slices, chunk_len} (device_layout.h): the words 32 entries past the cost array (grow_render_buffers)
 };
 
 int plan_render(const DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_rgb8, float* d_f32, const BatchInput* batch, const AccumInput* acc, RenderPlan& p) {
@@ -194,8 +194,8 @@ int plan_render(const DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_r
 
     // Pre-pass for this camera: costliest-first tile order (scheduling only) and removal of tiles that are provably empty (exact:
     // see dsrt_tile_cost_kernel).  DSRT_TUNE_NATURAL_ORDER switches both off, DSRT_TUNE_NO_CULLING keeps the order but culls nothing; counting builds never
-    // cull, so that their counters cover every sample.  The words 32 and 48 entries past the cost array receive the number of
-    // tiles that see geometry and the number of tiles in the order.
+    // cull, so that their counters cover every sample.  The words 32 and 33 entries past the cost array receive the number of
+    // heavy tiles and the number of tiles in the order.
     p.pre_stride = (size_t)t.mine + 64;
     if (p.pre_stride * (size_t)p.frames >= ((size_t)1 << 32)) { set_error("dsrt_render_batch: too many tiles in one batch (split the sequence)"); return DSRT_ERR_INVALID; }
     p.pre = batch ? PrePass::Batch : ((flags & 3u) != DSRT_TUNE_NATURAL_ORDER && t.mine > 0 ? PrePass::Ordered : PrePass::Natural);

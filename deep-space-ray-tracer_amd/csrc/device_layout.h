@@ -116,7 +116,7 @@ struct BatchFrame {
     float    sun_dir[3];
     uint32_t item_end;         // work items of frames 0 .. this one (exclusive end of this frame's range in the batch queue)
     uint32_t order_base;       // where this frame's tile order starts in RenderArgs::batch_order
-    uint32_t n_heavy, n_live;  // tiles that see geometry / tiles not proven empty
+    uint32_t n_heavy, n_live;  // heavy tiles (RenderArgs::sched below) / tiles not proven empty, of this ENTRY's share of the frame
     uint32_t slices, chunk_len; // rng_mode 1: work items per heavy pixel and their length
     uint32_t image_slot;       // which of the launch's output images this entry's pixels belong to
     uint32_t pad[2];
@@ -131,9 +131,12 @@ struct RenderArgs {
     uint32_t* queue;           // next work item of the HEAVY queue (pixels, or sample slices, of tiles that see geometry)
     uint32_t* queue_light;     // next work item of the LIGHT queue (pixels of the other live tiles); its own cache line
     const uint32_t* sched;     // written by the pre-pass, read-only during the render (path_machine.h, ST_FETCH):
-                               //   [0] n_heavy  tiles that see geometry (the first n_heavy entries of tile_order)
+                               //   [0] n_heavy  HEAVY tiles: at least 1/64 of the tile's pixels see geometry (the first n_heavy entries of tile_order; with
+                               //                8-pixel tiles: one pixel.  A 16- or 32-pixel tile that sees less is LIGHT, like one that sees nothing)
                                //   [1] n_live   tiles in tile_order: the shard's tiles minus those proven empty
                                //   [2] spread   lanes per wave (1..64) that serve the heavy queue first; the others start on the light one
+                               //   [3] slices   rng_mode 1: work items per heavy pixel (1 otherwise)      [4] chunk_len   samples per such item
+                               //   (DESIGN.md section 4 has the table; tests/_schedule_model.py computes every word)
     uint32_t* probe_queue;     // probe launch only: 64 queue words, 64 bytes apart (path_machine.h, ST_FETCH)
     int       hot;             // rng_mode 0: 1 = a wave that holds a pixel of a heavy tile raises its issue priority (render_body)
     union {

@@ -30,6 +30,9 @@ const RenderLaunchers& render_launchers(bool device_libm);          // device_ap
 // render_kernel.hip, first compilation only: the scheduling pre-pass ...
 hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_t* cost, uint32_t* order, uint32_t* sched, uint32_t items_per_pixel,
                              uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch = nullptr, uint32_t frames = 1, uint32_t stride = 0);
+// (dsrt_selftest_tile_order: the order kernel alone, one frame, on cost words the caller supplies -- no cost kernel in front)
+hipError_t launch_tile_order_arrays(const uint32_t* cost, uint32_t* order, int n, int tile, uint32_t* sched, uint32_t items_per_pixel, uint32_t resident_lanes, int spp,
+                                    hipStream_t stream);
 hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* tmp, const uint32_t* sched, hipStream_t stream);
 hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
                               uint32_t* total_items, hipStream_t stream);

@@ -525,7 +525,8 @@ __global__ void __launch_bounds__(256) dsrt_tile_cost_kernel(const DeviceScene S
     if (lane == 0 && n) atomicAdd(&cost[k], n);
 }
 
-// One block: counting sort of the shard's live tiles by cost, costliest first (65 bins; order inside a bin does not matter).
+// One block: counting sort of the shard's live tiles by cost, costliest first (65 bins; order inside a bin does not matter).  bin = 64 - min(64, pixels that see
+// geometry * 64 / tile^2); the tiles of bin 64 are the LIGHT tiles, the others -- at least 1/64 of their pixels see geometry -- the HEAVY ones, sched[0] of them.
 // (batch launches: one block per frame, the frames' arrays `stride` apart)
 __global__ void __launch_bounds__(1024) dsrt_tile_order_kernel(const uint32_t* __restrict__ cost, uint32_t* __restrict__ order, int n, int tile,
                                                                uint32_t* __restrict__ sched, uint32_t items_per_pixel, uint32_t resident_lanes, int spp, uint32_t stride) {
@@ -563,7 +564,7 @@ __global__ void __launch_bounds__(1024) dsrt_tile_order_kernel(const uint32_t* _
 }
 
 // Refinement of the order by measured cost: a probe launch of the render kernel itself (a few samples per pixel, same state
-// machine) has left the number of rays it traced for every tile in `work`; the tiles that see geometry -- the first sched[0]
+// machine) has left the number of rays it traced for every tile in `work`; the heavy tiles -- the first sched[0]
 // entries of `order` -- are re-sorted by it, most work first, so the pixels with the longest serial sample chains start at
 // once instead of wherever their tile's coverage count put them.  Scheduling only.
 __global__ void __launch_bounds__(1024) dsrt_tile_reorder_kernel(const uint32_t* __restrict__ work, uint32_t* __restrict__ order, uint32_t* __restrict__ tmp,
@@ -759,6 +760,12 @@ hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_
     }
     hipLaunchKernelGGL(dsrt_tile_cost_kernel, dim3((waves + 3) / 4, frames), dim3(256), 0, stream, S, P, cost, cull ? 1 : 0, batch, stride);
     hipLaunchKernelGGL(dsrt_tile_order_kernel, dim3(frames), dim3(1024), 0, stream, (const uint32_t*)cost, order, P.local_tiles, P.tile, sched, items_per_pixel, resident_lanes, P.spp, stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_order_arrays(const uint32_t* cost, uint32_t* order, int n, int tile, uint32_t* sched, uint32_t items_per_pixel, uint32_t resident_lanes, int spp,
+                                    hipStream_t stream) {
+    hipLaunchKernelGGL(dsrt_tile_order_kernel, dim3(1), dim3(1024), 0, stream, cost, order, n, tile, sched, items_per_pixel, resident_lanes, spp, 0u);
     return hipGetLastError();
 }
 

@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -1087,6 +1087,42 @@ int dsrt_selftest_devkat(DsrtContext* ctx, int fn, const float* in12, float* out
 /* Device check that the kernel's stateless Philox4x32-10 equals rocRAND's engine: the first n 32-bit words of
  * (seed, subsequence, offset 0) from both.  Host pointers. */
 int dsrt_selftest_philox(DsrtContext* ctx, uint64_t seed, uint64_t subsequence, int n, uint32_t* ours, uint32_t* rocrand_words);
+
+/* SELFTEST: the scheduling pre-pass ("Pre-pass, probe, rng_mode 1, batch"; tests/_schedule_model.py is its CPU model).  Test hooks only:
+ * nothing else calls them, and none changes what a launch does.
+ *
+ * dsrt_selftest_read_schedule: n_words (>= 1) 32-bit words from word first_word of one of the working buffers the context's LAST launch left, after waiting
+ * for the device.  The range is checked against the buffer's ALLOCATED length (buffers only grow: words beyond what the last launch wrote are stale or
+ * never written); a range outside it, an array no launch of this context has allocated yet, an unknown array and a null pointer are refused with
+ * DSRT_ERR_INVALID and `out` is not touched.  With mine = tiles_this_shard of dsrt_shard_layout, pre_stride = mine + 64, and frame f of a batch (f = 0 for
+ * a single frame) at f * pre_stride:
+ *   array 0, tile_cost    [0, mine)      the cost words: bit 31 = at least one 8x8 block of the tile is not provably empty, low bits = pixels whose centre ray
+ *                                        hits anything.  Not written by a DSRT_TUNE_NATURAL_ORDER launch.
+ *                         mine + 32 ...  the sched words: [0] n_heavy, [1] n_live, [2] spread, [3] slices, [4] chunk_len (every launch writes them;
+ *                                        a natural-order launch: mine, mine, 64, the host's slices and chunk_len)
+ *                         mine + 40, 41  list_len: the lengths of the heavy and the light pixel list (dsrt_render_accumulate_masked only)
+ *   array 1, tile_order   [0, n_live)    the local tiles in the order they are handed out, heavy part [0, n_heavy) first.  STALE after a
+ *                                        DSRT_TUNE_NATURAL_ORDER launch (that launch has no order array); entries from n_live on are never written.
+ *   array 2, tile_work    [0, mine)      meaningful only after a probe (rng_mode 0, spp >= 256, no DSRT_TUNE_NO_PROBE / NATURAL_ORDER): per local tile the most
+ *                                        rays one of its pixels needed for the probe's 4 samples, capped at 255; 0 for a tile outside the heavy part.  After a
+ *                                        batch: the LAST frame's probe.
+ *   array 3, batch_table  24 words per entry, 2 * frames entries (dsrt_render_batch only): cam[12], sun_dir[3], item_end, order_base, n_heavy, n_live, slices,
+ *                                        chunk_len, image_slot, 2 unused.  Entry f is the first eighth of frame f's heavy tiles, entry frames + f the rest.
+ *   array 4, pixel_list   (dsrt_render_accumulate_masked only) [0, mine * tile^2): the heavy list from 0, the light list from n_heavy * tile^2, entries
+ *                                        x | row << 16; then one word per 8x8 block of every live tile in order: its exclusive offset into the two lists run together.
+ *
+ * The three array kernels of the pre-pass on plain HOST arrays, with temporary device buffers of their own, as dsrt_selftest_math runs the math kernel:
+ *   dsrt_selftest_tile_order    cost[n] (low bits <= tile^2) -> order[n] (entries the kernel does not write: 0xFFFFFFFF) and sched5[0..4]; n may be 0.
+ *   dsrt_selftest_tile_reorder  work[n_work], order[n_order] (in place), sched5 (sched5[0] <= n_order heavy entries, each below n_work; sched5[2] < 64 = dealt).
+ *   dsrt_selftest_batch_table   per frame 5 sched words sched_stride (>= 5) apart and an order_base -> table_words[2 * frames * 24] (cameras zero, image_slot f) and the
+ *                               total of work items.  tt = pixels per tile.
+ * Anything that would make a kernel read or write outside those arrays is refused with DSRT_ERR_INVALID before anything is launched. */
+int dsrt_selftest_read_schedule(DsrtContext* ctx, int array, size_t first_word, size_t n_words, uint32_t* out);
+int dsrt_selftest_tile_order(DsrtContext* ctx, const uint32_t* cost, int n, int tile, uint32_t items_per_pixel, uint32_t resident_lanes, int spp, uint32_t* order,
+                             uint32_t* sched5);
+int dsrt_selftest_tile_reorder(DsrtContext* ctx, const uint32_t* work, int n_work, uint32_t* order, int n_order, const uint32_t* sched5);
+int dsrt_selftest_batch_table(DsrtContext* ctx, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
+                              const uint32_t* order_base, uint32_t* table_words, uint32_t* total_items);
 
 /* ===================================================================================== */
 /* All GPUs of a node from ONE host process (the reference's main() is one process calling */
