@@ -255,15 +255,20 @@ def make_desc(width, height, spp, max_depth=50, gamma=2.0, seed=1337, tile_size=
 DENOISE_GUIDES = ("normal", "position", "albedo", "range")            # DsrtDenoiseGuides' channels: G-buffer channels of those names (capi.GBUFFER_CHANNELS)
 
 
-def denoise_defaults(**changes):
-    """dsrt_denoise_defaults: the DsrtDenoise the library fills (iterations, normal_power_log2, sigma_l, sigma_z, sigma_a), with `changes` applied."""
-    p = capi.DsrtDenoise()
-    lib.dsrt_denoise_defaults(C.byref(p))
+def _defaults(struct, fill, changes):
+    """A `struct` as the library's `fill` function leaves it, with `changes` = {field: value} applied."""
+    p = struct()
+    fill(C.byref(p))
     for k, v in changes.items():
-        if k not in dict(capi.DsrtDenoise._fields_):
-            raise ValueError(f"DsrtDenoise has no field {k!r}")
+        if k not in dict(struct._fields_):
+            raise ValueError(f"{struct.__name__} has no field {k!r}")
         setattr(p, k, v)
     return p
+
+
+def denoise_defaults(**changes):
+    """dsrt_denoise_defaults: the DsrtDenoise the library fills (iterations, normal_power_log2, sigma_l, sigma_z, sigma_a), with `changes` applied."""
+    return _defaults(capi.DsrtDenoise, lib.dsrt_denoise_defaults, changes)
 
 
 def coverage_desc(pattern=None, samples=None):
@@ -302,13 +307,7 @@ def coverage_alpha_min():
 
 def temporal_defaults(**changes):
     """dsrt_temporal_defaults: the DsrtTemporal the library fills (alpha_min, normal_cos_min, plane_tol, min_support), with `changes` applied."""
-    p = capi.DsrtTemporal()
-    lib.dsrt_temporal_defaults(C.byref(p))
-    for k, v in changes.items():
-        if k not in dict(capi.DsrtTemporal._fields_):
-            raise ValueError(f"DsrtTemporal has no field {k!r}")
-        setattr(p, k, v)
-    return p
+    return _defaults(capi.DsrtTemporal, lib.dsrt_temporal_defaults, changes)
 
 
 def temporal_shading(flags_ptr, edge_guard=1):
@@ -322,13 +321,7 @@ UPSCALE_GUIDES = DENOISE_GUIDES + ("flags",)                         # DsrtUpsca
 
 def upscale_defaults(**changes):
     """dsrt_upscale_defaults: the DsrtUpscale the library fills (normal_power_log2, sigma_z, sigma_a, use_sun), with `changes` applied."""
-    p = capi.DsrtUpscale()
-    lib.dsrt_upscale_defaults(C.byref(p))
-    for k, v in changes.items():
-        if k not in dict(capi.DsrtUpscale._fields_):
-            raise ValueError(f"DsrtUpscale has no field {k!r}")
-        setattr(p, k, v)
-    return p
+    return _defaults(capi.DsrtUpscale, lib.dsrt_upscale_defaults, changes)
 
 
 def aligned_zeros(count, dtype=np.float32, align=64):
@@ -811,127 +804,106 @@ class Context:
             out[k] = self._device_tensor(x, _torch.float32, (desc.width * desc.height * comps, f"width*height*{comps}"), f"guide {k}")
         return out
 
-    def _denoise(self, what, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream, temporal=None, motion=None, shading=None, coverage=None):
-        """denoise_accumulated and, with temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None), denoise_temporal: the outputs `wants` names.
-        motion = (first_tri, num_tris, poses_prev, poses_cur, prim_id tensor): denoise_temporal_bodies.  shading = (flags tensor, edge_guard): denoise_temporal_shaded,
-        with or without a motion."""
-        acc = self._accum(desc, sums, sum_sq)
-        n = self._pixel_tensor(desc, n, _torch.int32, "n", required=False)
-        if n is None and samples_done is None:
-            raise ValueError(f"{what} needs samples_done or per-pixel counts n")
-        gd = capi.DsrtDenoiseGuides(**{k: _tensor_ptr(x) for k, x in self._guide_tensors(desc, guides).items()})
+    def _denoise(self, on_device, desc, sums, sum_sq, guides, samples_done, n, params, wants, stream=None, temporal=None, motion=None, shading=None, coverage=None):
+        """Every denoise_* method: from torch device tensors (on_device) or from numpy arrays into numpy arrays (the _to_host entry points); the outputs `wants` names.
+        coverage = (alpha or None, alpha_min): denoise_accumulated_coverage.  temporal = (prev_camera, history_prev, history_next, DsrtTemporal or None):
+        denoise_temporal; the host form makes the next history itself and returns it last.  motion = (first_tri, num_tris, poses_prev, poses_cur, prim_id):
+        denoise_temporal_bodies.  shading = (flags, edge_guard): denoise_temporal_shaded, with or without a motion."""
+        H, W = desc.height, desc.width
+        ptr = _tensor_ptr if on_device else _array_ptr
+        name = ("dsrt_denoise_accumulated_coverage" if coverage is not None else "dsrt_denoise_accumulated" if temporal is None else
+                "dsrt_denoise_temporal_shaded" if shading is not None else "dsrt_denoise_temporal_bodies" if motion is not None else "dsrt_denoise_temporal")
+
+        def pixels(x, dt, what, required=True):                                           # a width*height channel of the form's kind
+            if on_device:
+                return self._pixel_tensor(desc, x, getattr(_torch, np.dtype(dt).name), what, required)
+            return None if x is None and not required else np.ascontiguousarray(x, dt).reshape(H, W)
+
+        # the inputs
+        if on_device:
+            acc = self._accum(desc, sums, sum_sq)
+            n = pixels(n, np.int32, "n", required=False)
+            if n is None and samples_done is None:
+                raise ValueError(f"{name[5:]} needs samples_done or per-pixel counts n")
+            g = self._guide_tensors(desc, guides)
+        else:
+            S, S2 = (np.ascontiguousarray(x, np.uint64).reshape(H, W, 3) for x in (sums, sum_sq))
+            acc = DsrtAccum(_array_ptr(S), _array_ptr(S2))
+            n = pixels(n, np.uint32, "n", required=False)
+            if set(guides) != set(DENOISE_GUIDES):
+                raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
+            g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
+        gd = capi.DsrtDenoiseGuides(**{k: ptr(x) for k, x in g.items()})
         if temporal is not None:
             prev_camera, history_prev, history_next, tp = temporal
-            for name, h in (("history_prev", history_prev), ("history_next", history_next)):
-                if h is None:
-                    continue
-                if not isinstance(h, _torch.Tensor) or h.dtype != _torch.float32 or h.device.type != "cuda" or h.device.index != self.device:
-                    raise TypeError(f"{name} must be a float32 torch tensor on cuda:{self.device}")
-                self._device_tensor(h, _torch.float32, (desc.width * desc.height * capi.HISTORY_FLOATS, f"width*height*{capi.HISTORY_FLOATS}"), name)
+            hist = H * W * capi.HISTORY_FLOATS
+            if on_device:
+                for what, h in (("history_prev", history_prev), ("history_next", history_next)):
+                    if h is None:
+                        continue
+                    if not isinstance(h, _torch.Tensor) or h.dtype != _torch.float32 or h.device.type != "cuda" or h.device.index != self.device:
+                        raise TypeError(f"{what} must be a float32 torch tensor on cuda:{self.device}")
+                    self._device_tensor(h, _torch.float32, (hist, f"width*height*{capi.HISTORY_FLOATS}"), what)
+            else:                                                                         # (a host history is 16-byte aligned: copies that are)
+                if history_prev is not None:
+                    src, history_prev = history_prev, aligned_zeros(hist)
+                    history_prev[:] = np.asarray(src, np.float32).reshape(-1)
+                history_next = aligned_zeros(hist)
             tp = temporal_defaults() if tp is None else tp
         params = denoise_defaults() if params is None else params
-        out = _outputs(desc, wants, sums.device)
-        head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), _tensor_ptr(n), C.byref(gd))
-        tail = (C.byref(params), *map(_tensor_ptr, out), C.c_void_p(self._raw_stream(stream)))
-        if coverage is not None:                                                           # (alpha tensor or None, alpha_min): denoise_accumulated_coverage
-            alpha = self._pixel_tensor(desc, coverage[0], _torch.float32, "alpha", required=False)
-            _check(lib.dsrt_denoise_accumulated_coverage(*head, _tensor_ptr(alpha), C.c_float(coverage[1]), *tail), "dsrt_denoise_accumulated_coverage")
-        elif temporal is None:
-            _check(lib.dsrt_denoise_accumulated(*head, *tail), "dsrt_denoise_accumulated")
-        elif shading is not None:
-            m = keep = None
-            if motion is not None:
-                m, keep = _body_motion(*motion[:4], self._pixel_tensor(desc, motion[4], _torch.int32, "prim_id").data_ptr())
-            sh = temporal_shading(_tensor_ptr(self._pixel_tensor(desc, shading[0], _torch.uint8, "flags")), shading[1])
-            _check(lib.dsrt_denoise_temporal_shaded(*head, C.byref(m) if m is not None else None, C.byref(sh), C.byref(prev_camera) if prev_camera is not None else None,
-                                                    _tensor_ptr(history_prev), _tensor_ptr(history_next), C.byref(tp), *tail), "dsrt_denoise_temporal_shaded")
-        elif motion is not None:
-            prim = self._pixel_tensor(desc, motion[4], _torch.int32, "prim_id")
-            m, keep = _body_motion(*motion[:4], prim.data_ptr())
-            _check(lib.dsrt_denoise_temporal_bodies(*head, C.byref(m), C.byref(prev_camera) if prev_camera is not None else None, _tensor_ptr(history_prev),
-                                                    _tensor_ptr(history_next), C.byref(tp), *tail), "dsrt_denoise_temporal_bodies")
-        else:
-            _check(lib.dsrt_denoise_temporal(*head, C.byref(prev_camera) if prev_camera is not None else None, _tensor_ptr(history_prev), _tensor_ptr(history_next),
-                                             C.byref(tp), *tail), "dsrt_denoise_temporal")
-        return tuple(out)
+        out = _outputs(desc, wants, sums.device if on_device else None)
+        head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), ptr(n), C.byref(gd))
+        tail = (C.byref(params), *map(ptr, out)) + ((C.c_void_p(self._raw_stream(stream)),) if on_device else ())
 
-    def _denoise_to_host(self, desc, sums, sum_sq, guides, samples_done, n, params, wants, temporal=None, motion=None, shading=None, coverage=None):
-        """The same from numpy arrays into numpy arrays (temporal: (prev_camera, history_prev or None, DsrtTemporal or None); the next history is returned last)."""
-        H, W = desc.height, desc.width
-        S = np.ascontiguousarray(sums, np.uint64).reshape(H, W, 3)
-        S2 = np.ascontiguousarray(sum_sq, np.uint64).reshape(H, W, 3)
-        cnt = np.ascontiguousarray(n, np.uint32).reshape(H, W) if n is not None else None
-        if set(guides) != set(DENOISE_GUIDES):
-            raise ValueError(f"guides must hold exactly {list(DENOISE_GUIDES)}, not {sorted(guides)}")
-        g = {k: np.ascontiguousarray(guides[k], np.float32).reshape((H, W) + ((3,) if capi.GBUFFER_CHANNELS[k][1] == 3 else ())) for k in DENOISE_GUIDES}
-        acc = DsrtAccum(_array_ptr(S), _array_ptr(S2))
-        gd = capi.DsrtDenoiseGuides(**{k: _array_ptr(x) for k, x in g.items()})
-        if temporal is not None:
-            prev_camera, history_prev, tp = temporal
-            prev = None
-            if history_prev is not None:
-                prev = aligned_zeros(H * W * capi.HISTORY_FLOATS)
-                prev[:] = np.asarray(history_prev, np.float32).reshape(-1)
-            nxt = aligned_zeros(H * W * capi.HISTORY_FLOATS)
-            tp = temporal_defaults() if tp is None else tp
-        params = denoise_defaults() if params is None else params
-        out = _outputs(desc, wants)
-        head = (self._h, C.byref(desc), C.byref(acc), int(samples_done or 0), _array_ptr(cnt), C.byref(gd))
-        tail = (C.byref(params), *map(_array_ptr, out))
+        # the entry point's own arguments, between the two
+        mid, m, keep = (), None, None
         if coverage is not None:
-            alpha = np.ascontiguousarray(coverage[0], np.float32).reshape(H, W) if coverage[0] is not None else None
-            _check(lib.dsrt_denoise_accumulated_coverage_to_host(*head, _array_ptr(alpha), C.c_float(coverage[1]), *tail), "dsrt_denoise_accumulated_coverage_to_host")
-            return tuple(out)
-        if temporal is None:
-            _check(lib.dsrt_denoise_accumulated_to_host(*head, *tail), "dsrt_denoise_accumulated_to_host")
-            return tuple(out)
-        if shading is not None:
-            m = keep = None
+            alpha = pixels(coverage[0], np.float32, "alpha", required=False)
+            mid = (ptr(alpha), C.c_float(coverage[1]))
+        elif temporal is not None:
             if motion is not None:
-                prim = np.ascontiguousarray(motion[4], np.int32).reshape(H, W)
-                m, keep = _body_motion(*motion[:4], prim.ctypes.data)
-            flags = np.ascontiguousarray(shading[0], np.uint8).reshape(H, W)
-            sh = temporal_shading(_array_ptr(flags), shading[1])
-            _check(lib.dsrt_denoise_temporal_shaded_to_host(*head, C.byref(m) if m is not None else None, C.byref(sh), C.byref(prev_camera) if prev_camera is not None else None,
-                                                            _array_ptr(prev), _array_ptr(nxt), C.byref(tp), *tail), "dsrt_denoise_temporal_shaded_to_host")
-            return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
-        if motion is not None:
-            prim = np.ascontiguousarray(motion[4], np.int32).reshape(H, W)
-            m, keep = _body_motion(*motion[:4], prim.ctypes.data)
-            _check(lib.dsrt_denoise_temporal_bodies_to_host(*head, C.byref(m), C.byref(prev_camera) if prev_camera is not None else None, _array_ptr(prev), _array_ptr(nxt),
-                                                            C.byref(tp), *tail), "dsrt_denoise_temporal_bodies_to_host")
-            return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
-        _check(lib.dsrt_denoise_temporal_to_host(*head, C.byref(prev_camera) if prev_camera is not None else None, _array_ptr(prev), _array_ptr(nxt), C.byref(tp), *tail),
-               "dsrt_denoise_temporal_to_host")
-        return (*out, nxt.reshape(H, W, capi.HISTORY_FLOATS))
+                prim = pixels(motion[4], np.int32, "prim_id")
+                m, keep = _body_motion(*motion[:4], ptr(prim))
+            if shading is not None:
+                flags = pixels(shading[0], np.uint8, "flags")
+                sh = temporal_shading(ptr(flags), shading[1])
+                mid = (C.byref(m) if m is not None else None, C.byref(sh))
+            elif motion is not None:
+                mid = (C.byref(m),)
+            mid += (C.byref(prev_camera) if prev_camera is not None else None, ptr(history_prev), ptr(history_next), C.byref(tp))
+        if not on_device:
+            name += "_to_host"
+        _check(getattr(lib, name)(*head, *mid, *tail), name)
+        del keep
+        return tuple(out) if on_device or temporal is None else (*out, history_next.reshape(H, W, capi.HISTORY_FLOATS))
 
     def denoise_accumulated(self, desc, sums, sum_sq, guides, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
                             want_var=False, stream=None):
         """dsrt_denoise_accumulated: the filtered image of `sums` / `sum_sq` (int64 device tensors, as render_accumulate's) after `samples_done` samples per pixel
         or the per-pixel counts `n` (int32 device tensor), guided by `guides` = {"normal", "position", "albedo", "range": float32 device tensors, G-buffer
         channels}.  params: a DsrtDenoise (denoise_defaults()).  Returns (rgb8, f32, linear, var) device tensors of shape (height, width, 3), None where not asked for."""
-        return self._denoise("denoise_accumulated", desc, sums, sum_sq, guides, samples_done, n, params,
+        return self._denoise(True, desc, sums, sum_sq, guides, samples_done, n, params,
                              dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var), stream)
 
     def denoise_accumulated_to_host(self, desc, sums, sum_sq, guides, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False, want_linear=True,
                                     want_var=False):
         """dsrt_denoise_accumulated_to_host: the same from numpy arrays (uint64 sums (H, W, 3), uint32 counts (H, W), float32 guides) into numpy arrays."""
-        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var))
+        return self._denoise(False, desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var))
 
     def denoise_accumulated_coverage(self, desc, sums, sum_sq, guides, alpha, alpha_min=None, samples_done=None, n=None, params=None, want_rgb8=True, want_f32=False,
                                      want_linear=True, want_var=False, stream=None):
         """dsrt_denoise_accumulated_coverage: denoise_accumulated with COVERAGE DEMODULATION -- `alpha` a float32 device tensor of width*height elements (the alpha of a
         DIAGONAL render_coverage; None = the plain denoiser), `guides` usually that pass's rep channels.  alpha_min: default coverage_alpha_min()."""
         alpha_min = coverage_alpha_min() if alpha_min is None else alpha_min
-        return self._denoise("denoise_accumulated_coverage", desc, sums, sum_sq, guides, samples_done, n, params,
+        return self._denoise(True, desc, sums, sum_sq, guides, samples_done, n, params,
                              dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var), stream, coverage=(alpha, alpha_min))
 
     def denoise_accumulated_coverage_to_host(self, desc, sums, sum_sq, guides, alpha, alpha_min=None, samples_done=None, n=None, params=None, want_rgb8=True,
                                              want_f32=False, want_linear=True, want_var=False):
         """dsrt_denoise_accumulated_coverage_to_host: the same from numpy arrays into numpy arrays."""
         alpha_min = coverage_alpha_min() if alpha_min is None else alpha_min
-        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var),
-                                     coverage=(alpha, alpha_min))
+        return self._denoise(False, desc, sums, sum_sq, guides, samples_done, n, params, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var),
+                             coverage=(alpha, alpha_min))
 
     def render_denoised_coverage_to_host(self, desc, cov_desc=None, alpha_min=None, params=None, want_f32=False, want_linear=True, want_var=False, want_alpha=False):
         """dsrt_render_denoised_coverage_to_host: desc.spp samples, a DIAGONAL coverage pass and the coverage-aware filter: (rgb8, f32, linear, var, alpha, DsrtStats)."""
@@ -958,7 +930,7 @@ class Context:
         (the caller ping-pongs two); prev_camera: the GPUCamera history_prev was written under -- both None for the first frame of a sequence.  temporal: a
         DsrtTemporal (temporal_defaults()).  Returns (rgb8, f32, linear, var, prev_xy, weight) device tensors -- prev_xy (height, width, 2), weight (height, width) --
         None where not asked for."""
-        return self._denoise("denoise_temporal", desc, sums, sum_sq, guides, samples_done, n, params,
+        return self._denoise(True, desc, sums, sum_sq, guides, samples_done, n, params,
                              dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight), stream,
                              temporal=(prev_camera, history_prev, history_next, temporal))
 
@@ -966,9 +938,9 @@ class Context:
                                  want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=True, want_weight=True):
         """dsrt_denoise_temporal_to_host: the same from numpy arrays into numpy arrays.  history_prev: float32 (H, W, 16) or None.  Returns
         (rgb8, f32, linear, var, prev_xy, weight, history_next) -- history_next (H, W, 16), 64-byte aligned."""
-        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
-                                     dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight),
-                                     temporal=(prev_camera, history_prev, temporal))
+        return self._denoise(False, desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight),
+                             temporal=(prev_camera, history_prev, None, temporal))
 
     def denoise_temporal_bodies(self, desc, sums, sum_sq, guides, motion, history_next, prev_camera=None, history_prev=None, samples_done=None, n=None, temporal=None,
                                 params=None, want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_prev_xy=False, want_weight=False,
@@ -976,7 +948,7 @@ class Context:
         """dsrt_denoise_temporal_bodies: denoise_temporal with the motion stage (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES).  motion = (first_tri, num_tris,
         poses_prev, poses_cur, prim_id): the bodies' triangle ranges, the poses of the frame history_prev was written under and of this one ((bodies, 12) each), and
         the current G-buffer's prim_id (int32 device tensor).  Returns denoise_temporal's tuple and prev_position (height, width, 3) after it."""
-        return self._denoise("denoise_temporal_bodies", desc, sums, sum_sq, guides, samples_done, n, params,
+        return self._denoise(True, desc, sums, sum_sq, guides, samples_done, n, params,
                              dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
                                   prev_position=want_prev_position), stream, temporal=(prev_camera, history_prev, history_next, temporal), motion=motion)
 
@@ -985,9 +957,9 @@ class Context:
                                         want_prev_position=True):
         """dsrt_denoise_temporal_bodies_to_host: the same from numpy arrays into numpy arrays (prim_id int32 (H, W)).  Returns
         (rgb8, f32, linear, var, prev_xy, weight, prev_position, history_next)."""
-        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
-                                     dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
-                                          prev_position=want_prev_position), temporal=(prev_camera, history_prev, temporal), motion=motion)
+        return self._denoise(False, desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
+                                  prev_position=want_prev_position), temporal=(prev_camera, history_prev, None, temporal), motion=motion)
 
     def set_temporal_bodies(self, on=True):
         """dsrt_ctx_set_temporal_bodies: render_denoised_temporal_to_host follows the resident scene's bodies -- a pose update no longer ends the sequence; the
@@ -1005,7 +977,7 @@ class Context:
         """dsrt_denoise_temporal_shaded: denoise_temporal_bodies with the sun state (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING).  flags: the current
         G-buffer's flags channel (uint8 device tensor); motion as denoise_temporal_bodies', or None for a static scene (then no prev_position); edge_guard 0 or 1.
         Returns denoise_temporal_bodies' tuple and status (height, width) uint8 after it."""
-        return self._denoise("denoise_temporal_shaded", desc, sums, sum_sq, guides, samples_done, n, params,
+        return self._denoise(True, desc, sums, sum_sq, guides, samples_done, n, params,
                              dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
                                   prev_position=want_prev_position, status=want_status), stream, temporal=(prev_camera, history_prev, history_next, temporal),
                              motion=motion, shading=(flags, edge_guard))
@@ -1016,10 +988,10 @@ class Context:
         """dsrt_denoise_temporal_shaded_to_host: the same from numpy arrays into numpy arrays (flags uint8 (H, W)).  Returns
         (rgb8, f32, linear, var, prev_xy, weight, prev_position, status, history_next); prev_position is asked for by default where there is a motion."""
         want_prev_position = motion is not None if want_prev_position is None else want_prev_position
-        return self._denoise_to_host(desc, sums, sum_sq, guides, samples_done, n, params,
-                                     dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
-                                          prev_position=want_prev_position, status=want_status), temporal=(prev_camera, history_prev, temporal), motion=motion,
-                                     shading=(flags, edge_guard))
+        return self._denoise(False, desc, sums, sum_sq, guides, samples_done, n, params,
+                             dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, prev_xy=want_prev_xy, weight=want_weight,
+                                  prev_position=want_prev_position, status=want_status), temporal=(prev_camera, history_prev, None, temporal), motion=motion,
+                             shading=(flags, edge_guard))
 
     def set_temporal_shading(self, mode=2):
         """dsrt_ctx_set_temporal_shading: render_denoised_temporal_to_host keeps the sun state in its history -- 0 off (the default), 1 the tap test only, 2 with the
@@ -1236,11 +1208,15 @@ class Accumulator:
             raise ValueError("this accumulator has no per-pixel counts (counts=True, or a masked render)")
         return self.ctx.resolve_accumulated_counts(self.desc, self.sum, self.n, self.sum_sq if want_var else None, want_rgb8, want_f32, want_var, stream)
 
+    def _empty_guides(self):
+        """Uninitialised guide tensors of this frame: {"normal", "position", "albedo", "range"}, float32, (H, W, 3) or (H, W)."""
+        H, W = self.desc.height, self.desc.width
+        return {k: _torch.empty((H, W, 3) if capi.GBUFFER_CHANNELS[k][1] == 3 else (H, W), dtype=_torch.float32, device=self.sum.device) for k in DENOISE_GUIDES}
+
     def guides(self, ctx=None, stream=None):
         """The denoiser's guides of the context's current camera: {"normal", "position", "albedo", "range"} float32 device tensors (Context.render_gbuffer)."""
         ctx = ctx or self.ctx
-        H, W, dev = self.desc.height, self.desc.width, self.sum.device
-        g = {k: _torch.empty((H, W, 3) if capi.GBUFFER_CHANNELS[k][1] == 3 else (H, W), dtype=_torch.float32, device=dev) for k in DENOISE_GUIDES}
+        g = self._empty_guides()
         ctx.render_gbuffer(self.desc, {k: x.data_ptr() for k, x in g.items()}, stream=ctx._raw_stream(stream))
         return g
 
@@ -1248,9 +1224,8 @@ class Accumulator:
         """(alpha, guides) of a coverage pass over the context's current camera (Context.render_coverage; default DIAGONAL 64): alpha a float32 device tensor
         (H, W), guides the representative's {"normal", "position", "albedo", "range"} -- what denoise(alpha=..., guides=...) takes."""
         ctx = ctx or self.ctx
-        H, W, dev = self.desc.height, self.desc.width, self.sum.device
-        g = {k: _torch.empty((H, W, 3) if capi.GBUFFER_CHANNELS[k][1] == 3 else (H, W), dtype=_torch.float32, device=dev) for k in DENOISE_GUIDES}
-        alpha = _torch.empty((H, W), dtype=_torch.float32, device=dev)
+        g = self._empty_guides()
+        alpha = _torch.empty((self.desc.height, self.desc.width), dtype=_torch.float32, device=self.sum.device)
         ctx.render_coverage(self.desc, cov_desc, {"alpha": alpha.data_ptr()}, {k: x.data_ptr() for k, x in g.items()}, stream=ctx._raw_stream(stream))
         return alpha, g
 

@@ -129,21 +129,19 @@ int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, c
             for (int k = 0; k < 7; ++k) { a.cam[3 * k] = v[k].x; a.cam[3 * k + 1] = v[k].y; a.cam[3 * k + 2] = v[k].z; }
         }
         a.alpha_min = t->tp->alpha_min; a.normal_cos_min = t->tp->normal_cos_min; a.plane_tol = t->tp->plane_tol; a.min_support = t->tp->min_support;
-        if (t->bodies || t->shaded) {
-            BodyMotionArgs mo;                                                        // (all zero without a motion: no prim_id, no body moved)
-            std::memset(&mo, 0, sizeof mo);
-            if (t->bodies) {
-                BodyMotionTable tab;                                                  // (the motion's host arrays are read here, before the call returns)
-                pack_body_motion(*t->motion, tab);
-                mo.prim_id = t->motion->prim_id; mo.prev_position = t->prev_position; mo.moved = tab.moved;
-                static_assert(sizeof mo.first == sizeof tab.first && sizeof mo.count == sizeof tab.count && sizeof mo.poses == sizeof tab.poses, "BodyMotionArgs carries BodyMotionTable");
-                std::memcpy(mo.first, tab.first, sizeof mo.first); std::memcpy(mo.count, tab.count, sizeof mo.count); std::memcpy(mo.poses, tab.poses, sizeof mo.poses);
-            }
-            if (t->shaded) HIP_TRY(launch_temporal_shaded(a, mo, ShadingArgs{t->shading->flags, t->status, t->shading->edge_guard}, stream));
-            else HIP_TRY(launch_temporal_bodies(a, mo, stream));
-        } else {
-            HIP_TRY(launch_temporal(a, stream));
+        BodyMotionArgs mo;                                                            // (all zero without a motion: no prim_id, no body moved)
+        std::memset(&mo, 0, sizeof mo);
+        if (t->bodies) {
+            BodyMotionTable tab;                                                      // (the motion's host arrays are read here, before the call returns)
+            pack_body_motion(*t->motion, tab);
+            mo.prim_id = t->motion->prim_id; mo.prev_position = t->prev_position; mo.moved = tab.moved;
+            static_assert(sizeof mo.first == sizeof tab.first && sizeof mo.count == sizeof tab.count && sizeof mo.poses == sizeof tab.poses, "BodyMotionArgs carries BodyMotionTable");
+            std::memcpy(mo.first, tab.first, sizeof mo.first); std::memcpy(mo.count, tab.count, sizeof mo.count); std::memcpy(mo.poses, tab.poses, sizeof mo.poses);
         }
+        ShadingArgs sh{};
+        if (t->shaded) sh = ShadingArgs{t->shading->flags, t->status, t->shading->edge_guard};
+        // (the stage that follows shading takes the motion stage's argument with or without a motion)
+        HIP_TRY(launch_temporal(a, t->bodies || t->shaded ? &mo : nullptr, t->shaded ? &sh : nullptr, stream));
     }
     for (int i = 0; i < dn->iterations; ++i)
         HIP_TRY(launch_denoise_atrous(b, i & 1, desc->width, desc->height, 1 << i, dn->normal_power_log2, dn->sigma_l, dn->sigma_z, dn->sigma_a, stream));

@@ -84,7 +84,6 @@ struct TemporalArgs {
     float cam[21];
     float alpha_min, normal_cos_min, plane_tol, min_support;
 };
-hipError_t launch_temporal(const TemporalArgs& a, hipStream_t stream);
 // The same with the motion stage (include/dsrt.h, TEMPORAL ACCUMULATION WITH BODIES), a second kernel argument beside TemporalArgs, which stays as it is: the
 // G-buffer's prim_id, the optional X' output, per body >= 1 its triangle range [first, first + count) (zero for a body not given: an empty range), bit b of `moved`
 // set where body b's poses differ, and per body six float4 -- the cur pose's three rows {r0 r1 r2 t}, then the prev pose's (host/body_motion.cpp, BodyMotionTable).
@@ -95,12 +94,13 @@ struct BodyMotionArgs {
     uint32_t moved;
     float4 poses[kMaxBodies * 6];
 };
-hipError_t launch_temporal_bodies(const TemporalArgs& a, const BodyMotionArgs& mo, hipStream_t stream);
 // ... and with the sun state (include/dsrt.h, TEMPORAL ACCUMULATION THAT FOLLOWS SHADING), a third kernel argument; the other two stay as they are.  flags: the
 // current G-buffer's u8 channel; status: the optional byte per pixel; edge_guard 0 or 1.  mo.prim_id null: a static scene (every pixel body 0; moved = 0, and
 // prev_position null).
 struct ShadingArgs { const uint8_t* flags; uint8_t* status; int edge_guard; };
-hipError_t launch_temporal_shaded(const TemporalArgs& a, const BodyMotionArgs& mo, const ShadingArgs& sh, hipStream_t stream);
+// One launcher picks the kernel: null mo and null sh the static one (dsrt_temporal_kernel), mo alone the one with the motion stage, sh the one with the sun state
+// as well (mo is required then: all zero for a static scene).
+hipError_t launch_temporal(const TemporalArgs& a, const BodyMotionArgs* mo, const ShadingArgs* sh, hipStream_t stream);
 
 // upscale_kernel.hip (include/dsrt.h, UPSCALER).  The LOW-resolution frame packed for the taps, one 16-byte record per low-resolution pixel each: {c.rgb, range},
 // {v.rgb, flags as a bit pattern}, {N, 0}, {X, 0}, {A, 0}.  pack fills them (var and flags may be null: zeros); the upscale launch reads them and the OUTPUT
