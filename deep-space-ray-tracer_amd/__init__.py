@@ -319,6 +319,11 @@ def temporal_shading(flags_ptr, edge_guard=1):
 UPSCALE_GUIDES = DENOISE_GUIDES + ("flags",)                         # DsrtUpscaleGuides' channels; "flags" (uint8) is the optional one
 
 
+def upscale_coverage_alpha_min():
+    """dsrt_upscale_coverage_alpha_min: the default alpha_min of the coverage-aware upscaler and of the denoiser in front of it."""
+    return float(lib.dsrt_upscale_coverage_alpha_min())
+
+
 def upscale_defaults(**changes):
     """dsrt_upscale_defaults: the DsrtUpscale the library fills (normal_power_log2, sigma_z, sigma_a, use_sun), with `changes` applied."""
     return _defaults(capi.DsrtUpscale, lib.dsrt_upscale_defaults, changes)
@@ -418,7 +423,8 @@ def _array_ptr(a):
 
 
 _OUTPUTS = {"rgb8": (np.uint8, (3,)), "f32": (np.float32, (3,)), "linear": (np.float32, (3,)), "var": (np.float32, (3,)), "prev_xy": (np.float32, (2,)),
-            "weight": (np.float32, ()), "support": (np.float32, ()), "prev_position": (np.float32, (3,)), "status": (np.uint8, ())}
+            "weight": (np.float32, ()), "support": (np.float32, ()), "prev_position": (np.float32, (3,)), "status": (np.uint8, ()),
+            "level": (np.uint8, ())}
 
 
 def _outputs(desc, wants, device=None):
@@ -1074,6 +1080,67 @@ class Context:
         _check(lib.dsrt_render_upscaled_to_host(self._h, C.byref(lo_desc), hi.width, hi.height, C.byref(denoise) if denoise is not None else None, C.byref(params),
                                                 *map(_array_ptr, out), _array_ptr(lo_rgb8), C.byref(st)), "dsrt_render_upscaled_to_host")
         return (*out, lo_rgb8, st)
+
+    # ---- the upscaler with coverage (include/dsrt.h, COVERAGE-AWARE UPSCALER): the same, with the alphas of a DIAGONAL coverage pass at each raster ----
+    def upscale_guided_coverage(self, desc, lo_width, lo_height, lo_linear, lo_guides, hi_guides, lo_alpha, hi_alpha, alpha_min=None, lo_var=None, params=None,
+                                want_rgb8=True, want_f32=False, want_linear=True, want_var=False, want_support=False, want_level=False, stream=None):
+        """dsrt_upscale_guided_coverage (torch device tensors) or dsrt_upscale_guided_coverage_to_host (numpy arrays, chosen by lo_linear's type): upscale_guided with
+        `lo_alpha` (float32, lo_height*lo_width) and `hi_alpha` (float32, height*width), the alphas of a DIAGONAL render_coverage at each raster (both None = the plain
+        upscaler); lo_guides / hi_guides usually those passes' rep channels.  alpha_min: default upscale_coverage_alpha_min().
+        Returns (rgb8, f32, linear, var, support, level) of shape (height, width[, 3]), None where not asked for; level is uint8, 0 .. 3."""
+        on_device = _torch is not None and isinstance(lo_linear, _torch.Tensor)
+        w, h = int(lo_width), int(lo_height)
+        n = w * h * 3
+        alpha_min = upscale_coverage_alpha_min() if alpha_min is None else alpha_min
+        if on_device:
+            numel = (n, f"lo_width*lo_height*3 = {n}")
+            lin = self._device_tensor(lo_linear, _torch.float32, numel, "lo_linear")
+            var = self._device_tensor(lo_var, _torch.float32, numel, "lo_var", required=False)
+            a_lo = self._device_tensor(lo_alpha, _torch.float32, (w * h, f"lo_width*lo_height = {w * h}"), "lo_alpha", required=False)
+            a_hi = self._device_tensor(hi_alpha, _torch.float32, (desc.width * desc.height, f"width*height = {desc.width * desc.height}"), "hi_alpha", required=False)
+        else:
+            lin = np.ascontiguousarray(lo_linear, np.float32).reshape(n)
+            var = np.ascontiguousarray(lo_var, np.float32).reshape(n) if lo_var is not None else None
+            a_lo = np.ascontiguousarray(lo_alpha, np.float32).reshape(w * h) if lo_alpha is not None else None
+            a_hi = np.ascontiguousarray(hi_alpha, np.float32).reshape(desc.width * desc.height) if hi_alpha is not None else None
+        lo, keep_lo = self._upscale_guides(lo_guides, w, h, "low-resolution", on_device)
+        hi, keep_hi = self._upscale_guides(hi_guides, desc.width, desc.height, "output", on_device)
+        params = upscale_defaults() if params is None else params
+        out = _outputs(desc, dict(rgb8=want_rgb8, f32=want_f32, linear=want_linear, var=want_var, support=want_support, level=want_level), lin.device if on_device else None)
+        ptr = _tensor_ptr if on_device else _array_ptr
+        head = (self._h, C.byref(desc), w, h, ptr(lin), ptr(var), C.byref(lo), C.byref(hi), ptr(a_lo), ptr(a_hi), C.c_float(alpha_min), C.byref(params), *map(ptr, out))
+        if on_device:
+            _check(lib.dsrt_upscale_guided_coverage(*head, C.c_void_p(self._raw_stream(stream))), "dsrt_upscale_guided_coverage")
+        else:
+            _check(lib.dsrt_upscale_guided_coverage_to_host(*head), "dsrt_upscale_guided_coverage_to_host")
+        del keep_lo, keep_hi
+        return out
+
+    def upscale_guided_coverage_to_host(self, desc, lo_width, lo_height, lo_linear, lo_guides, hi_guides, lo_alpha, hi_alpha, **kw):
+        """dsrt_upscale_guided_coverage_to_host: upscale_guided_coverage from numpy arrays into numpy arrays (device tensors are copied to the host first)."""
+        host = lambda x: x.cpu().numpy() if _torch is not None and isinstance(x, _torch.Tensor) else x           # noqa: E731
+        kw = {k: host(x) if k == "lo_var" else x for k, x in kw.items()}
+        return self.upscale_guided_coverage(desc, lo_width, lo_height, np.asarray(host(lo_linear)), {k: host(x) for k, x in lo_guides.items()},
+                                            {k: host(x) for k, x in hi_guides.items()}, host(lo_alpha), host(hi_alpha), **kw)
+
+    def render_upscaled_coverage_to_host(self, lo_desc, out_width, out_height, cov_lo=None, cov_hi=None, alpha_min=None, denoise=None, params=None, want_f32=False,
+                                         want_linear=True, want_var=False, want_lo_rgb8=False, want_alpha=False):
+        """dsrt_render_upscaled_coverage_to_host: lo_desc.spp samples at lo_desc's size, a DIAGONAL coverage pass there (cov_lo: a coverage_desc(), None = the
+        default), the coverage-aware denoiser (`denoise`: a DsrtDenoise, None = the plain mean), a DIAGONAL coverage pass at the output size (cov_hi) and the
+        coverage-aware upscaler, into numpy arrays of out_height x out_width: (rgb8, f32, linear, var, lo_rgb8, alpha_hi, DsrtStats)."""
+        params = upscale_defaults() if params is None else params
+        alpha_min = upscale_coverage_alpha_min() if alpha_min is None else alpha_min
+        hi = DsrtRenderDesc.from_buffer_copy(lo_desc)
+        hi.width, hi.height = int(out_width), int(out_height)
+        out = _outputs(hi, dict(rgb8=True, f32=want_f32, linear=want_linear, var=want_var))
+        lo_rgb8 = np.zeros((lo_desc.height, lo_desc.width, 3), np.uint8) if want_lo_rgb8 else None
+        alpha = np.zeros((hi.height, hi.width), np.float32) if want_alpha else None
+        st = DsrtStats()
+        ref = lambda x: C.byref(x) if x is not None else None                        # noqa: E731
+        _check(lib.dsrt_render_upscaled_coverage_to_host(self._h, C.byref(lo_desc), hi.width, hi.height, ref(cov_lo), ref(cov_hi), C.c_float(alpha_min), ref(denoise),
+                                                         C.byref(params), *map(_array_ptr, out), _array_ptr(lo_rgb8), _array_ptr(alpha), C.byref(st)),
+               "dsrt_render_upscaled_coverage_to_host")
+        return (*out, lo_rgb8, alpha, st)
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

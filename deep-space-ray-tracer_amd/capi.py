@@ -207,6 +207,7 @@ EXPORTS = [
     "dsrt_denoise_temporal_shaded", "dsrt_denoise_temporal_shaded_to_host", "dsrt_ctx_set_temporal_shading", "dsrt_ctx_temporal_shading",
     "dsrt_coverage_defaults", "dsrt_render_coverage", "dsrt_render_coverage_to_host", "dsrt_denoise_coverage_alpha_min", "dsrt_denoise_accumulated_coverage",
     "dsrt_denoise_accumulated_coverage_to_host", "dsrt_render_denoised_coverage_to_host",
+    "dsrt_upscale_coverage_alpha_min", "dsrt_upscale_guided_coverage", "dsrt_upscale_guided_coverage_to_host", "dsrt_render_upscaled_coverage_to_host",
     "dsrt_selftest_read_schedule", "dsrt_selftest_tile_order", "dsrt_selftest_tile_reorder", "dsrt_selftest_batch_table",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
@@ -343,6 +344,13 @@ def load():
     sig("dsrt_upscale_guided", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp, vp])
     sig("dsrt_upscale_guided_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), P(DsrtUpscale), vp, vp, vp, vp, vp])
     sig("dsrt_render_upscaled_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, P(DsrtDenoise), P(DsrtUpscale), vp, vp, vp, vp, vp, P(DsrtStats)])
+    sig("dsrt_upscale_coverage_alpha_min", C.c_float, [])
+    sig("dsrt_upscale_guided_coverage", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), vp, vp, C.c_float, P(DsrtUpscale),
+                                                 vp, vp, vp, vp, vp, vp, vp])
+    sig("dsrt_upscale_guided_coverage_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, vp, vp, P(DsrtUpscaleGuides), P(DsrtUpscaleGuides), vp, vp, C.c_float,
+                                                         P(DsrtUpscale), vp, vp, vp, vp, vp, vp])
+    sig("dsrt_render_upscaled_coverage_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, P(DsrtCoverageDesc), P(DsrtCoverageDesc), C.c_float, P(DsrtDenoise),
+                                                          P(DsrtUpscale), vp, vp, vp, vp, vp, vp, P(DsrtStats)])
     sig("dsrt_host_scene_begin_body", C.c_int, [vp])
     sig("dsrt_host_scene_body_count", C.c_int, [vp])
     sig("dsrt_host_scene_body_range", C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int)])

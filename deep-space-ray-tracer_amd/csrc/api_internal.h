@@ -137,7 +137,7 @@ struct DsrtContext {
     dsrt::DevBuf<uint32_t> gb_status;     // dsrt_render_gbuffer's status word
     dsrt::DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
     dsrt::DevBuf<float4> dn_cl[2], dn_vl[2], dn_nr, dn_xf, dn_al;   // dsrt_denoise_accumulated: 7 records of 16 bytes per pixel (launchers.h, DenoiseBuffers)
-    dsrt::DevBuf<float4> up_rec[5];       // dsrt_upscale_guided: 5 records of 16 bytes per LOW-resolution pixel (launchers.h, UpscaleRecords)
+    dsrt::DevBuf<float4> up_rec[5];       // dsrt_upscale_guided[_coverage]: 5 records of 16 bytes per LOW-resolution pixel (launchers.h, UpscaleRecords)
     // dsrt_render_denoised_temporal_to_host: the sequence the context keeps -- two histories (tp_hist[tp_cur] holds the last frame's), that frame's camera and size
     dsrt::DevBuf<float4> tp_hist[2];
     GPUCamera tp_camera{};
@@ -244,6 +244,7 @@ struct FrameBuffers {
     const void *shade_flags, *status;                                  // ... and its sun state's (dsrt_denoise_temporal_shaded): the current G-buffer's flags, the status byte
     const void *lo_linear, *lo_var, *lo_normal, *lo_position, *lo_albedo, *lo_range, *lo_flags, *lo_rgb8;      // the upscaler's, low resolution ...
     const void *flags, *support;                                       // ... and output resolution
+    const void *lo_alpha, *level;                                      // dsrt_upscale_guided_coverage's: the low-resolution alpha (the output raster's is `alpha` above), the level byte
 };
 struct FrameBufferKind { size_t bytes; Dir dir; size_t align; bool lo = false; };
 constexpr size_t kHistoryBytes = 64;                                   // per pixel: include/dsrt.h, TEMPORAL ACCUMULATION
@@ -256,7 +257,8 @@ inline constexpr FrameBufferKind kFrameBuffers[] = {
     {4, Dir::In, 4}, {12, Dir::Out, 4},
     {1, Dir::In, 1}, {1, Dir::Out, 1},
     {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {12, Dir::In, 4, true}, {4, Dir::In, 4, true}, {1, Dir::In, 1, true},
-    {3, Dir::Out, 1, true}, {1, Dir::In, 1}, {4, Dir::Out, 4}};
+    {3, Dir::Out, 1, true}, {1, Dir::In, 1}, {4, Dir::Out, 4},
+    {4, Dir::In, 4, true}, {1, Dir::Out, 1}};
 constexpr size_t kFrameBufferCount = sizeof(FrameBuffers) / sizeof(void*);
 static_assert(sizeof kFrameBuffers / sizeof kFrameBuffers[0] == kFrameBufferCount, "kFrameBuffers has one entry per pointer of FrameBuffers");
 

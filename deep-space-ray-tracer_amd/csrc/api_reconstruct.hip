@@ -9,6 +9,7 @@ namespace {
 
 constexpr size_t kFrameTemporal = offsetof(FrameBuffers, history_prev) / sizeof(void*);
 constexpr size_t kFrameUpscale = offsetof(FrameBuffers, lo_linear) / sizeof(void*);
+constexpr float kUpscaleCoverageAlphaMin = 0.125f;                                    // dsrt_upscale_coverage_alpha_min: likewise (the subsection on the upscaler with coverage)
 constexpr float kCoverageAlphaMin = 0.0625f;                                          // dsrt_denoise_coverage_alpha_min: DESIGN.md section 4 says how it was chosen
 
 // The table's entries [from, to) against those before them and among themselves: alignment; then each of their outputs against every input up to `to` (over_input) and
@@ -217,9 +218,14 @@ int check_upscale_params(const char* fn, const DsrtUpscale* up) {
 }
 
 // The buffers of an upscaler call, device or host form alike: the shared rows are the output raster's.
+// The coverage part of an upscaler call (dsrt_upscale_guided_coverage; include/dsrt.h, COVERAGE-AWARE UPSCALER): null for dsrt_upscale_guided.  Both alphas null is
+// the plain upscaler (alpha_min is then only checked).
+struct UpscaleCoverageInput { const float* lo_alpha; const float* hi_alpha; float alpha_min; uint8_t* level; };
+
 FrameBuffers upscale_buffers(const float* lo_linear, const float* lo_var, const DsrtUpscaleGuides& lo, const DsrtUpscaleGuides& hi, const void* rgb8, const void* f32,
-                             const void* linear, const void* var, const void* support) {
+                             const void* linear, const void* var, const void* support, const UpscaleCoverageInput* cv = nullptr) {
     FrameBuffers b{};
+    if (cv) { b.alpha = cv->hi_alpha; b.lo_alpha = cv->lo_alpha; b.level = cv->level; }
     b.normal = hi.normal; b.position = hi.position; b.albedo = hi.albedo; b.range = hi.range; b.flags = hi.flags;
     b.rgb8 = rgb8; b.f32 = f32; b.linear = linear; b.var = var; b.support = support;
     b.lo_linear = lo_linear; b.lo_var = lo_var;
@@ -239,25 +245,31 @@ int check_upscale_sizes(const char* fn, int lo_width, int lo_height, int width, 
 // Everything dsrt_upscale_guided refuses, before anything is launched or written; the same for the host form's host pointers.
 int check_upscale(const char* fn, const DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* lo_linear, const float* lo_var,
                   const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const DsrtUpscale* up, const uint8_t* rgb8, const float* f32, const float* linear,
-                  const float* var, const float* support) {
+                  const float* var, const float* support, const UpscaleCoverageInput* cv = nullptr) {
     if (!ctx || !desc || !lo_linear || !lo || !hi || !up) return accum_fail(fn, "null argument");
     for (const DsrtUpscaleGuides* g : {lo, hi})
         if (!g->normal || !g->position || !g->albedo || !g->range) return accum_fail(fn, "a guide channel is NULL (normal, position, albedo and range are required; flags is the optional one)");
     if (int rc = check_frame_desc(fn, desc, false, true)) return rc;
     if (int rc = check_upscale_sizes(fn, lo_width, lo_height, desc->width, desc->height)) return rc;
     if (int rc = check_upscale_params(fn, up)) return rc;
-    if (!rgb8 && !f32 && !linear && !var && !support) return accum_fail(fn, "no output");
+    if (cv) {
+        if ((cv->lo_alpha != nullptr) != (cv->hi_alpha != nullptr)) return accum_fail(fn, "the two alphas go together: both NULL (the plain upscaler) or both given");
+        if (!(cv->alpha_min > 0.0f && cv->alpha_min <= 1.0f)) return accum_fail(fn, "alpha_min must be > 0 and <= 1");
+        if (cv->level && !cv->lo_alpha) return accum_fail(fn, "the level output needs the alphas");
+    }
+    if (!rgb8 && !f32 && !linear && !var && !support && !(cv && cv->level)) return accum_fail(fn, "no output");
     if (var && !lo_var) return accum_fail(fn, "the variance output needs the low-resolution variance (d_lo_var)");
     Staged s[kFrameBufferCount];
-    frame_table(upscale_buffers(lo_linear, lo_var, *lo, *hi, rgb8, f32, linear, var, support), (size_t)desc->width * desc->height, s, (size_t)lo_width * lo_height);
+    frame_table(upscale_buffers(lo_linear, lo_var, *lo, *hi, rgb8, f32, linear, var, support, cv), (size_t)desc->width * desc->height, s, (size_t)lo_width * lo_height);
     return check_frame_table(fn, s, 0, kFrameBufferCount, "an output range overlaps an input range", "two output ranges overlap", nullptr);
 }
 
 int upscale_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* d_lo_linear, const float* d_lo_var,
                  const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const DsrtUpscale* up, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var,
-                 float* d_support, hipStream_t stream) {
+                 float* d_support, hipStream_t stream, const UpscaleCoverageInput* cv = nullptr) {
     int rc;
-    if ((rc = check_upscale(fn, ctx, desc, lo_width, lo_height, d_lo_linear, d_lo_var, lo, hi, up, d_rgb8, d_f32, d_linear, d_var, d_support))) return rc;
+    if ((rc = check_upscale(fn, ctx, desc, lo_width, lo_height, d_lo_linear, d_lo_var, lo, hi, up, d_rgb8, d_f32, d_linear, d_var, d_support, cv))) return rc;
+    const bool coverage = cv && cv->lo_alpha;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t px_lo = (size_t)lo_width * lo_height;
     // (growing frees the old records: the launch that may still read them has to be over first)
@@ -265,7 +277,8 @@ int upscale_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, i
     for (DevBuf<float4>& r : ctx->up_rec) if ((rc = r.grow(px_lo))) return rc;
     const UpscaleRecords rec{ctx->up_rec[0].p, ctx->up_rec[1].p, ctx->up_rec[2].p, ctx->up_rec[3].p, ctx->up_rec[4].p};
     if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (the denoiser, a G-buffer) comes first
-    HIP_TRY(launch_upscale_pack(d_lo_linear, d_lo_var, lo->normal, lo->position, lo->albedo, lo->range, lo->flags, px_lo, rec, stream));
+    if (coverage) HIP_TRY(launch_upscale_pack_coverage(d_lo_linear, d_lo_var, lo->normal, lo->position, lo->albedo, lo->range, lo->flags, cv->lo_alpha, px_lo, rec, stream));
+    else HIP_TRY(launch_upscale_pack(d_lo_linear, d_lo_var, lo->normal, lo->position, lo->albedo, lo->range, lo->flags, px_lo, rec, stream));
     UpscaleArgs a;
     std::memset(&a, 0, sizeof a);
     a.cr = rec.cr; a.vf = rec.vf; a.nn = rec.nn; a.xx = rec.xx; a.aa = rec.aa;
@@ -274,7 +287,8 @@ int upscale_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, i
     a.w = lo_width; a.h = lo_height; a.W = desc->width; a.H = desc->height;
     a.normal_power_log2 = up->normal_power_log2; a.use_sun = up->use_sun != 0; a.lo_has_flags = lo->flags != nullptr;
     a.sigma_z = up->sigma_z; a.sigma_a = up->sigma_a; a.inv_gamma = inv_gamma_of(*desc);
-    HIP_TRY(launch_upscale(a, desc->math_mode == 1, stream));
+    if (coverage) HIP_TRY(launch_upscale_coverage(UpscaleCoverageArgs{a, cv->hi_alpha, cv->level, cv->alpha_min}, desc->math_mode == 1, stream));
+    else HIP_TRY(launch_upscale(a, desc->math_mode == 1, stream));
     return launch_finish(ctx, stream, nullptr);                                      // the records are the context's: its next launch on any stream comes behind
 }
 
@@ -548,6 +562,94 @@ int dsrt_render_upscaled_to_host(DsrtContext* ctx, const DsrtRenderDesc* lo_desc
         return dsrt_upscale_guided(ctx, &hi_desc, lo_desc->width, lo_desc->height, lo_linear.p, lo_var.p, &lo, &hi, up, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
                                    (float*)m.var, nullptr, nullptr);
     }, px_lo);
+    });
+}
+
+// ---- The upscaler with coverage (include/dsrt.h, COVERAGE-AWARE UPSCALER): the same calls with the two alphas, alpha_min and the level output ----
+float dsrt_upscale_coverage_alpha_min(void) { return kUpscaleCoverageAlphaMin; }
+
+int dsrt_upscale_guided_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* d_lo_linear, const float* d_lo_var,
+                                 const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const float* d_lo_alpha, const float* d_hi_alpha, float alpha_min,
+                                 const DsrtUpscale* up, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, float* d_support, uint8_t* d_level, void* stream_v) {
+    return dsrt::guarded("dsrt_upscale_guided_coverage", [&]() -> int {
+    const UpscaleCoverageInput cv{d_lo_alpha, d_hi_alpha, alpha_min, d_level};
+    return upscale_impl("dsrt_upscale_guided_coverage", ctx, desc, lo_width, lo_height, d_lo_linear, d_lo_var, lo, hi, up, d_rgb8, d_f32, d_linear, d_var, d_support,
+                        (hipStream_t)stream_v, &cv);
+    });
+}
+
+int dsrt_upscale_guided_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* h_lo_linear, const float* h_lo_var,
+                                         const DsrtUpscaleGuides* h_lo, const DsrtUpscaleGuides* h_hi, const float* h_lo_alpha, const float* h_hi_alpha, float alpha_min,
+                                         const DsrtUpscale* up, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_support, uint8_t* h_level) {
+    return dsrt::guarded("dsrt_upscale_guided_coverage_to_host", [&]() -> int {
+    const char* fn = "dsrt_upscale_guided_coverage_to_host";
+    const UpscaleCoverageInput hcv{h_lo_alpha, h_hi_alpha, alpha_min, h_level};
+    if (int rc = check_upscale(fn, ctx, desc, lo_width, lo_height, h_lo_linear, h_lo_var, h_lo, h_hi, up, h_rgb8, h_f32, h_linear, h_var, h_support, &hcv)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const FrameBuffers h = upscale_buffers(h_lo_linear, h_lo_var, *h_lo, *h_hi, h_rgb8, h_f32, h_linear, h_var, h_support, &hcv);
+    return staged_frame_call(h, (size_t)desc->width * desc->height, true, [&](const FrameBuffers& m) {
+        const DsrtUpscaleGuides lo = lo_guides_of(m), hi = hi_guides_of(m);
+        const UpscaleCoverageInput cv{(const float*)m.lo_alpha, (const float*)m.alpha, alpha_min, (uint8_t*)m.level};
+        return upscale_impl(fn, ctx, desc, lo_width, lo_height, (const float*)m.lo_linear, (const float*)m.lo_var, &lo, &hi, up, (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear,
+                            (float*)m.var, (float*)m.support, nullptr, &cv);
+    }, (size_t)lo_width * lo_height);
+    });
+}
+
+// The convenience form with coverage: the five calls of include/dsrt.h; both rasters' alphas and representatives' guides are on the device for the call.
+int dsrt_render_upscaled_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* lo_desc, int out_width, int out_height, const DsrtCoverageDesc* cov_lo,
+                                          const DsrtCoverageDesc* cov_hi, float alpha_min, const DsrtDenoise* denoise, const DsrtUpscale* up, uint8_t* h_rgb8, float* h_f32,
+                                          float* h_linear, float* h_var, uint8_t* h_lo_rgb8, float* h_alpha_hi, DsrtStats* stats) {
+    return dsrt::guarded("dsrt_render_upscaled_coverage_to_host", [&]() -> int {
+    const char* fn = "dsrt_render_upscaled_coverage_to_host";
+    DsrtDenoise dn;
+    dsrt_denoise_defaults(&dn);
+    if (denoise) dn = *denoise; else dn.iterations = 0;
+    int spp, rc;
+    if (!ctx || !lo_desc) return accum_fail(fn, "null argument");
+    DsrtRenderDesc hi_desc = *lo_desc;
+    hi_desc.width = out_width; hi_desc.height = out_height;
+    if ((rc = check_frame_desc(fn, lo_desc, false, true)) || (rc = check_frame_desc(fn, &hi_desc, false, true))) return rc;
+    if ((rc = check_upscale_sizes(fn, lo_desc->width, lo_desc->height, out_width, out_height)) || (rc = check_upscale_params(fn, up))) return rc;
+    DsrtCoverageDesc cd[2];
+    const DsrtCoverageDesc* given[2] = {cov_lo, cov_hi};
+    for (int k = 0; k < 2; ++k) {
+        dsrt_coverage_defaults(&cd[k]);
+        if (given[k]) cd[k] = *given[k];
+        if (cd[k].pattern != DSRT_COVERAGE_DIAGONAL || cd[k].samples < 1 || cd[k].samples > 64) return accum_fail(fn, "the coverage passes must be DSRT_COVERAGE_DIAGONAL with samples in 1..64");
+    }
+    if (!(alpha_min > 0.0f && alpha_min <= 1.0f)) return accum_fail(fn, "alpha_min must be > 0 and <= 1");
+    if ((uintptr_t)h_alpha_hi & 3u) return accum_fail(fn, "pointer not 4-byte aligned");
+    if ((rc = check_render_denoised(fn, ctx, lo_desc, &dn, false, nullptr, h_rgb8 || h_f32 || h_linear || h_var, &spp))) return rc;      // (the scene is looked for last)
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t px_lo = (size_t)lo_desc->width * (size_t)lo_desc->height, px = (size_t)out_width * (size_t)out_height;
+    FrameScratch f, g;                                                    // f: the low-resolution frame's sums and guides; g: the output raster's guides (its sums are not used)
+    DevBuf<float> lo_linear, lo_var, lo_alpha, hi_alpha;
+    DevBuf<uint8_t> lo_flags, hi_flags;
+    if ((rc = f.init(px_lo, false, true)) || (rc = lo_linear.alloc(px_lo * 3)) || (rc = lo_var.alloc(px_lo * 3)) || (rc = lo_flags.alloc(px_lo)) || (rc = lo_alpha.alloc(px_lo))) return rc;
+    if ((rc = g.normal.alloc(px * 3)) || (rc = g.position.alloc(px * 3)) || (rc = g.albedo.alloc(px * 3)) || (rc = g.range.alloc(px)) || (rc = hi_flags.alloc(px)) ||
+        (rc = hi_alpha.alloc(px))) return rc;
+    f.gb.flags = lo_flags.p;
+    g.gb.normal = g.normal.p; g.gb.position = g.position.p; g.gb.albedo = g.albedo.p; g.gb.range = g.range.p; g.gb.flags = hi_flags.p;
+    DsrtCoverage cv_lo{}, cv_hi{};
+    cv_lo.alpha = lo_alpha.p; cv_lo.rep = f.gb;
+    cv_hi.alpha = hi_alpha.p; cv_hi.rep = g.gb;
+    const DsrtUpscaleGuides lo{f.normal.p, f.position.p, f.albedo.p, f.range.p, lo_flags.p}, hi{g.normal.p, g.position.p, g.albedo.p, g.range.p, hi_flags.p};
+    FrameBuffers h{};
+    h.rgb8 = h_rgb8; h.f32 = h_f32; h.linear = h_linear; h.var = h_var; h.lo_rgb8 = h_lo_rgb8;
+    DsrtStats local;
+    if ((rc = staged_frame_call(h, px, true, [&](const FrameBuffers& m) -> int {
+        int r;
+        if ((r = dsrt_render_accumulate(ctx, lo_desc, 0, spp, 1, &f.acc, nullptr, stats ? stats : &local))) return r;
+        if ((r = dsrt_render_coverage(ctx, lo_desc, &cd[0], nullptr, &cv_lo, nullptr, nullptr))) return r;
+        if ((r = dsrt_denoise_accumulated_coverage(ctx, lo_desc, &f.acc, spp, nullptr, &f.guides, lo_alpha.p, alpha_min, &dn, (uint8_t*)m.lo_rgb8, nullptr, lo_linear.p,
+                                                   lo_var.p, nullptr))) return r;
+        if ((r = dsrt_render_coverage(ctx, &hi_desc, &cd[1], nullptr, &cv_hi, nullptr, nullptr))) return r;
+        return dsrt_upscale_guided_coverage(ctx, &hi_desc, lo_desc->width, lo_desc->height, lo_linear.p, lo_var.p, &lo, &hi, lo_alpha.p, hi_alpha.p, alpha_min, up,
+                                            (uint8_t*)m.rgb8, (float*)m.f32, (float*)m.linear, (float*)m.var, nullptr, nullptr, nullptr);
+    }, px_lo))) return rc;
+    if (h_alpha_hi) HIP_TRY(hipMemcpy(h_alpha_hi, hi_alpha.p, px * sizeof(float), hipMemcpyDeviceToHost));
+    return DSRT_OK;
     });
 }
 

@@ -117,6 +117,13 @@ struct UpscaleArgs {
 hipError_t launch_upscale_pack(const float* linear, const float* var, const float* normal, const float* position, const float* albedo, const float* range,
                                const uint8_t* flags, size_t n_pixels, const UpscaleRecords& r, hipStream_t stream);
 hipError_t launch_upscale(const UpscaleArgs& a, bool device_libm, hipStream_t stream);
+// ... with coverage (include/dsrt.h, COVERAGE-AWARE UPSCALER): `alpha` / hi_alpha one float per low-resolution / output pixel, never null here (a call without them
+// uses the two above: their kernels are the HAS_ALPHA = false instantiations of the same bodies).  pack keeps the low-resolution alpha in the normal record's spare
+// word, {N, alpha}: working memory stays five records.  out_level (optional): one byte per output pixel, the level that produced it.
+struct UpscaleCoverageArgs { UpscaleArgs up; const float* hi_alpha; uint8_t* out_level; float alpha_min; };
+hipError_t launch_upscale_pack_coverage(const float* linear, const float* var, const float* normal, const float* position, const float* albedo, const float* range,
+                                        const uint8_t* flags, const float* alpha, size_t n_pixels, const UpscaleRecords& r, hipStream_t stream);
+hipError_t launch_upscale_coverage(const UpscaleCoverageArgs& a, bool device_libm, hipStream_t stream);
 
 // bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES).  What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
 // dsrt_scene_upload_bodies made resident beside them.  A movable ENTRY is a pair record of tri_pairs that holds triangles of a body >= 1; entries are sorted by body.

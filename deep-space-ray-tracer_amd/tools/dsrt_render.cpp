@@ -47,7 +47,12 @@
 //     part first, stacked top to bottom in one single-channel map of height (bodies + 1) * H -- the share of the sub-samples that hit that body.
 //   * with --denoise: --coverage-aware [ALPHA_MIN] filters the covered part of every pixel (include/dsrt.h, COVERAGE DEMODULATION: a DIAGONAL 64 coverage pass gives
 //     alpha and the guides, dsrt_denoise_accumulated_coverage; ALPHA_MIN in (0, 1], default the library's), so that silhouette pixels and trusses thinner than a
-//     pixel are filtered too.  Does not combine with --temporal or --upscale.
+//     pixel are filtered too.  Does not combine with --temporal.
+//   * rng_mode 1 only: --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N] is the upscaler with coverage (include/dsrt.h, COVERAGE-AWARE UPSCALER:
+//     dsrt_render_upscaled_coverage_to_host): a DIAGONAL N coverage pass at each raster (default 64; a grid: pattern is a usage error) gives the alphas and the
+//     guides (ALPHA_MIN: default the library's for this chain), the low-resolution frame is unmixed before the gather, and trusses thinner than a low-resolution pixel come out at the output resolution.  Writes
+//     <frame>, <frame>_lowres and <frame>_alpha.pfm (the output raster's alpha); --coverage then only chooses N and writes no files of its own.  The three flags
+//     --denoise --upscale --coverage-aware together stay a usage error: the low-resolution frame of this mode is the plain mean.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -84,7 +89,8 @@ int main(int argc, char** argv) {
     int denoise_iterations = -1;                                    // -1: the library's default
     bool coverage = false, coverage_aware = false;
     DsrtCoverageDesc cov_desc{DSRT_COVERAGE_DIAGONAL, 64};
-    float alpha_min = dsrt_denoise_coverage_alpha_min();
+    float alpha_min = dsrt_denoise_coverage_alpha_min();            // (with --upscale: dsrt_upscale_coverage_alpha_min(), unless a value is given)
+    bool alpha_min_given = false;
     const char* usage_coverage = "dsrt_render: --coverage takes grid:S (S = 1 .. 8) or diag:N (N = 1 .. 64)\n";
     bool upscale = false;
     int upscale_factor = 4;                                         // the reference's scale (src/main.cpp:444)
@@ -137,7 +143,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--coverage-aware") {                         // with --denoise: the filter works on the covered part of every pixel; the value (alpha_min) is optional
             coverage_aware = true;
-            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) alpha_min = (float)std::atof(argv[++i]);
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) { alpha_min = (float)std::atof(argv[++i]); alpha_min_given = true; }
         }
         else if (a == "--temporal") temporal = true;                // with --denoise: reprojected frame history (include/dsrt.h, TEMPORAL ACCUMULATION)
         else if (a == "--flow") flow = true;                        // with --temporal: <frame>_flow.pfm, every pixel's displacement from the previous frame
@@ -154,12 +160,14 @@ int main(int argc, char** argv) {
             upscale = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') upscale_factor = std::atoi(argv[++i]);
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
     if ((int)bodies.size() > DSRT_MAX_BODIES - 1) { std::fprintf(stderr, "dsrt_render: at most %d --body\n", DSRT_MAX_BODIES - 1); return 2; }
     if (!body_poses_file.empty() && bodies.empty()) { std::fprintf(stderr, "dsrt_render: --body-poses needs --body\n"); return 2; }
+    if (upscale && coverage_aware && rng_mode != 1) { std::fprintf(stderr, "dsrt_render: --upscale --coverage-aware needs --rng-mode 1 (or --fast)\n"); return 2; }
+    if (upscale && coverage_aware && coverage && cov_desc.pattern != DSRT_COVERAGE_DIAGONAL) { std::fprintf(stderr, "dsrt_render: --upscale --coverage-aware takes --coverage diag:N (N = 1 .. 64), not a grid: pattern\n"); return 2; }
     if (upscale && rng_mode != 1) {                                 // the reference's bytes are not upscaled here: the flag is announced and ignored, as it always was
         std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
         upscale = false;
@@ -177,8 +185,8 @@ int main(int argc, char** argv) {
     if (denoise && (passes != 0 || adaptive || gbuffer)) { std::fprintf(stderr, "dsrt_render: --denoise does not combine with --passes / --adaptive / --gbuffer\n"); return 2; }
     if (denoise && denoise_iterations > 6) { std::fprintf(stderr, "dsrt_render: --denoise ITER must be between 0 and 6\n"); return 2; }
     if (denoise && spp < 2) { std::fprintf(stderr, "dsrt_render: --denoise needs --spp 2 or more\n"); return 2; }
-    if (coverage_aware && !denoise) { std::fprintf(stderr, "dsrt_render: --coverage-aware needs --denoise\n"); return 2; }
-    if (coverage_aware && (temporal || upscale)) { std::fprintf(stderr, "dsrt_render: --coverage-aware does not combine with --temporal / --upscale\n"); return 2; }
+    if (coverage_aware && !denoise && !upscale) { std::fprintf(stderr, "dsrt_render: --coverage-aware needs --denoise or --upscale\n"); return 2; }
+    if (coverage_aware && (temporal || (denoise && upscale))) { std::fprintf(stderr, "dsrt_render: --coverage-aware does not combine with --temporal, nor with --denoise and --upscale together\n"); return 2; }
     if (coverage_aware && !(alpha_min > 0.0f && alpha_min <= 1.0f)) { std::fprintf(stderr, "dsrt_render: --coverage-aware ALPHA_MIN must be > 0 and <= 1\n"); return 2; }
     if (temporal && !denoise) { std::fprintf(stderr, "dsrt_render: --temporal needs --denoise\n"); return 2; }
     if (flow && !temporal) { std::fprintf(stderr, "dsrt_render: --flow needs --temporal\n"); return 2; }
@@ -409,7 +417,25 @@ int main(int argc, char** argv) {
     std::vector<float> big_var(variance ? out_values : 0);
     DsrtUpscale up;
     dsrt_upscale_defaults(&up);
-    if (upscale) frame_step = [&](size_t, const std::string& base) -> int {
+    const bool upscale_coverage = upscale && coverage_aware;        // (--coverage then only chooses the passes' N: it writes no files of its own)
+    DsrtCoverageDesc up_cov;
+    dsrt_coverage_defaults(&up_cov);
+    if (upscale_coverage && coverage) { up_cov = cov_desc; coverage = false; }
+    if (upscale_coverage && !alpha_min_given) alpha_min = dsrt_upscale_coverage_alpha_min();
+    std::vector<float> big_alpha(upscale_coverage ? (size_t)out_w * out_h : 0);
+    if (upscale_coverage) frame_step = [&](size_t, const std::string& base) -> int {
+        if (dsrt_render_upscaled_coverage_to_host(ctx, &d, out_w, out_h, &up_cov, &up_cov, alpha_min, nullptr, &up, big.data(), nullptr, nullptr,
+                                                  variance ? big_var.data() : nullptr, img.data(), big_alpha.data(), nullptr) != DSRT_OK) return fail("rendering and upscaling with coverage");
+        const std::string path = base + ext;
+        if ((png ? dsrt_write_png(path.c_str(), big.data(), out_w, out_h) : dsrt_write_ppm(path.c_str(), big.data(), out_w, out_h)) != DSRT_OK ||
+            !write_image(base + "_lowres" + ext, img.data())) return fail("writing the frame");
+        if (dsrt_write_pfm((base + "_alpha.pfm").c_str(), big_alpha.data(), out_w, out_h, 1) != DSRT_OK) return fail("writing the alpha");
+        if (variance && dsrt_write_pfm((base + "_var.pfm").c_str(), big_var.data(), out_w, out_h, 3) != DSRT_OK) return fail("writing the variance");
+        std::printf("upscale: %d x %d -> %d x %d, coverage-aware: DIAGONAL %d, alpha_min %g\nSaved %s, %s_lowres%s, _alpha.pfm%s\n", width, height, out_w, out_h, up_cov.samples,
+                    (double)alpha_min, path.c_str(), base.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
+        return 0;
+    };
+    else if (upscale) frame_step = [&](size_t, const std::string& base) -> int {
         if (dsrt_render_upscaled_to_host(ctx, &d, out_w, out_h, denoise ? &dn : nullptr, &up, big.data(), nullptr, nullptr, variance ? big_var.data() : nullptr, img.data(),
                                          nullptr) != DSRT_OK) return fail("rendering and upscaling");
         const std::string path = base + ext;

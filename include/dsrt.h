@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -1063,6 +1063,78 @@ int  dsrt_upscale_guided_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, i
 int  dsrt_render_upscaled_to_host(DsrtContext* ctx, const DsrtRenderDesc* lo_desc, int out_width, int out_height, const DsrtDenoise* denoise /* NULL = iterations 0 */,
                                   const DsrtUpscale* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, uint8_t* h_lo_rgb8 /* optional, w*h*3 */,
                                   DsrtStats* stats);
+
+/*
+ * COVERAGE-AWARE UPSCALER (dsrt_upscale_guided_coverage; on top of the UPSCALER and COVERAGE).  A low-resolution pixel that a truss crosses holds alpha x (the
+ * radiance of the truss), alpha the share of its samples that hit: its mean mixes structure and space, and no guide can unmix it.  A DIAGONAL coverage pass at each
+ * raster can: take the low-resolution mean / alpha, upsample it guided by full-resolution ground truth, and multiply by a full-resolution alpha.  The guides lo / hi
+ * are meant to be the `rep` channels of the same passes, so `range` is finite wherever any sub-sample hit: an output pixel whose centre ray misses but which a truss
+ * crosses is no longer black, and a low-resolution pixel whose centre ray misses is a tap.  Plain G-buffer channels are legal too.  tests/_upscale_coverage_model.py
+ * reproduces every bit.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written.  "as UPSCALER" is the arithmetic above,
+ * word for word.
+ *   Inputs beyond UPSCALER's: alpha_lo (w x h floats), alpha_hi (W x H floats), both the `alpha` of a DIAGONAL coverage pass; alpha_min in (0, 1].
+ *   Per output pixel P, R = range_hi[P], aP = alpha_hi[P]:
+ *     LEVEL 0.  !(R <= FLT_MAX) || !(aP > 0.0f) (a NaN alpha included): c' = v' = support = +0.  Otherwise fx, fy, x0, y0, the 4 x 4 taps, their order (qy outer,
+ *     qx inner) and the tent b are as UPSCALER.
+ *     Per tap q, a = alpha_lo[q]: the tap is USABLE iff a >= alpha_min (a NaN alpha is not).  For a usable tap
+ *       u.k = c_q.k / a;   aa = a * a;   vu.k = v_q.k / aa
+ *     LEVEL 1 (guided, unmixed).  Skipped: a tap outside the image, a tap that is not usable, a tap with !(range_q <= FLT_MAX), a tap on the other side of the sun
+ *     bit (UPSCALER's use_sun rule).  For the others wn, ez, ea2 as UPSCALER and
+ *       wt = ((b * wn) * a) / ((1.0f + ez*ez) * (1.0f + ea2))          -- the factor a weighs a tap by the share of its samples that landed on structure
+ *       sw += wt;   sc.k += wt*u.k;   sv.k += (wt*wt)*vu.k
+ *     sw > 0:  c'.k = (sc.k/sw) * aP,  v'.k = (sv.k/(sw*sw)) * (aP*aP),  support = sw.
+ *     LEVEL 2 (when !(sw > 0)).  The same loop over every usable tap inside the image, no range or sun test, wt = b * a; the same quotients and the same
+ *     multiplication by aP and aP*aP; support = +0.
+ *     LEVEL 3 (when still !(sw > 0)).  UPSCALER's level 2 exactly: every tap inside the image, wt = b, the mixed c_q and v_q, and no multiplication by aP; it never
+ *     divides by zero, by the argument above.  support = +0.
+ *   Outputs.  UPSCALER's, with its tone map and 8-bit store applied to c', and d_level (optional, one byte per pixel): 0, 1, 2 or 3, the level that produced the pixel.
+ *   TWO IDENTITIES.  With both alpha pointers NULL the call is dsrt_upscale_guided bit for bit (alpha_min is then only checked, and d_level must be NULL: the plain
+ *   upscaler has no such output).  With both alphas 1.0f everywhere and any legal alpha_min the results are dsrt_upscale_guided's bit for bit: x / 1, x * 1 and
+ *   (b * wn) * 1 are exact, every tap is usable, and level 2 is then the old level 2 (its sw is positive, so level 3 is never reached).
+ *
+ * dsrt_upscale_guided_coverage: dsrt_upscale_guided's envelope, stream ordering and working-memory ownership.  Working memory stays 80 bytes per low-resolution
+ *   pixel: alpha_lo rides in the spare word of the normal record, {N, alpha} (the {c, range} record that decides whether a tap counts has no spare word).
+ *   DSRT_ERR_INVALID: everything dsrt_upscale_guided refuses (d_level counts as an output); exactly one alpha pointer given; alpha_min not in (0, 1] (NaN is
+ *   refused); d_level without the alphas; a misaligned alpha pointer; d_level or an alpha overlapping an output.  A refused call touches no buffer.
+ * dsrt_upscale_guided_coverage_to_host: the same from HOST buffers into HOST buffers, synchronously.
+ * dsrt_render_upscaled_coverage_to_host: the convenience form, exactly this chain of calls, in order: lo_desc->spp samples with second moments at w x h; a DIAGONAL
+ *   coverage pass at w x h (alpha and rep: normal, position, albedo, range, flags); dsrt_denoise_accumulated_coverage with those (denoise NULL = iterations 0); a
+ *   DIAGONAL coverage pass at out_width x out_height; dsrt_upscale_guided_coverage.  cov_lo / cov_hi NULL = dsrt_coverage_defaults; a GRID pattern is refused, as
+ *   dsrt_render_denoised_coverage_to_host refuses it.  The denoiser and the upscaler share the one alpha_min.  h_lo_rgb8 (optional, w*h*3 bytes): the third step's
+ *   image; h_alpha_hi (optional, out_width*out_height floats): the fourth step's alpha.  DSRT_ERR_NO_SCENE before an upload.  stats (optional): the accumulate launch's.
+ * dsrt_upscale_coverage_alpha_min: the default alpha_min of this chain, 1/8 -- not the denoiser's 1/16: measured below, 1/8 is the best of {1/64, 1/16, 1/8, 1/4} over
+ *   the covered pixels and over the whole frame on both scenes (by 0.7 % and 0.4 % over 1/16).
+ *   Measured on the CPU model (tests/test_upscale_coverage_host.py): DIAGONAL 64 at both rasters, the coverage-aware denoiser in front, MSE
+ *   against 256 spp at the output size under another seed; "plain" is dsrt_upscale_guided's chain, "native" the same sample budget (spp / 4) at the output size,
+ *   coverage-denoised; sets: partial = 0 < alpha_hi < 1, centre misses = the centre ray misses and alpha_hi > 0 (dsrt_upscale_guided writes these black), covered =
+ *   alpha_hi > 0.  MSE plain / native / this chain with alpha_min 1/64, 1/16, 1/8, 1/4 / with 1/8 and DIAGONAL 16 at the output raster:
+ *     station_near 100 x 56 -> 200 x 112, 16 spp
+ *       partial        2789 px: 1.312e-2 / 3.99e-3 / 5.23e-3, 3.49e-3, 3.31e-3, 3.98e-3 / 3.40e-3
+ *       centre misses  1529 px: 9.70e-3 / 2.13e-3 / 2.00e-3, 1.70e-3, 1.70e-3, 1.82e-3 / 1.68e-3
+ *       covered        9665 px: 8.831e-3 / 4.199e-3 / 6.054e-3, 5.541e-3, 5.500e-3, 5.713e-3 / 5.470e-3         levels 0..3 at 1/8: 12735, 9542, 123, 0
+ *     textured 48 x 32 -> 96 x 64, 8 spp
+ *       partial         238 px: 4.743e-2 / 8.29e-3 / 3.00e-4, 2.80e-4, 2.64e-4, 2.99e-4 / 4.30e-4
+ *       centre misses   141 px: 4.781e-2 / 1.001e-2 / 7.77e-5, 7.56e-5, 7.37e-5, 7.27e-5 / 2.29e-4
+ *       covered        3203 px: 8.896e-3 / 8.123e-3 / 4.887e-3, 4.874e-3, 4.853e-3, 4.853e-3 / 4.874e-3         levels 0..3 at 1/8: 2941, 3203, 0, 0
+ *   Over the covered pixels this chain has 0.62 (station) and 0.55 (room) of the plain chain's error, and 1.31 and 0.60 of the native frame's: the successor of
+ *   UPSCALER's 1.70, which is the plain chain against the plain native frame over the same pixels.  Measured on an MI355X (GPU probe, tools/upscale_probe.py): the
+ *   gather kernel takes 102 us at 960 x 540 -> 1920 x 1080 and 363 us at 1920 x 1080 -> 3840 x 2160, 1.36 and 1.34 times dsrt_upscale_guided's; what the form costs
+ *   is the output raster's coverage pass, 7.9 / 23.9 ms at 1080p and 25.8 / 86.4 ms at 4K for DIAGONAL 16 / 64.  With 64 sub-samples the whole frame is slower than
+ *   the native frame of the same sample budget; 16 is the recommended count for cov_hi.
+ */
+float dsrt_upscale_coverage_alpha_min(void);
+int  dsrt_upscale_guided_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* d_lo_linear, const float* d_lo_var /* optional */,
+                                  const DsrtUpscaleGuides* lo, const DsrtUpscaleGuides* hi, const float* d_lo_alpha, const float* d_hi_alpha, float alpha_min,
+                                  const DsrtUpscale* params, uint8_t* d_rgb8, float* d_f32, float* d_linear, float* d_var, float* d_support, uint8_t* d_level, void* stream);
+int  dsrt_upscale_guided_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, int lo_width, int lo_height, const float* h_lo_linear, const float* h_lo_var,
+                                          const DsrtUpscaleGuides* h_lo, const DsrtUpscaleGuides* h_hi, const float* h_lo_alpha, const float* h_hi_alpha, float alpha_min,
+                                          const DsrtUpscale* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, float* h_support, uint8_t* h_level);
+int  dsrt_render_upscaled_coverage_to_host(DsrtContext* ctx, const DsrtRenderDesc* lo_desc, int out_width, int out_height, const DsrtCoverageDesc* cov_lo /* NULL = defaults */,
+                                           const DsrtCoverageDesc* cov_hi /* NULL = defaults */, float alpha_min, const DsrtDenoise* denoise /* NULL = iterations 0 */,
+                                           const DsrtUpscale* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, uint8_t* h_lo_rgb8 /* optional, w*h*3 */,
+                                           float* h_alpha_hi /* optional, W*H */, DsrtStats* stats);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,

@@ -8,6 +8,11 @@ synchronous _to_host calls (`--frame-reps` of them), result copies included.  Pe
   atrous_iteration    the yardstick: one a-trous iteration of the denoiser at the OUTPUT size (two iterations minus one, same run, the denoiser's unchanged kernel)
   frame_upscaled_64   dsrt_render_upscaled_to_host: 64 spp at the low resolution, denoised (defaults), upscaled
   frame_native_64/16  dsrt_render_denoised_to_host at the output size with 64 and with 16 spp
+  upscale_coverage_call   dsrt_upscale_guided_coverage (include/dsrt.h, COVERAGE-AWARE UPSCALER) on the alphas and representatives of DIAGONAL 64 coverage passes at both
+                      rasters and the coverage-denoised low-resolution frame, interleaved with upscale_call in the same process; covered_fraction (alpha > 0 at the
+                      output raster) and the pixels per level say how many more pixels do work than hit_fraction's
+  coverage_hi_8/16/64 dsrt_render_coverage (alpha and the five representative channels) at the output size, DIAGONAL 8, 16 and 64: what the form adds to a frame
+  frame_upscaled_coverage_64_n8/16/64   dsrt_render_upscaled_coverage_to_host: 64 spp at the low resolution, both coverage passes DIAGONAL n, coverage-denoised, upscaled
   kernels_us          with --trace: every upscale / a-trous kernel's average from a kernel trace (rocprofv3 --kernel-trace --stats around a child of its own that runs
                       only upscale calls and two-iteration denoise calls): the upscale kernel's time ALONE
 Prints one JSON line.
@@ -70,6 +75,18 @@ def child(a):
         four = lambda g: {k: g[k] for k in d.DENOISE_GUIDES}                          # noqa: E731
         _, _, c, v = ctx.denoise_accumulated(lo_desc, acc.sum, acc.sum_sq, four(lo), samples_done=a.spp, want_rgb8=False, want_var=True, stream=raw)
         hi = gbuffer(hi_desc)
+        cov = {n: d.coverage_desc("diag", n) for n in (8, 16, 64)}
+
+        def coverage(desc, n, alpha=None, g=None):
+            if g is None:
+                alpha = torch.empty((desc.height, desc.width), dtype=torch.float32, device=dev)
+                g = gbuffer(desc)
+            ctx.render_coverage(desc, cov[n], {"alpha": alpha.data_ptr()}, {k: x.data_ptr() for k, x in g.items()}, stream=raw)
+            return alpha, g
+
+        a_lo, r_lo = coverage(lo_desc, 64)
+        _, _, cc, cv = ctx.denoise_accumulated_coverage(lo_desc, acc.sum, acc.sum_sq, four(r_lo), a_lo, samples_done=a.spp, want_rgb8=False, want_var=True, stream=raw)
+        a_hi, r_hi = coverage(hi_desc, 64)
         few = d.make_desc(W, H, 2, depth, rng_mode=1)                                # the yardstick's frame: sums at the output size (two samples: only the filter is timed)
         acc_hi = d.Accumulator(ctx, few, moments=True)
         acc_hi.render(0, stream=raw)
@@ -79,12 +96,17 @@ def child(a):
         def run(cfg):
             if cfg == "upscale_call":
                 ctx.upscale_guided(hi_desc, w, h, c, lo, hi, lo_var=v, stream=raw)
+            elif cfg == "upscale_coverage_call":
+                ctx.upscale_guided_coverage(hi_desc, w, h, cc, r_lo, r_hi, a_lo, a_hi, lo_var=cv, stream=raw)
             elif cfg == "gbuffer_hi":
                 gbuffer(hi_desc, hi)
+            elif cfg.startswith("coverage_hi_"):
+                coverage(hi_desc, int(cfg.rsplit("_", 1)[1]), a_tmp, r_tmp)
             else:
                 ctx.denoise_accumulated(few, acc_hi.sum, acc_hi.sum_sq, four(hi), samples_done=2, params=d.denoise_defaults(iterations=int(cfg[-1])), stream=raw)
 
-        cfgs = ["upscale_call", "atrous_1", "atrous_2"] + ([] if a.child == "trace" else ["gbuffer_hi"])
+        a_tmp, r_tmp = coverage(hi_desc, 8)                                          # (the timed coverage passes write here: a_hi / r_hi stay DIAGONAL 64's)
+        cfgs = ["upscale_call", "upscale_coverage_call", "atrous_1", "atrous_2"] + ([] if a.child == "trace" else ["gbuffer_hi", "coverage_hi_8", "coverage_hi_16", "coverage_hi_64"])
         ms = {}
         for rep in range(a.warmup + a.reps):
             k = rep % len(cfgs)
@@ -101,8 +123,16 @@ def child(a):
         row = {"median_ms": med, "min_ms": {k: min(x) for k, x in ms.items()}, "max_ms": {k: max(x) for k, x in ms.items()},
                "atrous_iteration_ms": med["atrous_2"] - med["atrous_1"], "hit_fraction": float(torch.isfinite(hi["range"]).double().mean())}
         row["upscale_call_over_iteration"] = med["upscale_call"] / row["atrous_iteration_ms"]
+        row["upscale_coverage_call_over_upscale_call"] = med["upscale_coverage_call"] / med["upscale_call"]
+        row["covered_fraction"] = float((a_hi > 0).double().mean())
+        level = ctx.upscale_guided_coverage(hi_desc, w, h, cc, r_lo, r_hi, a_lo, a_hi, want_rgb8=False, want_linear=False, want_level=True, stream=raw)[5]
+        row["pixels_per_level"] = torch.bincount(level.flatten().long(), minlength=4).tolist()
         if a.child != "trace":
             frames = {"frame_upscaled_64": lambda: ctx.render_upscaled_to_host(lo_desc, W, H, denoise=d.denoise_defaults()),
+                      **{f"frame_upscaled_coverage_64_n{n}": (lambda n=n: ctx.render_upscaled_coverage_to_host(lo_desc, W, H, cov_lo=cov[n], cov_hi=cov[n],
+                                                                                                                   denoise=d.denoise_defaults())) for n in (8, 16, 64)},
+                      "frame_native_coverage_64": lambda: ctx.render_denoised_coverage_to_host(hi_desc),
+                      "frame_native_coverage_16": lambda: ctx.render_denoised_coverage_to_host(d.make_desc(W, H, max(a.spp // 4, 2), depth, rng_mode=1)),
                       "frame_native_64": lambda: ctx.render_denoised_to_host(hi_desc),
                       "frame_native_16": lambda: ctx.render_denoised_to_host(d.make_desc(W, H, max(a.spp // 4, 2), depth, rng_mode=1))}
             wall = {}
