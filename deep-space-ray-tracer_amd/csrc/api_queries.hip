@@ -2,6 +2,7 @@
 // host forms.  Calls the launchers of gbuffer_kernel.hip, coverage_kernel.hip and raycast_kernel.hip; api_reconstruct.hip's convenience forms call
 // dsrt_render_gbuffer and dsrt_render_coverage.
 #include <algorithm>
+#include <type_traits>
 
 #include "api_internal.h"
 
@@ -38,6 +39,26 @@ void channels(const S& s, const size_t (&bytes_per)[N], size_t n, Dir dir, Stage
     const void* p[N];
     std::memcpy(p, &s, sizeof p);
     for (size_t k = 0; k < N; ++k) out[k] = Staged{p[k], n * bytes_per[k], dir};
+}
+
+// What the G-buffer and the coverage pass take from the context and the resident scene: the scene's view, the camera and its optical axis, the sun, the LDS stack's size.
+template <typename Args>
+void set_view(Args& a, const DsrtContext* ctx, const PackedScene* sc) {
+    a.scene = sc->view;
+    const GPUCamera& c = ctx->frame.camera;
+    pack_camera(c, a.cam);
+    a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
+    a.sun_dir[0] = ctx->frame.sun_dir.x; a.sun_dir[1] = ctx->frame.sun_dir.y; a.sun_dir[2] = ctx->frame.sun_dir.z;
+    a.sun_enabled = ctx->frame.sun_enabled;
+    a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
+}
+
+// The caller's channel pointers into a kernel's argument block: DsrtGBuffer's eleven, or DsrtRayHits' nine (it has no depth and no sun_cos).
+template <typename Args, typename Channels>
+void set_channels(Args& a, const Channels& c) {
+    a.t = c.t; a.range = c.range; a.position = c.position; a.normal = c.normal; a.uv = c.uv; a.albedo = c.albedo;
+    a.prim_id = c.prim_id; a.material_id = c.material_id; a.flags = c.flags;
+    if constexpr (std::is_same_v<Channels, DsrtGBuffer>) { a.depth = c.depth; a.sun_cos = c.sun_cos; }
 }
 
 // Ray queries (raycast_kernel.hip).  Argument checks shared by the device and the host form: every range is known from `count`.
@@ -122,17 +143,11 @@ int dsrt_render_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, const Dsr
     HIP_TRY(hipSetDevice(ctx->device));
     CoverageArgs a;
     std::memset(&a, 0, sizeof a);
-    a.scene = sc->view;
-    const GPUCamera& c = ctx->frame.camera;
-    pack_camera(c, a.cam);
-    a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
-    a.sun_dir[0] = ctx->frame.sun_dir.x; a.sun_dir[1] = ctx->frame.sun_dir.y; a.sun_dir[2] = ctx->frame.sun_dir.z;
-    a.sun_enabled = ctx->frame.sun_enabled;
+    set_view(a, ctx, sc);
     a.width = desc->width; a.height = desc->height;
     a.pattern = cd->pattern; a.samples = cd->samples;
     a.n = coverage_samples(*cd);
     a.per_wave = 64 / a.n;
-    a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
     const DsrtGBuffer& gb = cov->rep;
     a.hits = cov->hits; a.alpha = cov->alpha; a.mask = (unsigned long long*)cov->mask;
     a.sun_hits = cov->sun_hits; a.sun_alpha = cov->sun_alpha; a.sun_mask = (unsigned long long*)cov->sun_mask;
@@ -141,8 +156,7 @@ int dsrt_render_coverage(DsrtContext* ctx, const DsrtRenderDesc* desc, const Dsr
         a.n_classes = classes->count;
         std::memcpy(a.class_first, classes->first, sizeof a.class_first); std::memcpy(a.class_num, classes->num, sizeof a.class_num);
     }
-    a.t = gb.t; a.range = gb.range; a.depth = gb.depth; a.position = gb.position; a.normal = gb.normal; a.uv = gb.uv; a.albedo = gb.albedo;
-    a.prim_id = gb.prim_id; a.material_id = gb.material_id; a.sun_cos = gb.sun_cos; a.flags = gb.flags;
+    set_channels(a, gb);
     a.want_sun = cov->sun_hits || cov->sun_alpha || cov->sun_mask || gb.flags;
     for (size_t k = kCoverageOwn; k < kCoverageChannels; ++k) a.want_rep = a.want_rep || ch[k].host;
     if (int rc = ctx->gb_status.grow(1)) return rc;                          // (one launch at a time per context: the G-buffer pass's word serves)
@@ -181,18 +195,11 @@ int dsrt_render_gbuffer(DsrtContext* ctx, const DsrtRenderDesc* desc, const Dsrt
     HIP_TRY(hipSetDevice(ctx->device));
     GBufferArgs a;
     std::memset(&a, 0, sizeof a);
-    a.scene = sc->view;
-    const GPUCamera& c = ctx->frame.camera;
-    pack_camera(c, a.cam);
-    a.neg_w[0] = -c.w.x; a.neg_w[1] = -c.w.y; a.neg_w[2] = -c.w.z;
-    a.sun_dir[0] = ctx->frame.sun_dir.x; a.sun_dir[1] = ctx->frame.sun_dir.y; a.sun_dir[2] = ctx->frame.sun_dir.z;
-    a.sun_enabled = ctx->frame.sun_enabled;
+    set_view(a, ctx, sc);
     a.width = desc->width; a.height = desc->height;
     a.tiles_x = (desc->width + 7) / 8;
     const int tiles = a.tiles_x * ((desc->height + 7) / 8);
-    a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
-    a.t = gb->t; a.range = gb->range; a.depth = gb->depth; a.position = gb->position; a.normal = gb->normal; a.uv = gb->uv; a.albedo = gb->albedo;
-    a.prim_id = gb->prim_id; a.material_id = gb->material_id; a.sun_cos = gb->sun_cos; a.flags = gb->flags;
+    set_channels(a, *gb);
     if (int rc = ctx->gb_status.grow(1)) return rc;
     a.status = ctx->gb_status.p;
     return launch_enveloped(ctx, (hipStream_t)stream_v, a.status, stats, "G-buffer", tiles, [&](hipStream_t s) { return launch_gbuffer(a, tiles, s); });
@@ -232,8 +239,7 @@ int dsrt_trace_rays(DsrtContext* ctx, int count, const DsrtRays* rays, int mode,
     a.origins = rays->origins; a.dirs = rays->dirs; a.t_min = rays->t_min; a.t_max = rays->t_max;
     a.count = count;
     a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
-    a.t = hits->t; a.range = hits->range; a.position = hits->position; a.normal = hits->normal; a.uv = hits->uv; a.albedo = hits->albedo;
-    a.prim_id = hits->prim_id; a.material_id = hits->material_id; a.flags = hits->flags;
+    set_channels(a, *hits);
     if (int rc = ctx->rc_status.grow(1)) return rc;
     a.status = ctx->rc_status.p;
     const int blocks = (int)(((size_t)count + 63) / 64);                   // one lane per ray

@@ -5,20 +5,20 @@
 //   * One lane per sub-sample.  A 64-thread workgroup is one wave and holds P = 64 / n consecutive pixels of the image in linear order: pixel
 //     p = workgroup * P + lane / n, sub-sample k = lane % n.  Lanes beyond P * n and lanes of pixels >= W * H are idle.  A wave's pixels may wrap from one
 //     row's end to the next row's start; with n = 64 a wave is a pixel and its ballot is the pixel's mask.  The n rays of a pixel are as coherent as rays get.
-//   * The walk, the LDS [entry][lane] stack sized by the tree's depth, the sphere loop and the record assembly are the G-buffer pass's, restated (sharing them
-//     through walk_common.h would change that kernel's code; tools/device_code_diff.py holds it and the raycast kernel unchanged).
+//   * The walk and the LDS [entry][lane] stack sized by the tree's depth are the G-buffer pass's (walk_common.h); so are the record assembly, the sphere loop, the
+//     shadow ray's any-hit tail and the stores of `rep`, which all three query kernels take from hit_record.h (what sharing them did to the device code:
+//     profiles/hit_record/device_code_diff.md).
 //   * Phase 2: every hit lane that faces the Sun traces its any-hit shadow ray -- all lanes of a pixel group work -- only when a sun output or rep.flags is asked for.
 //   * Reduction: the wave's ballot of `hit`, shifted and masked to the pixel group's n bits, is the mask, its popcount the count; the same for the Sun bit and
 //     for each class (at most 16 wave-uniform ballots).  The representative: every hit lane forms key << 6 | k and one LDS atomicMin per hit lane on the pixel
 //     group's word picks the lane that writes `rep` (an integer minimum: deterministic whatever the order).  Lane k = 0 of a group writes counts, alphas, masks.
 //   * No global atomic but the status word; no scratch.
+#include "hit_record.h"
 #include "launchers.h"
-#include "walk_common.h"
 
 namespace dsrt {
 
 namespace {
-constexpr uint32_t kCvHit = 1u, kCvFront = 2u, kCvSphere = 4u, kCvSunVisible = 8u;      // DSRT_GB_* of include/dsrt.h
 constexpr int kCoverageGrid = 0;                                                        // DSRT_COVERAGE_GRID
 }
 
@@ -62,48 +62,16 @@ __global__ void __launch_bounds__(64) dsrt_coverage_kernel(const CoverageArgs a)
     int slot = -1;
     if (live) walk_reference_tree<false>(S, stk, a.stack_entries, ro, rd, rinv, kTMin, closest, slot, hu, hv, status);
 
-    // ---- finish scene_hit :516-551: the triangle's record from (slot, t, u, v), then the spheres ----
-    bool hit = false, front = false, sphere = false;
-    F3 hp = mk(0, 0, 0), hn = mk(0, 0, 0);
-    int mat_id = -1, tex_id = -1, prim = -1;
-    if (slot >= 0) {
-        const float4* sh = S.tri_shade + (size_t)slot * 3;
-        const float4 a0 = sh[0], a1 = sh[1], a2 = sh[2];
-        const float t = closest;
-        hp = mk(ro.x + t * rd.x, ro.y + t * rd.y, ro.z + t * rd.z);
-        const float wgt = 1.0f - hu - hv;                                    // :359-369
-        F3 nn = ((mk(a0.x, a0.y, a0.z) * wgt) + (mk(a0.w, a1.x, a1.y) * hu)) + (mk(a1.z, a1.w, a2.x) * hv);
-        nn = normalize(nn);
-        front = dot(rd, nn) < 0.0f;
-        hn = front ? nn : (nn * -1.0f);
-        mat_id = __float_as_int(a2.y);
-        tex_id = __float_as_int(a2.z);
-        prim = __float_as_int(a2.w);
-        hit = true;
-    }
-    for (int i = 0; live && i < S.num_spheres; ++i) {
-        const GPUSphere sph = S.spheres[i];
-        float t_hit; F3 n_hit;
-        if (hit_sphere(sph, ro, rd, closest, t_hit, n_hit)) {
-            hit = true; sphere = true;
-            closest = t_hit;
-            hp = mk(ro.x + t_hit * rd.x, ro.y + t_hit * rd.y, ro.z + t_hit * rd.z);
-            front = dot(rd, n_hit) < 0.0f;
-            hn = front ? n_hit : (n_hit * -1.0f);
-            mat_id = sph.material_id;
-            tex_id = -1;
-            prim = -2 - i;
-            hu = 0.0f; hv = 0.0f;
-        }
-    }
-    if (hit && (unsigned)mat_id >= (unsigned)S.num_materials) { status |= kFlagBadMaterial; hit = false; }
+    // ---- finish scene_hit :516-551 (hit_record.h): the triangle's record from (slot, t, u, v), then the spheres ----
+    const HitRecord h = finish_scene_hit(S, ro, rd, kTMin, closest, slot, hu, hv, live, status);
+    const bool hit = h.hit;
 
     // ---- the Sun: cos_theta of :800-806 and the shadow ray's start ----
     float cos_t = 0.0f;
     F3 ldir = mk(0, 0, 0);
     if (a.sun_enabled) {
         ldir = normalize(mk(-a.sun_dir[0], -a.sun_dir[1], -a.sun_dir[2]));
-        if (hit) cos_t = fmaxf(0.0f, dot(hn, ldir));
+        if (hit) cos_t = fmaxf(0.0f, dot(h.n, ldir));
     }
     bool sun_visible = false;
 
@@ -111,17 +79,12 @@ __global__ void __launch_bounds__(64) dsrt_coverage_kernel(const CoverageArgs a)
     const bool need_shadow = a.want_sun && hit && cos_t > 0.0f;
     if (__builtin_amdgcn_ballot_w64(need_shadow) != 0ull) {
         if (need_shadow) {
-            const F3 so = hp + (hn * 1e-3f);
+            const F3 so = h.p + (h.n * 1e-3f);
             const F3 sinv = mk(1.0f / ldir.x, 1.0f / ldir.y, 1.0f / ldir.z);
             float s_closest = kTMax, su = 0.0f, sv = 0.0f;
             int s_slot = -1;
             walk_reference_tree<true>(S, stk, a.stack_entries, so, ldir, sinv, kTMin, s_closest, s_slot, su, sv, status);
-            bool blocked = s_slot >= 0;
-            for (int i = 0; !blocked && i < S.num_spheres; ++i) {
-                float t_hit; F3 n_hit;
-                blocked = hit_sphere(S.spheres[i], so, ldir, s_closest, t_hit, n_hit);
-            }
-            sun_visible = !blocked;
+            sun_visible = !any_hit_blocked(S, so, ldir, kTMin, s_closest, s_slot);
         }
     }
 
@@ -145,7 +108,7 @@ __global__ void __launch_bounds__(64) dsrt_coverage_kernel(const CoverageArgs a)
     if (a.class_hits) {
         for (int c = 0; c < a.n_classes; ++c) {                              // wave-uniform: one ballot per class
             const int first = a.class_first[c];
-            const bool in_c = hit && !sphere && prim >= first && (uint32_t)(prim - first) < (uint32_t)a.class_num[c];
+            const bool in_c = hit && !h.sphere && h.prim >= first && (uint32_t)(h.prim - first) < (uint32_t)a.class_num[c];
             const unsigned long long m_c = (__builtin_amdgcn_ballot_w64(in_c) >> shift) & group_bits;
             if (head) a.class_hits[p * (size_t)a.n_classes + (size_t)c] = (uint8_t)__popcll(m_c);
         }
@@ -159,34 +122,8 @@ __global__ void __launch_bounds__(64) dsrt_coverage_kernel(const CoverageArgs a)
         __syncthreads();
         const bool writer = hit ? rep_word[grp] == word : (head && hits == 0);
         if (writer) {
-            const float inf = __builtin_inff();
-            if (a.t) a.t[p] = hit ? closest : inf;
-            if (a.range) a.range[p] = hit ? closest * sqrtf(dot(rd, rd)) : inf;
-            if (a.depth) a.depth[p] = hit ? closest * dot(rd, ld3(a.neg_w)) : inf;
-            if (a.position) { float* o = a.position + p * 3; o[0] = hit ? hp.x : 0.0f; o[1] = hit ? hp.y : 0.0f; o[2] = hit ? hp.z : 0.0f; }
-            if (a.normal) { float* o = a.normal + p * 3; o[0] = hit ? hn.x : 0.0f; o[1] = hit ? hn.y : 0.0f; o[2] = hit ? hn.z : 0.0f; }
-            if (a.uv) { float* o = a.uv + p * 2; o[0] = hit ? hu : 0.0f; o[1] = hit ? hv : 0.0f; }
-            if (a.albedo) {
-                F3 alb = mk(0, 0, 0);
-                if (hit) {
-                    const float4 m1 = S.materials[(size_t)mat_id * 3 + 1];
-                    alb = mk(m1.x, m1.y, m1.z);                              // :763-774
-                    if (tex_id >= 0 && S.tri_uv) {
-                        const float4* uvp = S.tri_uv + (size_t)slot * 2;
-                        const float4 u0 = uvp[0], u1 = uvp[1];
-                        const float wgt = 1.0f - hu - hv;
-                        const float u_tex = wgt * u0.x + hu * u0.z + hv * u1.x;
-                        const float v_tex = wgt * u0.y + hu * u0.w + hv * u1.y;
-                        uint32_t n_fetch = 0;
-                        alb = alb * tex2d(S, tex_id, u_tex, v_tex, n_fetch);
-                    }
-                }
-                float* o = a.albedo + p * 3; o[0] = alb.x; o[1] = alb.y; o[2] = alb.z;
-            }
-            if (a.prim_id) a.prim_id[p] = hit ? prim : -1;
-            if (a.material_id) a.material_id[p] = hit ? mat_id : -1;
-            if (a.sun_cos) a.sun_cos[p] = cos_t;
-            if (a.flags) a.flags[p] = (uint8_t)(hit ? (kCvHit | (front ? kCvFront : 0u) | (sphere ? kCvSphere : 0u) | (sun_visible ? kCvSunVisible : 0u)) : 0u);
+            const HitChannels ch = {a.t, a.range, a.depth, a.position, a.normal, a.uv, a.albedo, a.prim_id, a.material_id, a.sun_cos, a.flags};
+            store_hit(S, ch, p, h, rd, a.neg_w, cos_t, sun_visible);
         }
     }
     if (status) atomicOr(a.status, status);
