@@ -329,6 +329,33 @@ def upscale_defaults(**changes):
     return _defaults(capi.DsrtUpscale, lib.dsrt_upscale_defaults, changes)
 
 
+def sensor_psf_gaussian(sigma, size):
+    """dsrt_sensor_psf_gaussian: a normalised size x size Gaussian PSF (float32, row-major) for sensor_defaults(psf=...)."""
+    taps = np.zeros((int(size), int(size)), np.float32)
+    _check(lib.dsrt_sensor_psf_gaussian(float(sigma), int(size), taps.ctypes.data), "dsrt_sensor_psf_gaussian")
+    return taps
+
+
+def sensor_defaults(psf=None, **changes):
+    """dsrt_sensor_defaults (include/dsrt.h, SENSOR MODEL): the DsrtSensor the library fills, with `changes` applied.  psf: a square float32 array of odd size
+    (1 .. 33), kept alive by the struct it is set in; None = no blur."""
+    p = _defaults(capi.DsrtSensor, lib.dsrt_sensor_defaults, changes)
+    if psf is not None:
+        taps = np.ascontiguousarray(psf, np.float32)
+        if taps.ndim != 2 or taps.shape[0] != taps.shape[1]:
+            raise ValueError(f"psf must be a square 2-D array, not {taps.shape}")
+        p.psf, p.psf_size = taps.ctypes.data, taps.shape[0]
+        p._keep_psf = taps
+    return p
+
+
+def write_pnm16(path, dn, bits):
+    """dsrt_write_pnm16: a raw frame (H, W) or (H, W, 3) of uint16 DN from a `bits`-bit ADC as P5 / P6 with maxval 2^bits - 1."""
+    a = np.ascontiguousarray(dn, dtype=np.uint16)
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    _check(lib.dsrt_write_pnm16(str(path).encode(), a.ctypes.data, int(a.shape[1]), int(a.shape[0]), int(ch), (1 << int(bits)) - 1), "dsrt_write_pnm16")
+
+
 def aligned_zeros(count, dtype=np.float32, align=64):
     """A zeroed numpy array of `count` elements whose data starts on an `align`-byte boundary (a host history buffer must be 16-byte aligned)."""
     raw = np.zeros(count * np.dtype(dtype).itemsize + align, np.uint8)
@@ -1141,6 +1168,32 @@ class Context:
                                                          C.byref(params), *map(_array_ptr, out), _array_ptr(lo_rgb8), _array_ptr(alpha), C.byref(st)),
                "dsrt_render_upscaled_coverage_to_host")
         return (*out, lo_rgb8, alpha, st)
+
+    # ---- the detector model (include/dsrt.h, SENSOR MODEL): a linear frame as raw DN ----
+    def sensor_apply(self, desc, linear, params=None, want_dn=True, want_signal=False, want_rgb8=False, stream=None):
+        """dsrt_sensor_apply (a torch device tensor) or dsrt_sensor_apply_to_host (a numpy array, chosen by linear's type): the linear frame `linear` (float32,
+        desc.height*desc.width*3: the denoiser's or the upscaler's) through the detector `params` (a DsrtSensor: sensor_defaults()).  Returns (dn, signal, rgb8): uint16
+        and float32 of shape (height, width, 3), or (height, width) with params.mono, and uint8 (height, width, 3); None where not asked for."""
+        params = sensor_defaults() if params is None else params
+        on_device = _torch is not None and isinstance(linear, _torch.Tensor)
+        n = desc.width * desc.height * 3
+        if on_device:
+            lin = self._device_tensor(linear, _torch.float32, (n, f"width*height*3 = {n}"), "linear")
+        else:
+            lin = np.ascontiguousarray(linear, np.float32).reshape(n)
+        planes = (desc.height, desc.width) if params.mono else (desc.height, desc.width, 3)
+        shapes = ((want_dn, planes, np.uint16), (want_signal, planes, np.float32), (want_rgb8, (desc.height, desc.width, 3), np.uint8))
+        if on_device:
+            out = tuple(_torch.empty(shape, dtype=getattr(_torch, np.dtype(dt).name), device=lin.device) if want else None for want, shape, dt in shapes)
+        else:
+            out = tuple(np.zeros(shape, dt) if want else None for want, shape, dt in shapes)
+        ptr = _tensor_ptr if on_device else _array_ptr
+        head = (self._h, C.byref(desc), ptr(lin), C.byref(params), *map(ptr, out))
+        if on_device:
+            _check(lib.dsrt_sensor_apply(*head, C.c_void_p(self._raw_stream(stream))), "dsrt_sensor_apply")
+        else:
+            _check(lib.dsrt_sensor_apply_to_host(*head), "dsrt_sensor_apply_to_host")
+        return out
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

@@ -158,6 +158,12 @@ class DsrtCoverageClasses(C.Structure):
     _fields_ = [("count", C.c_int), ("first", C.c_int * 16), ("num", C.c_int * 16)]
 
 
+class DsrtSensor(C.Structure):
+    _fields_ = [("psf", C.c_void_p), ("psf_size", C.c_int), ("mono", C.c_int), ("gain_e", C.c_float), ("prnu", C.c_float), ("dark_e", C.c_float), ("dsnu_e", C.c_float),
+                ("read_e", C.c_float), ("full_well_e", C.c_float), ("e_per_dn", C.c_float), ("offset_dn", C.c_float), ("bits", C.c_int), ("noise", C.c_int),
+                ("seed", C.c_uint64), ("frame", C.c_uint32)]
+
+
 class DsrtCoverage(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("hits", "alpha", "mask", "sun_hits", "sun_alpha", "sun_mask", "class_hits")] + [("rep", DsrtGBuffer)]
 
@@ -208,6 +214,7 @@ EXPORTS = [
     "dsrt_coverage_defaults", "dsrt_render_coverage", "dsrt_render_coverage_to_host", "dsrt_denoise_coverage_alpha_min", "dsrt_denoise_accumulated_coverage",
     "dsrt_denoise_accumulated_coverage_to_host", "dsrt_render_denoised_coverage_to_host",
     "dsrt_upscale_coverage_alpha_min", "dsrt_upscale_guided_coverage", "dsrt_upscale_guided_coverage_to_host", "dsrt_render_upscaled_coverage_to_host",
+    "dsrt_sensor_defaults", "dsrt_sensor_psf_gaussian", "dsrt_sensor_apply", "dsrt_sensor_apply_to_host", "dsrt_write_pnm16",
     "dsrt_selftest_read_schedule", "dsrt_selftest_tile_order", "dsrt_selftest_tile_reorder", "dsrt_selftest_batch_table",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
@@ -351,6 +358,11 @@ def load():
                                                          P(DsrtUpscale), vp, vp, vp, vp, vp, vp])
     sig("dsrt_render_upscaled_coverage_to_host", C.c_int, [vp, P(DsrtRenderDesc), C.c_int, C.c_int, P(DsrtCoverageDesc), P(DsrtCoverageDesc), C.c_float, P(DsrtDenoise),
                                                           P(DsrtUpscale), vp, vp, vp, vp, vp, vp, P(DsrtStats)])
+    sig("dsrt_sensor_defaults", None, [P(DsrtSensor)])
+    sig("dsrt_sensor_psf_gaussian", C.c_int, [C.c_float, C.c_int, vp])
+    sig("dsrt_sensor_apply", C.c_int, [vp, P(DsrtRenderDesc), vp, P(DsrtSensor), vp, vp, vp, vp])
+    sig("dsrt_sensor_apply_to_host", C.c_int, [vp, P(DsrtRenderDesc), vp, P(DsrtSensor), vp, vp, vp])
+    sig("dsrt_write_pnm16", C.c_int, [C.c_char_p, vp, C.c_int, C.c_int, C.c_int, C.c_int])
     sig("dsrt_host_scene_begin_body", C.c_int, [vp])
     sig("dsrt_host_scene_body_count", C.c_int, [vp])
     sig("dsrt_host_scene_body_range", C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int)])
@@ -380,7 +392,7 @@ def load():
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
     for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
-                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
+                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses, None, DsrtSensor)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
         if struct is not None and lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

@@ -138,6 +138,8 @@ struct DsrtContext {
     dsrt::DevBuf<uint32_t> rc_status;     // dsrt_trace_rays' status word
     dsrt::DevBuf<float4> dn_cl[2], dn_vl[2], dn_nr, dn_xf, dn_al;   // dsrt_denoise_accumulated: 7 records of 16 bytes per pixel (launchers.h, DenoiseBuffers)
     dsrt::DevBuf<float4> up_rec[5];       // dsrt_upscale_guided[_coverage]: 5 records of 16 bytes per LOW-resolution pixel (launchers.h, UpscaleRecords)
+    dsrt::DevBuf<float> sn_psf;           // dsrt_sensor_apply: the taps on the device, and what they hold now (a call with the same taps uploads nothing)
+    std::vector<float> sn_psf_host;
     // dsrt_render_denoised_temporal_to_host: the sequence the context keeps -- two histories (tp_hist[tp_cur] holds the last frame's), that frame's camera and size
     dsrt::DevBuf<float4> tp_hist[2];
     GPUCamera tp_camera{};

@@ -125,6 +125,19 @@ hipError_t launch_upscale_pack_coverage(const float* linear, const float* var, c
                                         const uint8_t* flags, const float* alpha, size_t n_pixels, const UpscaleRecords& r, hipStream_t stream);
 hipError_t launch_upscale_coverage(const UpscaleCoverageArgs& a, bool device_libm, hipStream_t stream);
 
+// sensor_kernel.hip (include/dsrt.h, SENSOR MODEL).  in: the linear frame, W*H*3 floats; psf: psf_size x psf_size taps on the DEVICE (null = no blur, psf_size then
+// unused); the outputs that are not null are written (at least one is), C = 1 (`mono`) or 3 planes per pixel in out_dn and out_signal, always 3 bytes in out_rgb8.
+// The rest is DsrtSensor's, the seed as its two Philox key words.
+struct SensorArgs {
+    const float* in; const float* psf;
+    uint16_t* out_dn; float* out_signal; uint8_t* out_rgb8;
+    int W, H, psf_size;
+    float gain_e, prnu, dark_e, dsnu_e, read_e, full_well_e, e_per_dn, offset_dn;
+    int bits, noise;
+    uint32_t seed_lo, seed_hi, frame;
+};
+hipError_t launch_sensor(const SensorArgs& a, bool mono, hipStream_t stream);
+
 // bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES).  What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
 // dsrt_scene_upload_bodies made resident beside them.  A movable ENTRY is a pair record of tri_pairs that holds triangles of a body >= 1; entries are sorted by body.
 struct BodiesView {

@@ -168,6 +168,7 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_COVERAGE_DESC: return sizeof(DsrtCoverageDesc);
         case DSRT_SIZEOF_COVERAGE: return sizeof(DsrtCoverage);
         case DSRT_SIZEOF_COVERAGE_CLASSES: return sizeof(DsrtCoverageClasses);
+        case DSRT_SIZEOF_SENSOR: return sizeof(DsrtSensor);
         default: return 0;
     }
 }

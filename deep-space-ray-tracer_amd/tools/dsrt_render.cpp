@@ -53,6 +53,17 @@
 //     guides (ALPHA_MIN: default the library's for this chain), the low-resolution frame is unmixed before the gather, and trusses thinner than a low-resolution pixel come out at the output resolution.  Writes
 //     <frame>, <frame>_lowres and <frame>_alpha.pfm (the output raster's alpha); --coverage then only chooses N and writes no files of its own.  The three flags
 //     --denoise --upscale --coverage-aware together stay a usage error: the low-resolution frame of this mode is the plain mean.
+//   * rng_mode 1 only: --sensor SPEC degrades each frame's LINEAR image into what a camera would have delivered (include/dsrt.h, SENSOR MODEL: dsrt_sensor_apply_to_host)
+//     and writes <frame>_raw.pgm (mono) or <frame>_raw.ppm, the raw DN frame with maxval 2^bits - 1 (two bytes per sample, most significant first, above 8 bits), and
+//     <frame>_sensor.png, its top eight bits.  SPEC is a comma list, every key optional, the rest the library's defaults:
+//       psf=gauss:SIGMA:SIZE | psf=FILE.pfm (one channel, odd square size up to 33)   gain=  read=  dark=  prnu=  dsnu=  well=  epdn=  offset=  bits=  mono  noise=0|1  seed=
+//     e.g. psf=gauss:1.2:9,gain=20000,read=12,dark=3,prnu=0.01,dsnu=2,well=20000,epdn=5,offset=64,bits=12,mono,seed=7.  A malformed SPEC is a usage error before any
+//     device is touched.  The linear image is the chosen chain's: the denoiser's (--denoise, with or without --temporal or --coverage-aware), the upscaler's
+//     (--upscale: the raw frame then has the output size), and without either the plain mean (dsrt_render_denoised_to_host with 0 iterations).  The detector's
+//     `frame` is the frame's index in the pose file, so in a sequence the fixed pattern (prnu, dsnu) stays put while the temporal noise changes.  With --denoise the
+//     undenoised image is then called <frame>_noisy: _raw is the detector's.  In rng_mode 0 the flag is announced and ignored, like --upscale.  Does not combine with
+//     --adaptive, --passes or --gbuffer.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +84,99 @@ static bool write_mask_pgm(const std::string& path, const std::vector<uint8_t>& 
     for (size_t i = 0; i < flags.size(); ++i) px[i] = (flags[i] & bit) ? 255 : 0;
     bool ok = std::fprintf(f, "P5\n%d %d\n255\n", width, height) > 0 && std::fwrite(px.data(), 1, px.size(), f) == px.size();
     return std::fclose(f) == 0 && ok;
+}
+
+// --sensor SPEC (include/dsrt.h, SENSOR MODEL): the library's defaults with the SPEC's keys applied, and the taps the psf key made.  Everything dsrt_sensor_apply
+// would refuse of the parameters is refused here already, with `why` saying what: the CLI then ends before a device context exists.
+struct SensorSpec { DsrtSensor p; std::vector<float> taps; };
+
+// A one-channel PFM ("Pf", rows bottom-up, a negative scale = little-endian) of odd square size as row-major taps, top row first.
+static bool read_psf_pfm(const std::string& path, std::vector<float>& taps, int& size, std::string& why) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) { why = "cannot open " + path; return false; }
+    std::string magic;
+    int w = 0, h = 0;
+    double scale = 0.0;
+    if (!(in >> magic >> w >> h >> scale) || magic != "Pf" || scale == 0.0) { why = path + " is not a one-channel PFM (Pf)"; return false; }
+    if (w != h || !(w & 1) || w < 1 || w > 33) { why = path + ": a PSF is square, of odd size between 1 and 33"; return false; }
+    in.get();                                                      // the single white-space byte after the scale
+    std::vector<uint8_t> bytes((size_t)w * h * 4);
+    if (!in.read((char*)bytes.data(), (std::streamsize)bytes.size())) { why = path + " is shorter than its header says"; return false; }
+    taps.resize((size_t)w * h);
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const uint8_t* b = bytes.data() + ((size_t)(h - 1 - y) * w + x) * 4;
+            const uint32_t u = scale < 0.0 ? (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24
+                                           : (uint32_t)b[3] | (uint32_t)b[2] << 8 | (uint32_t)b[1] << 16 | (uint32_t)b[0] << 24;
+            std::memcpy(&taps[(size_t)y * w + x], &u, 4);
+        }
+    size = w;
+    return true;
+}
+
+static bool parse_sensor_spec(const std::string& spec, SensorSpec& out, std::string& why) {
+    dsrt_sensor_defaults(&out.p);
+    auto number = [&](const std::string& key, const std::string& v, double& x) {
+        char* end = nullptr;
+        x = std::strtod(v.c_str(), &end);
+        if (v.empty() || *end) { why = key + " needs a number, not '" + v + "'"; return false; }
+        return true;
+    };
+    if (spec.empty()) { why = "an empty SPEC"; return false; }
+    size_t at = 0;
+    while (at <= spec.size()) {
+        const size_t comma = std::min(spec.find(',', at), spec.size());
+        const std::string item = spec.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eq = item.find('=');
+        const std::string key = item.substr(0, eq), v = eq == std::string::npos ? "" : item.substr(eq + 1);
+        double x = 0.0;
+        if (key == "mono" && eq == std::string::npos) out.p.mono = 1;
+        else if (eq == std::string::npos) { why = item.empty() ? "an empty item" : "'" + item + "' needs a value (key=value); known keys: psf gain read dark prnu dsnu well epdn offset bits mono noise seed"; return false; }
+        else if (key == "psf") {
+            int size = 0;
+            if (v.rfind("gauss:", 0) == 0) {
+                const size_t colon = v.find(':', 6);
+                double sigma = 0.0, n = 0.0;
+                if (colon == std::string::npos || !number("psf=gauss:SIGMA", v.substr(6, colon - 6), sigma) || !number("psf=gauss:SIGMA:SIZE", v.substr(colon + 1), n)) {
+                    if (why.empty()) why = "psf=gauss takes SIGMA:SIZE";
+                    return false;
+                }
+                size = (int)n;
+                if ((double)size != n || size < 1 || size > 33 || !(size & 1)) { why = "psf=gauss:SIGMA:SIZE needs an odd SIZE between 1 and 33"; return false; }
+                out.taps.resize((size_t)size * size);
+                if (dsrt_sensor_psf_gaussian((float)sigma, size, out.taps.data()) != DSRT_OK) { why = "psf=gauss:SIGMA:SIZE needs SIGMA > 0"; return false; }
+            } else if (!read_psf_pfm(v, out.taps, size, why)) return false;
+            for (float t : out.taps) if (!(t >= 0.0f) || !std::isfinite(t)) { why = "a PSF tap is negative or not finite"; return false; }
+            out.p.psf_size = size;
+        }
+        else if (key == "seed") {
+            char* end = nullptr;
+            out.p.seed = std::strtoull(v.c_str(), &end, 0);
+            if (v.empty() || *end || v[0] == '-') { why = "seed needs an unsigned integer, not '" + v + "'"; return false; }
+        }
+        else if (!number(key, v, x)) return false;
+        else if (key == "gain") out.p.gain_e = (float)x;
+        else if (key == "read") out.p.read_e = (float)x;
+        else if (key == "dark") out.p.dark_e = (float)x;
+        else if (key == "prnu") out.p.prnu = (float)x;
+        else if (key == "dsnu") out.p.dsnu_e = (float)x;
+        else if (key == "well") out.p.full_well_e = (float)x;
+        else if (key == "epdn") out.p.e_per_dn = (float)x;
+        else if (key == "offset") out.p.offset_dn = (float)x;
+        else if (key == "bits" || key == "mono" || key == "noise") {
+            if (x != std::floor(x) || std::fabs(x) > 64.0) { why = key + " needs a small integer"; return false; }
+            (key == "bits" ? out.p.bits : key == "mono" ? out.p.mono : out.p.noise) = (int)x;
+        }
+        else { why = "unknown key '" + key + "'; known keys: psf gain read dark prnu dsnu well epdn offset bits mono noise seed"; return false; }
+    }
+    const DsrtSensor& p = out.p;
+    if (!(p.gain_e > 0.0f) || !(p.e_per_dn > 0.0f) || !(p.full_well_e > 0.0f)) { why = "gain, epdn and well must be > 0"; return false; }
+    if (!(p.prnu >= 0.0f) || !(p.dark_e >= 0.0f) || !(p.dsnu_e >= 0.0f) || !(p.read_e >= 0.0f)) { why = "prnu, dark, dsnu and read must be >= 0"; return false; }
+    if (!std::isfinite(p.offset_dn)) { why = "offset must be finite"; return false; }
+    if (p.bits < 8 || p.bits > 16) { why = "bits must be between 8 and 16"; return false; }
+    if ((p.mono != 0 && p.mono != 1) || (p.noise != 0 && p.noise != 1)) { why = "mono and noise are 0 or 1"; return false; }
+    return true;
 }
 
 static int fail(const char* what) {
@@ -97,6 +201,8 @@ int main(int argc, char** argv) {
     std::vector<std::pair<std::string, double>> bodies;             // --body OBJ [--body-scale S], repeatable: movable rigid bodies 1, 2, ... (include/dsrt.h, MOVABLE RIGID BODIES)
     std::string body_poses_file;                                    // --body-poses FILE: one line per rendered frame, 12 numbers per body (row-major 3x4 [R | t], model frame)
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
+    bool sensor = false;
+    SensorSpec sensor_spec;                                         // --sensor SPEC (include/dsrt.h, SENSOR MODEL)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -160,7 +266,12 @@ int main(int argc, char** argv) {
             upscale = true;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') upscale_factor = std::atoi(argv[++i]);
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]]\n"); return 2; }
+        else if (a == "--sensor") {                                 // rng_mode 1: the detector model over each frame's linear image (include/dsrt.h, SENSOR MODEL)
+            std::string why;
+            if (!parse_sensor_spec(next("--sensor"), sensor_spec, why)) { std::fprintf(stderr, "dsrt_render: --sensor: %s\n", why.c_str()); return 2; }
+            sensor = true;
+        }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]] [--rng-mode 1 --sensor SPEC]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
@@ -172,6 +283,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "dsrt_render: --upscale is not supported (post-process outside this library)\n");
         upscale = false;
     }
+    if (sensor && rng_mode != 1) {                                  // the linear frame is rng_mode 1's: announced and ignored, like --upscale
+        std::fprintf(stderr, "dsrt_render: --sensor needs --rng-mode 1 (or --fast): ignored\n");
+        sensor = false;
+    }
+    if (sensor && (adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --sensor does not combine with --adaptive / --passes / --gbuffer\n"); return 2; }
+    if (sensor && spp < 2) { std::fprintf(stderr, "dsrt_render: --sensor needs --spp 2 or more\n"); return 2; }
     if (upscale && (upscale_factor < 2 || upscale_factor > 8)) { std::fprintf(stderr, "dsrt_render: --upscale S must be between 2 and 8\n"); return 2; }
     if (upscale && (temporal || adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --upscale does not combine with --temporal / --adaptive / --passes / --gbuffer\n"); return 2; }
     if (upscale && spp < 2) { std::fprintf(stderr, "dsrt_render: --upscale needs --spp 2 or more\n"); return 2; }
@@ -295,6 +412,12 @@ int main(int argc, char** argv) {
         return (png ? dsrt_write_png(path.c_str(), image, width, height) : dsrt_write_ppm(path.c_str(), image, width, height)) == DSRT_OK;
     };
 
+    // --sensor: every chain below also hands out its LINEAR image (at the upscaler's output size with --upscale), the detector's input.
+    const int sensor_w = upscale ? width * upscale_factor : width, sensor_h = upscale ? height * upscale_factor : height;
+    std::vector<float> sensor_linear(sensor ? (size_t)sensor_w * sensor_h * 3 : 0);
+    float* const lin = sensor ? sensor_linear.data() : nullptr;
+    const std::string undenoised = sensor ? "_noisy" : "_raw";     // (with --sensor, _raw is the detector's raw frame)
+
     // The modes that render frame by frame: one step each, over buffers that stay empty where the mode does not use them.
     const bool host_sums = !upscale && ((denoise && !temporal) || (!denoise && !adaptive && (passes != 0 || variance)));
     std::vector<uint8_t> img(image_bytes), raw(denoise && !upscale ? image_bytes : 0);
@@ -331,10 +454,10 @@ int main(int argc, char** argv) {
     dsrt_temporal_defaults(&tp);
     if (denoise && temporal) frame_step = [&](size_t q, const std::string& base) -> int {
         d.seed = 1337 + (uint64_t)ids[q];
-        if (dsrt_render_denoised_temporal_to_host(ctx, &d, &dn, &tp, q == 0 ? 1 : 0, img.data(), nullptr, nullptr, variance ? var.data() : nullptr,
+        if (dsrt_render_denoised_temporal_to_host(ctx, &d, &dn, &tp, q == 0 ? 1 : 0, img.data(), nullptr, lin, variance ? var.data() : nullptr,
                                                   flow ? prev_xy.data() : nullptr, nullptr) != DSRT_OK) return fail("rendering with temporal accumulation");
         if (dsrt_render_to_host(ctx, &d, raw.data(), nullptr, nullptr) != DSRT_OK) return fail("rendering the raw image");
-        if (!write_image(base + ext, img.data()) || !write_image(base + "_raw" + ext, raw.data())) return fail("writing the frame");
+        if (!write_image(base + ext, img.data()) || !write_image(base + undenoised + ext, raw.data())) return fail("writing the frame");
         if (!write_var(base)) return fail("writing the variance");
         if (flow) {
             for (size_t i = 0; i < px; ++i) {
@@ -344,8 +467,8 @@ int main(int argc, char** argv) {
             }
             if (dsrt_write_pfm((base + "_flow.pfm").c_str(), flow_px.data(), width, height, 3) != DSRT_OK) return fail("writing the flow");
         }
-        std::printf("denoise: %d iterations, temporal, seed %llu\nSaved %s, %s_raw%s%s%s\n", dn.iterations, (unsigned long long)d.seed, (base + ext).c_str(), base.c_str(),
-                    ext.c_str(), variance ? ", _var.pfm" : "", flow ? ", _flow.pfm" : "");
+        std::printf("denoise: %d iterations, temporal, seed %llu\nSaved %s, %s%s%s%s%s\n", dn.iterations, (unsigned long long)d.seed, (base + ext).c_str(), base.c_str(),
+                    undenoised.c_str(), ext.c_str(), variance ? ", _var.pfm" : "", flow ? ", _flow.pfm" : "");
         return 0;
     };
 
@@ -369,23 +492,23 @@ int main(int argc, char** argv) {
             std::memset(&cv, 0, sizeof cv);
             cv.alpha = alpha.data(); cv.rep = g;
             if (dsrt_render_coverage_to_host(ctx, &d, &cd, nullptr, &cv, nullptr) != DSRT_OK) return fail("rendering the coverage");
-            if (dsrt_denoise_accumulated_coverage_to_host(ctx, &d, &acc, spp, nullptr, &guides, alpha.data(), alpha_min, &dn, img.data(), nullptr, nullptr,
+            if (dsrt_denoise_accumulated_coverage_to_host(ctx, &d, &acc, spp, nullptr, &guides, alpha.data(), alpha_min, &dn, img.data(), nullptr, lin,
                                                           variance ? var.data() : nullptr) != DSRT_OK) return fail("denoising");
         } else {
         if (dsrt_render_gbuffer_to_host(ctx, &d, &g, nullptr) != DSRT_OK) return fail("rendering the G-buffer");
-        if (dsrt_denoise_accumulated_to_host(ctx, &d, &acc, spp, nullptr, &guides, &dn, img.data(), nullptr, nullptr, variance ? var.data() : nullptr) != DSRT_OK)
+        if (dsrt_denoise_accumulated_to_host(ctx, &d, &acc, spp, nullptr, &guides, &dn, img.data(), nullptr, lin, variance ? var.data() : nullptr) != DSRT_OK)
             return fail("denoising");
         }
-        if (!write_image(base + ext, img.data()) || !write_image(base + "_raw" + ext, raw.data())) return fail("writing the frame");
+        if (!write_image(base + ext, img.data()) || !write_image(base + undenoised + ext, raw.data())) return fail("writing the frame");
         if (!write_var(base)) return fail("writing the variance");
         if (coverage_aware) std::printf("coverage-aware: alpha_min %g\n", (double)alpha_min);
-        std::printf("denoise: %d iterations\nSaved %s, %s_raw%s%s\n", dn.iterations, (base + ext).c_str(), base.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
+        std::printf("denoise: %d iterations\nSaved %s, %s%s%s%s\n", dn.iterations, (base + ext).c_str(), base.c_str(), undenoised.c_str(), ext.c_str(), variance ? " and _var.pfm" : "");
         return 0;
     };
 
     // --passes / --variance: each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
     // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).
-    if (!adaptive && !denoise && !upscale && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
+    if (!adaptive && !denoise && !upscale && !sensor && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
         const int P = passes > 0 ? passes : 1;
         std::fill(sum.begin(), sum.end(), 0ull);
         std::fill(sq.begin(), sq.end(), 0ull);
@@ -424,7 +547,7 @@ int main(int argc, char** argv) {
     if (upscale_coverage && !alpha_min_given) alpha_min = dsrt_upscale_coverage_alpha_min();
     std::vector<float> big_alpha(upscale_coverage ? (size_t)out_w * out_h : 0);
     if (upscale_coverage) frame_step = [&](size_t, const std::string& base) -> int {
-        if (dsrt_render_upscaled_coverage_to_host(ctx, &d, out_w, out_h, &up_cov, &up_cov, alpha_min, nullptr, &up, big.data(), nullptr, nullptr,
+        if (dsrt_render_upscaled_coverage_to_host(ctx, &d, out_w, out_h, &up_cov, &up_cov, alpha_min, nullptr, &up, big.data(), nullptr, lin,
                                                   variance ? big_var.data() : nullptr, img.data(), big_alpha.data(), nullptr) != DSRT_OK) return fail("rendering and upscaling with coverage");
         const std::string path = base + ext;
         if ((png ? dsrt_write_png(path.c_str(), big.data(), out_w, out_h) : dsrt_write_ppm(path.c_str(), big.data(), out_w, out_h)) != DSRT_OK ||
@@ -436,7 +559,7 @@ int main(int argc, char** argv) {
         return 0;
     };
     else if (upscale) frame_step = [&](size_t, const std::string& base) -> int {
-        if (dsrt_render_upscaled_to_host(ctx, &d, out_w, out_h, denoise ? &dn : nullptr, &up, big.data(), nullptr, nullptr, variance ? big_var.data() : nullptr, img.data(),
+        if (dsrt_render_upscaled_to_host(ctx, &d, out_w, out_h, denoise ? &dn : nullptr, &up, big.data(), nullptr, lin, variance ? big_var.data() : nullptr, img.data(),
                                          nullptr) != DSRT_OK) return fail("rendering and upscaling");
         const std::string path = base + ext;
         if ((png ? dsrt_write_png(path.c_str(), big.data(), out_w, out_h) : dsrt_write_ppm(path.c_str(), big.data(), out_w, out_h)) != DSRT_OK ||
@@ -491,6 +614,36 @@ int main(int argc, char** argv) {
         return 0;
     };
 
+    // --sensor without --denoise or --upscale: the plain mean of the frame's samples as its linear image (the denoiser with 0 iterations); with --variance its variance.
+    DsrtDenoise dn_mean = dn;
+    dn_mean.iterations = 0;
+    if (sensor && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
+        DsrtStats st;
+        if (dsrt_render_denoised_to_host(ctx, &d, &dn_mean, img.data(), nullptr, lin, variance ? var.data() : nullptr, &st) != DSRT_OK) return fail("rendering the linear frame");
+        const std::string path = base + ext;
+        if (!write_image(path, img.data())) return fail("writing the frame");
+        if (!write_var(base)) return fail("writing the variance");
+        std::printf("kernel %.3f ms\nSaved %s%s\n", st.kernel_ms, path.c_str(), variance ? " and _var.pfm" : "");
+        return 0;
+    };
+    // --sensor: the detector over the linear image the frame's step left (include/dsrt.h, SENSOR MODEL); `frame` is the frame's index in the pose file
+    sensor_spec.p.psf = sensor_spec.taps.empty() ? nullptr : sensor_spec.taps.data();
+    const size_t sensor_px = (size_t)sensor_w * sensor_h, sensor_planes = sensor_spec.p.mono ? 1 : 3;
+    std::vector<uint16_t> sensor_dn(sensor ? sensor_px * sensor_planes : 0);
+    std::vector<uint8_t> sensor_rgb(sensor ? sensor_px * 3 : 0);
+    auto write_sensor = [&](size_t id, const std::string& base) -> int {
+        DsrtRenderDesc sd = d;
+        sd.width = sensor_w; sd.height = sensor_h;
+        sensor_spec.p.frame = (uint32_t)id;
+        if (dsrt_sensor_apply_to_host(ctx, &sd, lin, &sensor_spec.p, sensor_dn.data(), nullptr, sensor_rgb.data()) != DSRT_OK) return fail("applying the sensor model");
+        const std::string raw_path = base + (sensor_spec.p.mono ? "_raw.pgm" : "_raw.ppm");
+        if (dsrt_write_pnm16(raw_path.c_str(), sensor_dn.data(), sensor_w, sensor_h, (int)sensor_planes, (1 << sensor_spec.p.bits) - 1) != DSRT_OK ||
+            dsrt_write_png((base + "_sensor.png").c_str(), sensor_rgb.data(), sensor_w, sensor_h) != DSRT_OK) return fail("writing the raw frame");
+        std::printf("sensor: %d x %d, %d bits, %s, frame %u\nSaved %s, %s_sensor.png\n", sensor_w, sensor_h, sensor_spec.p.bits, sensor_spec.p.mono ? "mono" : "colour",
+                    sensor_spec.p.frame, raw_path.c_str(), base.c_str());
+        return 0;
+    };
+
     // --body: a batch launch has one scene and therefore one set of poses (include/dsrt.h), so a run with bodies renders one launch per frame
     if (!bodies.empty() && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
         DsrtStats st;
@@ -509,6 +662,7 @@ int main(int argc, char** argv) {
         }
         if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
         if (const int rc = frame_step(q, frame_base(ids[q]))) return rc;
+        if (sensor) if (const int rc = write_sensor(ids[q], frame_base(ids[q]))) return rc;
         if (coverage) if (const int rc = write_coverage(frame_base(ids[q]))) return rc;
     }
     size_t per_launch = 32;

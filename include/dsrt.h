@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host, DsrtSensor, dsrt_sensor_defaults, dsrt_sensor_psf_gaussian, dsrt_sensor_apply, dsrt_sensor_apply_to_host, dsrt_write_pnm16, DSRT_SIZEOF_SENSOR).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -63,6 +63,7 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_COVERAGE_DESC 20
 #define DSRT_SIZEOF_COVERAGE      21
 #define DSRT_SIZEOF_COVERAGE_CLASSES 22
+#define DSRT_SIZEOF_SENSOR        24   /* (23 is left unassigned and answers 0, like 17: tests/test_coverage_host.py holds it to that as the first unknown index of its day) */
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -1135,6 +1136,83 @@ int  dsrt_render_upscaled_coverage_to_host(DsrtContext* ctx, const DsrtRenderDes
                                            const DsrtCoverageDesc* cov_hi /* NULL = defaults */, float alpha_min, const DsrtDenoise* denoise /* NULL = iterations 0 */,
                                            const DsrtUpscale* params, uint8_t* h_rgb8, float* h_f32, float* h_linear, float* h_var, uint8_t* h_lo_rgb8 /* optional, w*h*3 */,
                                            float* h_alpha_hi /* optional, W*H */, DsrtStats* stats);
+
+/*
+ * SENSOR MODEL (after the DENOISER or the UPSCALER): the clean linear frame as a navigation camera would have delivered it -- optical blur, photon shot noise, read
+ * noise, fixed-pattern noise, full-well saturation and an ADC of 8 to 16 bits -- as a REPRODUCIBLE raw frame of DN (digital numbers, the ADC's output counts).  The
+ * degradation acts on linear signal, which is why it belongs here and not on the tone-mapped 8-bit image; and the noise is counter-based Philox keyed by pixel, plane
+ * and frame, so the same seed and frame index give the same DN on any GPU, under any launch shape, and in the CPU model: tests/_sensor_model.py reproduces every bit.
+ * A dataset can be regenerated, and a failure traced to a pixel.
+ * WHAT THE INPUT IS.  Every sample is clamped to [0, 1] before it is summed (the reference's src/gpu_render.cu:935), so the linear frame -- d_linear of the denoiser
+ * and the upscalers -- is an exposure-normalised signal, not radiance: 1.0 is "the exposure's white".  gain_e maps signal 1.0 to electrons (full well x exposure).
+ * Glare from a sunlit panel, blooming and anything else that needs radiance above white is therefore not representable.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written; sqrtf, / and floorf are the IEEE ones;
+ * fmaxf and fminf return the other operand when one is a NaN; the constants are float literals.
+ *   Let C = 1 (mono != 0) or 3, and r = (psf_size - 1) / 2.  For plane k (0 .. C-1) of pixel P = (x, y), y the buffer row, 0 the top row:
+ *   1. Input plane.  Colour: c_k is input channel k.  Mono: c = (0.2126f*r + 0.7152f*g) + 0.0722f*b of the input pixel -- the luminance is taken BEFORE the blur.
+ *   2. Blur, a true convolution: the image of a point source is the PSF itself, not its mirror image.
+ *        s = +0.0f;  for ky = -r .. r (outer), kx = -r .. r (inner): a tap with (x+kx, y+ky) outside the image is skipped (space is black); otherwise
+ *        s = s + psf[(r-ky)*psf_size + (r-kx)] * c(x+kx, y+ky)
+ *      One accumulator per plane; nothing is reassociated.  psf == NULL is psf_size = 1 with the tap 1.0f, bit for bit (so an input of -0.0f gives s = +0.0f).
+ *   3. Gaussian-like draws, one Philox4x32-10 block each (the generator of rng_mode 1): key = (seed's low word, seed's high word),
+ *        counter = (y*W + x,  k + 4*kind,  frame_word,  0x53454E53)
+ *      kind 0 is the temporal draw z0, with frame_word = frame; kind 1 is the PRNU draw z1 and kind 2 the DSNU draw z2, both with frame_word = 0: the fixed
+ *      pattern does not depend on `frame`.  With S the integer sum of the eight 16-bit halves of the block's four output words,
+ *        z = ((float)S - 262140.0f) * kInvSigma,      kInvSigma = 0x1.3988e2p-16f
+ *      the fp32 value nearest 1/sqrt(2863311530); 2863311530 = 8 (2^32 - 1) / 12 is the variance of S and 262140 = 8 x 65535 / 2 its mean.  This is an
+ *      Irwin-Hall sum of eight uniform terms: unit variance, excess kurtosis -0.15, tails cut at +-4.9 sigma.  (The library has no deterministic logf, and a
+ *      Box-Muller transform would need one.)  A draw whose coefficient is zero is NOT generated and counts as +0.0f: z1 when prnu == 0, z2 when dsnu_e == 0, z0
+ *      when noise == 0.
+ *   4. Electrons.
+ *        e  = s * gain_e
+ *        e  = e * (1.0f + prnu*z1)
+ *        d  = fmaxf(dark_e + dsnu_e*z2, 0.0f)
+ *        m  = fmaxf(e, 0.0f) + d
+ *        sg = sqrtf(m + read_e*read_e)                  -- shot noise of variance m and read noise, as one Gaussian
+ *        q  = fminf(m + sg*z0, full_well_e)
+ *   5. ADC.
+ *        v  = floorf((q / e_per_dn + offset_dn) + 0.5f)
+ *        DN = 0 when !(v >= 0) (a NaN included), 2^bits - 1 when v > 2^bits - 1, (uint16_t)v otherwise.
+ *   6. Outputs; at least one, and any subset gives the same bytes in each.
+ *        d_dn      W*H*C uint16_t, interleaved like the input (mono: one per pixel)
+ *        d_signal  W*H*C floats: the noise-free s of step 2, the blurred ground truth
+ *        d_rgb8    always W*H*3 bytes: DN >> (bits - 8); a mono plane is written three times
+ *
+ * dsrt_sensor_apply: desc gives width and height and nothing else; d_linear is W*H*3 floats.  Asynchronous on `stream`; like dsrt_upscale_guided it waits for the
+ *   context's previous launch, the next launch waits for it, it needs no scene, and the context's camera, sun and render buffers are left as they were.  The input is
+ *   read only.  The taps are copied into a device buffer that belongs to the context (grown on demand, freed by dsrt_ctx_destroy) before the call returns; a call
+ *   whose taps differ from the last call's waits on the host for the context's previous launch first, a call with the same taps uploads nothing.
+ *   DSRT_ERR_INVALID: a NULL ctx, desc, input or params; W or H < 2, 2^31 pixels; with a psf, psf_size even or outside [1, 33], or a tap that is negative or not
+ *   finite; gain_e, e_per_dn or full_well_e not > 0, prnu, dark_e, dsnu_e or read_e not >= 0 (NaN is refused by the same tests); offset_dn not finite; bits
+ *   outside [8, 16]; no output; a pointer not aligned to its element; an output range that overlaps the input or another output.  A refused call touches no buffer.
+ * dsrt_sensor_apply_to_host: the same from a HOST buffer into HOST buffers, synchronously.
+ * dsrt_sensor_defaults: psf NULL (psf_size 0), mono 0, gain_e 20000, prnu 0, dark_e 0, dsnu_e 0, read_e 10, full_well_e 20000, e_per_dn 5, offset_dn 64, bits 12,
+ *   noise 1, seed 1337, frame 0: white just fills the well, and the well just fills the 12-bit ADC above its offset.
+ * dsrt_sensor_psf_gaussian: a host helper.  taps[size*size], row-major: exp(-(kx^2 + ky^2) / (2 sigma^2)) in double, divided by the double sum of the taps taken in
+ *   row-major order, rounded to float.  A convenience: its bits are NOT part of the contract (exp is the C library's).  DSRT_ERR_INVALID: size even or outside
+ *   [1, 33], sigma not > 0 or not finite, NULL taps.
+ * dsrt_write_pnm16: a raw frame as a PNM file: P5 (channels 1) or P6 (channels 3), rows top-down, maxval = 2^bits - 1; two bytes per sample, most significant
+ *   first, when maxval > 255 (one byte otherwise: the format's own rule).
+ */
+typedef struct DsrtSensor {
+    const float* psf; int psf_size;   /* HOST pointer, psf_size x psf_size taps, row-major; psf_size odd, 1..33; NULL = no blur (psf_size is then ignored) */
+    int   mono;                       /* 0: three planes r,g,b   1: one plane, luminance taken BEFORE the blur */
+    float gain_e;                     /* electrons per unit of linear signal (full well x exposure) */
+    float prnu;                       /* relative sigma of the per-pixel gain, fixed pattern */
+    float dark_e, dsnu_e;             /* dark electrons per frame, and the sigma of their fixed pattern */
+    float read_e;                     /* read noise, electrons rms */
+    float full_well_e;                /* saturation, electrons */
+    float e_per_dn, offset_dn; int bits;   /* ADC: bits in [8, 16] */
+    int   noise;                      /* 0: the temporal draw z0 is +0 and no Philox word is generated for it */
+    uint64_t seed; uint32_t frame;
+} DsrtSensor;
+void dsrt_sensor_defaults(DsrtSensor* out);
+int  dsrt_sensor_psf_gaussian(float sigma, int size, float* taps);
+int  dsrt_sensor_apply(DsrtContext* ctx, const DsrtRenderDesc* desc /* width, height only */, const float* d_linear /* W*H*3 */, const DsrtSensor* params, uint16_t* d_dn,
+                       float* d_signal, uint8_t* d_rgb8, void* stream);
+int  dsrt_sensor_apply_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const float* h_linear, const DsrtSensor* params, uint16_t* h_dn, float* h_signal, uint8_t* h_rgb8);
+int  dsrt_write_pnm16(const char* path, const uint16_t* dn, int width, int height, int channels /* 1 = P5, 3 = P6 */, int maxval);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
