@@ -356,6 +356,26 @@ def write_pnm16(path, dn, bits):
     _check(lib.dsrt_write_pnm16(str(path).encode(), a.ctypes.data, int(a.shape[1]), int(a.shape[0]), int(ch), (1 << int(bits)) - 1), "dsrt_write_pnm16")
 
 
+def stars_from_catalog(ra_deg, dec_deg, mag, flux_mag0=(1.0, 1.0, 1.0)):
+    """dsrt_stars_from_catalog (include/dsrt.h, POINT SOURCES): a catalogue of right ascensions, declinations (degrees) and magnitudes as (dirs, flux) -- float64 (N, 3)
+    unit directions in the catalogue's frame (pose_to_model(pose, dirs, direction=True) brings them into the model frame) and float32 (N, 3) fluxes,
+    flux_mag0 * 10^(-0.4 mag) per channel."""
+    ra, dec, m = (np.ascontiguousarray(x, np.float64).reshape(-1) for x in (ra_deg, dec_deg, mag))
+    if not (ra.size == dec.size == m.size):
+        raise ValueError(f"stars_from_catalog: {ra.size} right ascensions, {dec.size} declinations, {m.size} magnitudes")
+    f0 = np.ascontiguousarray(flux_mag0, np.float32).reshape(3)
+    dirs, flux = np.zeros((ra.size, 3), np.float64), np.zeros((ra.size, 3), np.float32)
+    _check(lib.dsrt_stars_from_catalog(int(ra.size), ra.ctypes.data, dec.ctypes.data, m.ctypes.data, f0.ctypes.data, dirs.ctypes.data, flux.ctypes.data), "dsrt_stars_from_catalog")
+    return dirs, flux
+
+
+def synthetic_star_catalog(seed, count, mag_min=0.0, mag_max=6.5):
+    """dsrt_stars_synthetic_catalog: (ra_deg, dec_deg, mag), float64 (count,) each -- uniform on the sphere, magnitudes in [mag_min, mag_max] with N(< m) ~ 10^(0.5 m)."""
+    ra, dec, m = (np.zeros(int(count), np.float64) for _ in range(3))
+    _check(lib.dsrt_stars_synthetic_catalog(int(seed), int(count), float(mag_min), float(mag_max), ra.ctypes.data, dec.ctypes.data, m.ctypes.data), "dsrt_stars_synthetic_catalog")
+    return ra, dec, m
+
+
 def aligned_zeros(count, dtype=np.float32, align=64):
     """A zeroed numpy array of `count` elements whose data starts on an `align`-byte boundary (a host history buffer must be 16-byte aligned)."""
     raw = np.zeros(count * np.dtype(dtype).itemsize + align, np.uint8)
@@ -1194,6 +1214,44 @@ class Context:
         else:
             _check(lib.dsrt_sensor_apply_to_host(*head), "dsrt_sensor_apply_to_host")
         return out
+
+    # ---- the star field (include/dsrt.h, POINT SOURCES): occluded point sources in the linear frame ----
+    def render_stars(self, desc, dirs, flux, linear=None, occlusion=True, want=("layer", "xy", "status"), stream=None, want_stats=False):
+        """dsrt_render_stars (torch device tensors) or dsrt_render_stars_to_host (numpy arrays, chosen by dirs' type): the stars `dirs` (float32 (N, 3), model frame,
+        towards the star) of flux `flux` (float32 (N, 3)) through the context's camera and resident scene.  linear: the frame (float32, height*width*3) that
+        "linear_out" adds the layer to.  want: names of capi.STAR_OUTPUTS.  Returns {name: array}: layer and linear_out (height, width, 3) float32, xy (N, 2) float32,
+        status (N,) uint8.  With want_stats, returns (outputs, DsrtStats) and the call synchronises."""
+        names = list(want)
+        unknown = set(names) - set(capi.STAR_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown star output(s) {sorted(unknown)}; known: {list(capi.STAR_OUTPUTS)}")
+        on_device = _torch is not None and isinstance(dirs, _torch.Tensor)
+        n = int(dirs.shape[0])
+        px3 = desc.width * desc.height * 3
+        if on_device:
+            d = self._device_tensor(dirs, _torch.float32, (n * 3, f"N*3 = {n * 3}"), "dirs")
+            f = self._device_tensor(flux, _torch.float32, (n * 3, f"N*3 = {n * 3}"), "flux")
+            lin = self._device_tensor(linear, _torch.float32, (px3, f"width*height*3 = {px3}"), "linear", required=False)
+        else:
+            d, f = (np.ascontiguousarray(x, np.float32).reshape(n * 3) for x in (dirs, flux))
+            lin = None if linear is None else np.ascontiguousarray(linear, np.float32).reshape(px3)
+        out = {}
+        for k in names:
+            dt, per, comps = capi.STAR_OUTPUTS[k]
+            shape = (desc.height, desc.width, comps) if per == "pixel" else ((n, comps) if comps > 1 else (n,))
+            out[k] = _torch.empty(shape, dtype=getattr(_torch, np.dtype(dt).name), device=d.device) if on_device else np.zeros(shape, dt)
+        st = DsrtStats() if want_stats else None
+        if n == 0 and not any(capi.STAR_OUTPUTS[k][1] == "pixel" for k in names):      # per-star outputs of no stars: nothing to launch
+            return (out, st) if want_stats else out
+        ptr = _tensor_ptr if on_device else _array_ptr
+        stars = capi.DsrtStars(n, 1 if occlusion else 0, ptr(d) if n else None, ptr(f) if n else None, ptr(lin))
+        sout = capi.DsrtStarsOut(**{k: ptr(x) for k, x in out.items()})
+        head = (self._h, C.byref(desc), C.byref(stars), C.byref(sout))
+        if on_device:
+            _check(lib.dsrt_render_stars(*head, C.c_void_p(self._raw_stream(stream)), C.byref(st) if st is not None else None), "dsrt_render_stars")
+        else:
+            _check(lib.dsrt_render_stars_to_host(*head, C.byref(st) if st is not None else None), "dsrt_render_stars_to_host")
+        return (out, st) if want_stats else out
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

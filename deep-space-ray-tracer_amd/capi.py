@@ -164,6 +164,20 @@ class DsrtSensor(C.Structure):
                 ("seed", C.c_uint64), ("frame", C.c_uint32)]
 
 
+class DsrtStars(C.Structure):
+    _fields_ = [("count", C.c_int), ("occlusion", C.c_int), ("dir", C.c_void_p), ("flux", C.c_void_p), ("linear_in", C.c_void_p)]
+
+
+class DsrtStarsOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("layer", "linear_out", "xy", "status")]
+
+
+# The star field's outputs (include/dsrt.h, POINT SOURCES), in DsrtStarsOut's order: name -> (numpy dtype, per pixel or per star, components).
+STAR_OUTPUTS = {"layer": ("<f4", "pixel", 3), "linear_out": ("<f4", "pixel", 3), "xy": ("<f4", "star", 2), "status": ("u1", "star", 1)}
+STAR_PROJECTED, STAR_VISIBLE, STAR_INSIDE = 1, 2, 4                     # the bits of the status byte
+MAX_STARS = 1 << 22
+
+
 class DsrtCoverage(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("hits", "alpha", "mask", "sun_hits", "sun_alpha", "sun_mask", "class_hits")] + [("rep", DsrtGBuffer)]
 
@@ -215,6 +229,7 @@ EXPORTS = [
     "dsrt_denoise_accumulated_coverage_to_host", "dsrt_render_denoised_coverage_to_host",
     "dsrt_upscale_coverage_alpha_min", "dsrt_upscale_guided_coverage", "dsrt_upscale_guided_coverage_to_host", "dsrt_render_upscaled_coverage_to_host",
     "dsrt_sensor_defaults", "dsrt_sensor_psf_gaussian", "dsrt_sensor_apply", "dsrt_sensor_apply_to_host", "dsrt_write_pnm16",
+    "dsrt_render_stars", "dsrt_render_stars_to_host", "dsrt_stars_from_catalog", "dsrt_stars_synthetic_catalog",
     "dsrt_selftest_read_schedule", "dsrt_selftest_tile_order", "dsrt_selftest_tile_reorder", "dsrt_selftest_batch_table",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
@@ -363,6 +378,10 @@ def load():
     sig("dsrt_sensor_apply", C.c_int, [vp, P(DsrtRenderDesc), vp, P(DsrtSensor), vp, vp, vp, vp])
     sig("dsrt_sensor_apply_to_host", C.c_int, [vp, P(DsrtRenderDesc), vp, P(DsrtSensor), vp, vp, vp])
     sig("dsrt_write_pnm16", C.c_int, [C.c_char_p, vp, C.c_int, C.c_int, C.c_int, C.c_int])
+    sig("dsrt_render_stars", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtStars), P(DsrtStarsOut), vp, P(DsrtStats)])
+    sig("dsrt_render_stars_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtStars), P(DsrtStarsOut), P(DsrtStats)])
+    sig("dsrt_stars_from_catalog", C.c_int, [C.c_int, vp, vp, vp, vp, vp, vp])
+    sig("dsrt_stars_synthetic_catalog", C.c_int, [C.c_uint64, C.c_int, C.c_double, C.c_double, vp, vp, vp])
     sig("dsrt_host_scene_begin_body", C.c_int, [vp])
     sig("dsrt_host_scene_body_count", C.c_int, [vp])
     sig("dsrt_host_scene_body_range", C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int)])
@@ -392,7 +411,7 @@ def load():
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
     for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
-                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses, None, DsrtSensor)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
+                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses, None, DsrtSensor, None, DsrtStars, DsrtStarsOut)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
         if struct is not None and lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

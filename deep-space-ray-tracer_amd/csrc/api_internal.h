@@ -140,6 +140,9 @@ struct DsrtContext {
     dsrt::DevBuf<float4> up_rec[5];       // dsrt_upscale_guided[_coverage]: 5 records of 16 bytes per LOW-resolution pixel (launchers.h, UpscaleRecords)
     dsrt::DevBuf<float> sn_psf;           // dsrt_sensor_apply: the taps on the device, and what they hold now (a call with the same taps uploads nothing)
     std::vector<float> sn_psf_host;
+    dsrt::DevBuf<uint32_t> st_list, st_ctrl;          // dsrt_render_stars: the projected stars' indices; {the list's length, the status word}
+    dsrt::DevBuf<unsigned long long> st_acc;          // ... and the fixed-point frame the deposits are summed in, width*height*3
+    bool st_acc_clean = false;                        // every word of st_acc is zero: the resolve kernel puts back the zeros, so only a new or a doubtful buffer is cleared
     // dsrt_render_denoised_temporal_to_host: the sequence the context keeps -- two histories (tp_hist[tp_cur] holds the last frame's), that frame's camera and size
     dsrt::DevBuf<float4> tp_hist[2];
     GPUCamera tp_camera{};

@@ -138,6 +138,22 @@ struct SensorArgs {
 };
 hipError_t launch_sensor(const SensorArgs& a, bool mono, hipStream_t stream);
 
+// stars_kernel.hip (include/dsrt.h, POINT SOURCES).  dir / flux: count x 3 floats; cam: the context's GPUCamera's origin, lower_left_corner, horizontal, vertical,
+// u, v, w; list (count words) and list_len (one word, zero at launch): the projected stars' indices; acc: W*H*3 sums, zero at launch and zero again after it, null when neither layer nor
+// linear_out is asked for (nothing is deposited or resolved then); the outputs that are not null are written; status: the walk's kFlag* bits.
+struct StarsArgs {
+    DeviceScene scene;
+    const float* dir; const float* flux; const float* linear_in;
+    int count, width, height, occlusion;
+    int stack_entries;         // LDS stack entries per lane the launch provides (>= the tree's stack_need)
+    float cam[21];
+    uint32_t* list; uint32_t* list_len;
+    unsigned long long* acc;
+    float* layer; float* linear_out; float* xy; uint8_t* star_status;
+    uint32_t* status;
+};
+hipError_t launch_stars(const StarsArgs& a, hipStream_t stream);             // project, deposit, resolve: three launches in stream order
+
 // bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES).  What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
 // dsrt_scene_upload_bodies made resident beside them.  A movable ENTRY is a pair record of tri_pairs that holds triangles of a body >= 1; entries are sorted by body.
 struct BodiesView {

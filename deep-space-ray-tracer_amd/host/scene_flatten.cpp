@@ -169,6 +169,8 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_COVERAGE: return sizeof(DsrtCoverage);
         case DSRT_SIZEOF_COVERAGE_CLASSES: return sizeof(DsrtCoverageClasses);
         case DSRT_SIZEOF_SENSOR: return sizeof(DsrtSensor);
+        case DSRT_SIZEOF_STARS: return sizeof(DsrtStars);
+        case DSRT_SIZEOF_STARS_OUT: return sizeof(DsrtStarsOut);
         default: return 0;
     }
 }

@@ -63,6 +63,13 @@
 //     `frame` is the frame's index in the pose file, so in a sequence the fixed pattern (prnu, dsnu) stays put while the temporal noise changes.  With --denoise the
 //     undenoised image is then called <frame>_noisy: _raw is the detector's.  In rng_mode 0 the flag is announced and ignored, like --upscale.  Does not combine with
 //     --adaptive, --passes or --gbuffer.
+//   * rng_mode 1 only: --stars FILE[,flux=F][,occlusion=0] adds a star field to each frame's LINEAR image (include/dsrt.h, POINT SOURCES: dsrt_render_stars_to_host).
+//     FILE holds one `ra_deg dec_deg mag` per line (blank lines and lines that begin with # are skipped); a star's flux is F * 10^(-0.4 mag) in all three channels
+//     (F: default 1, linear signal x pixel of a magnitude-0 star); occlusion=0 draws the stars through the scene.  Per frame the catalogue's directions go through
+//     that frame's pose (dsrt_pose_dirs_to_model), and the layer is added to the chain's linear image -- after the denoiser or the upscaler, at the output size, and
+//     before --sensor, whose raw frame then contains the stars.  Writes <frame>_stars.pfm (the layer) and <frame>_stars.txt (per star: index, fx, fy, status);
+//     without --sensor nothing else changes.  A malformed spec or catalogue is a usage error before any device is touched.  In rng_mode 0 the flag is announced and
+//     ignored, like --sensor; it refuses the combinations --sensor refuses.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -111,6 +118,51 @@ static bool read_psf_pfm(const std::string& path, std::vector<float>& taps, int&
             std::memcpy(&taps[(size_t)y * w + x], &u, 4);
         }
     size = w;
+    return true;
+}
+
+// --stars FILE[,flux=F][,occlusion=0] (include/dsrt.h, POINT SOURCES): the catalogue as world directions and fluxes.
+struct StarsSpec { std::vector<double> world_dirs; std::vector<float> flux; int occlusion = 1; };
+
+static bool parse_stars_spec(const std::string& spec, StarsSpec& out, std::string& why) {
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t comma = spec.find(',', at);
+        parts.push_back(spec.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+    }
+    if (parts[0].empty()) { why = "FILE[,flux=F][,occlusion=0|1]: no FILE"; return false; }
+    double flux0 = 1.0;
+    for (size_t k = 1; k < parts.size(); ++k) {
+        const size_t eq = parts[k].find('=');
+        const std::string key = parts[k].substr(0, eq), v = eq == std::string::npos ? "" : parts[k].substr(eq + 1);
+        char* end = nullptr;
+        const double x = std::strtod(v.c_str(), &end);
+        if (v.empty() || *end) { why = "`" + parts[k] + "` is not key=number"; return false; }
+        if (key == "flux") { if (!(x >= 0.0) || !std::isfinite(x)) { why = "flux must be >= 0 and finite"; return false; } flux0 = x; }
+        else if (key == "occlusion") { if (x != 0.0 && x != 1.0) { why = "occlusion is 0 or 1"; return false; } out.occlusion = (int)x; }
+        else { why = "unknown key `" + key + "` (flux, occlusion)"; return false; }
+    }
+    std::ifstream in(parts[0]);
+    if (!in) { why = "cannot open " + parts[0]; return false; }
+    std::vector<double> ra, dec, mag;
+    std::string line;
+    while (std::getline(in, line)) {
+        const size_t start = line.find_first_not_of(" \t\r");
+        if (start == std::string::npos || line[start] == '#') continue;
+        std::istringstream is(line);
+        double a, d, m;
+        std::string rest;
+        if (!(is >> a >> d >> m) || (is >> rest) || !std::isfinite(a) || !std::isfinite(d) || !std::isfinite(m)) {
+            why = parts[0] + ": line " + std::to_string(ra.size() + 1) + " of the catalogue is not `ra_deg dec_deg mag`"; return false;
+        }
+        ra.push_back(a); dec.push_back(d); mag.push_back(m);
+    }
+    if (ra.size() > ((size_t)1 << 22)) { why = parts[0] + " holds more than 2^22 stars"; return false; }
+    const float f3[3] = {(float)flux0, (float)flux0, (float)flux0};
+    out.world_dirs.resize(ra.size() * 3); out.flux.resize(ra.size() * 3);
+    if (dsrt_stars_from_catalog((int)ra.size(), ra.data(), dec.data(), mag.data(), f3, out.world_dirs.data(), out.flux.data()) != DSRT_OK) { why = dsrt_last_error(); return false; }
     return true;
 }
 
@@ -203,6 +255,8 @@ int main(int argc, char** argv) {
     bool sah = false, lbvh = false, png = false, strict_textures = false, certified = false, gbuffer = false, variance = false;
     bool sensor = false;
     SensorSpec sensor_spec;                                         // --sensor SPEC (include/dsrt.h, SENSOR MODEL)
+    bool stars = false;
+    StarsSpec stars_spec;                                           // --stars FILE[,flux=F][,occlusion=0] (include/dsrt.h, POINT SOURCES)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -271,7 +325,12 @@ int main(int argc, char** argv) {
             if (!parse_sensor_spec(next("--sensor"), sensor_spec, why)) { std::fprintf(stderr, "dsrt_render: --sensor: %s\n", why.c_str()); return 2; }
             sensor = true;
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]] [--rng-mode 1 --sensor SPEC]\n"); return 2; }
+        else if (a == "--stars") {                                  // rng_mode 1: a star field added to each frame's linear image (include/dsrt.h, POINT SOURCES)
+            std::string why;
+            if (!parse_stars_spec(next("--stars"), stars_spec, why)) { std::fprintf(stderr, "dsrt_render: --stars: %s\n", why.c_str()); return 2; }
+            stars = true;
+        }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]] [--rng-mode 1 --sensor SPEC] [--rng-mode 1 --stars FILE[,flux=F][,occlusion=0]]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
@@ -287,6 +346,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "dsrt_render: --sensor needs --rng-mode 1 (or --fast): ignored\n");
         sensor = false;
     }
+    if (stars && rng_mode != 1) {                                   // announced and ignored, like --sensor
+        std::fprintf(stderr, "dsrt_render: --stars needs --rng-mode 1 (or --fast): ignored\n");
+        stars = false;
+    }
+    if (stars && (adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --stars does not combine with --adaptive / --passes / --gbuffer\n"); return 2; }
+    if (stars && spp < 2) { std::fprintf(stderr, "dsrt_render: --stars needs --spp 2 or more\n"); return 2; }
     if (sensor && (adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --sensor does not combine with --adaptive / --passes / --gbuffer\n"); return 2; }
     if (sensor && spp < 2) { std::fprintf(stderr, "dsrt_render: --sensor needs --spp 2 or more\n"); return 2; }
     if (upscale && (upscale_factor < 2 || upscale_factor > 8)) { std::fprintf(stderr, "dsrt_render: --upscale S must be between 2 and 8\n"); return 2; }
@@ -412,10 +477,11 @@ int main(int argc, char** argv) {
         return (png ? dsrt_write_png(path.c_str(), image, width, height) : dsrt_write_ppm(path.c_str(), image, width, height)) == DSRT_OK;
     };
 
-    // --sensor: every chain below also hands out its LINEAR image (at the upscaler's output size with --upscale), the detector's input.
+    // --sensor, --stars: every chain below also hands out its LINEAR image (at the upscaler's output size with --upscale), the star field's and the detector's input.
+    const bool wants_linear = sensor || stars;
     const int sensor_w = upscale ? width * upscale_factor : width, sensor_h = upscale ? height * upscale_factor : height;
-    std::vector<float> sensor_linear(sensor ? (size_t)sensor_w * sensor_h * 3 : 0);
-    float* const lin = sensor ? sensor_linear.data() : nullptr;
+    std::vector<float> sensor_linear(wants_linear ? (size_t)sensor_w * sensor_h * 3 : 0);
+    float* const lin = wants_linear ? sensor_linear.data() : nullptr;
     const std::string undenoised = sensor ? "_noisy" : "_raw";     // (with --sensor, _raw is the detector's raw frame)
 
     // The modes that render frame by frame: one step each, over buffers that stay empty where the mode does not use them.
@@ -508,7 +574,7 @@ int main(int argc, char** argv) {
 
     // --passes / --variance: each frame as P interleaved sample sets (first = p, stride = P) added into one pair of sums: after pass p every pixel holds samples from
     // its whole area, and after the last the image is the one-launch image byte for byte (include/dsrt.h, SAMPLE SETS).
-    if (!adaptive && !denoise && !upscale && !sensor && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
+    if (!adaptive && !denoise && !upscale && !wants_linear && (passes != 0 || variance)) frame_step = [&](size_t, const std::string& base) -> int {
         const int P = passes > 0 ? passes : 1;
         std::fill(sum.begin(), sum.end(), 0ull);
         std::fill(sq.begin(), sq.end(), 0ull);
@@ -614,16 +680,43 @@ int main(int argc, char** argv) {
         return 0;
     };
 
-    // --sensor without --denoise or --upscale: the plain mean of the frame's samples as its linear image (the denoiser with 0 iterations); with --variance its variance.
+    // --sensor or --stars without --denoise or --upscale: the plain mean of the frame's samples as its linear image (the denoiser with 0 iterations); with --variance its variance.
     DsrtDenoise dn_mean = dn;
     dn_mean.iterations = 0;
-    if (sensor && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
+    if (wants_linear && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
         DsrtStats st;
         if (dsrt_render_denoised_to_host(ctx, &d, &dn_mean, img.data(), nullptr, lin, variance ? var.data() : nullptr, &st) != DSRT_OK) return fail("rendering the linear frame");
         const std::string path = base + ext;
         if (!write_image(path, img.data())) return fail("writing the frame");
         if (!write_var(base)) return fail("writing the variance");
         std::printf("kernel %.3f ms\nSaved %s%s\n", st.kernel_ms, path.c_str(), variance ? " and _var.pfm" : "");
+        return 0;
+    };
+    // --stars: the star field added to the linear image the frame's step left (include/dsrt.h, POINT SOURCES), the catalogue through the frame's pose
+    const size_t n_stars = stars_spec.flux.size() / 3;
+    std::vector<float> star_dirs(stars ? n_stars * 3 : 0), star_xy(stars ? n_stars * 2 : 0), star_layer(stars ? sensor_linear.size() : 0), star_sum(star_layer.size());
+    std::vector<uint8_t> star_status(stars ? n_stars : 0);
+    auto write_stars = [&](size_t id, const std::string& base) -> int {
+        DsrtRenderDesc sd = d;
+        sd.width = sensor_w; sd.height = sensor_h;
+        if (n_stars && dsrt_pose_dirs_to_model(&poses[id], (int)n_stars, stars_spec.world_dirs.data(), star_dirs.data()) != DSRT_OK) return fail("bringing the stars into the model frame");
+        DsrtStars in;
+        std::memset(&in, 0, sizeof in);
+        in.count = (int)n_stars; in.occlusion = stars_spec.occlusion; in.dir = star_dirs.data(); in.flux = stars_spec.flux.data(); in.linear_in = lin;
+        const DsrtStarsOut out{star_layer.data(), star_sum.data(), n_stars ? star_xy.data() : nullptr, n_stars ? star_status.data() : nullptr};
+        if (dsrt_render_stars_to_host(ctx, &sd, &in, &out, nullptr) != DSRT_OK) return fail("rendering the star field");
+        sensor_linear = star_sum;                                   // what --sensor sees
+        if (dsrt_write_pfm((base + "_stars.pfm").c_str(), star_layer.data(), sensor_w, sensor_h, 3) != DSRT_OK) return fail("writing the star layer");
+        FILE* f = std::fopen((base + "_stars.txt").c_str(), "w");
+        if (!f) { std::fprintf(stderr, "dsrt_render: cannot write %s_stars.txt\n", base.c_str()); return 1; }
+        size_t visible = 0;
+        for (size_t i = 0; i < n_stars; ++i) {
+            std::fprintf(f, "%zu %.9g %.9g %u\n", i, (double)star_xy[2 * i], (double)star_xy[2 * i + 1], (unsigned)star_status[i]);
+            visible += (star_status[i] >> 1) & 1u;
+        }
+        if (std::fclose(f) != 0) { std::fprintf(stderr, "dsrt_render: short write to %s_stars.txt\n", base.c_str()); return 1; }
+        std::printf("stars: %zu of %zu visible at %d x %d%s\nSaved %s_stars.pfm, %s_stars.txt\n", visible, n_stars, sensor_w, sensor_h, stars_spec.occlusion ? "" : ", occlusion off",
+                    base.c_str(), base.c_str());
         return 0;
     };
     // --sensor: the detector over the linear image the frame's step left (include/dsrt.h, SENSOR MODEL); `frame` is the frame's index in the pose file
@@ -662,6 +755,7 @@ int main(int argc, char** argv) {
         }
         if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
         if (const int rc = frame_step(q, frame_base(ids[q]))) return rc;
+        if (stars) if (const int rc = write_stars(ids[q], frame_base(ids[q]))) return rc;
         if (sensor) if (const int rc = write_sensor(ids[q], frame_base(ids[q]))) return rc;
         if (coverage) if (const int rc = write_coverage(frame_base(ids[q]))) return rc;
     }

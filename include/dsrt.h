@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host, DsrtSensor, dsrt_sensor_defaults, dsrt_sensor_psf_gaussian, dsrt_sensor_apply, dsrt_sensor_apply_to_host, dsrt_write_pnm16, DSRT_SIZEOF_SENSOR).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host, DsrtSensor, dsrt_sensor_defaults, dsrt_sensor_psf_gaussian, dsrt_sensor_apply, dsrt_sensor_apply_to_host, dsrt_write_pnm16, DSRT_SIZEOF_SENSOR, DsrtStars, DsrtStarsOut, dsrt_render_stars, dsrt_render_stars_to_host, dsrt_stars_from_catalog, dsrt_stars_synthetic_catalog, DSRT_SIZEOF_STARS, DSRT_SIZEOF_STARS_OUT).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -64,6 +64,8 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_COVERAGE      21
 #define DSRT_SIZEOF_COVERAGE_CLASSES 22
 #define DSRT_SIZEOF_SENSOR        24   /* (23 is left unassigned and answers 0, like 17: tests/test_coverage_host.py holds it to that as the first unknown index of its day) */
+#define DSRT_SIZEOF_STARS         26   /* (25 is left unassigned and answers 0, like 17 and 23: tests/test_sensor_host.py holds it to that) */
+#define DSRT_SIZEOF_STARS_OUT     27
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -1213,6 +1215,68 @@ int  dsrt_sensor_apply(DsrtContext* ctx, const DsrtRenderDesc* desc /* width, he
                        float* d_signal, uint8_t* d_rgb8, void* stream);
 int  dsrt_sensor_apply_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const float* h_linear, const DsrtSensor* params, uint16_t* h_dn, float* h_signal, uint8_t* h_rgb8);
 int  dsrt_write_pnm16(const char* path, const uint16_t* dn, int width, int height, int channels /* 1 = P5, 3 = P6 */, int maxval);
+
+/*
+ * POINT SOURCES (before the SENSOR MODEL): a star field in the linear frame.  The renderer's sky is exactly black; a navigation camera's is not: stars are what a
+ * star tracker and an attitude filter work on, they appear and vanish behind trusses and visiting vehicles, and they are the natural input of the sensor model's PSF.
+ * This pass projects a catalogue of directions through the context's camera, tests each star against the resident scene, and deposits its flux into the frame with
+ * bilinear weights; per star it returns the sub-pixel centroid and the visibility, which are the labels of a star-identification or attitude data set.  Like every
+ * output of this library the result is REPRODUCIBLE: deposits are summed as integers, so the frame does not depend on the order of the stars or of the additions
+ * (a float atomicAdd splat differs in its last bits from run to run), and tests/_stars_model.py reproduces every bit.
+ *
+ * INPUTS.  count stars, 0 <= count <= 2^22.  dir: count x 3 floats, directions in the MODEL frame towards the star (dsrt_pose_dirs_to_model takes inertial
+ * directions there); they need not be unit vectors.  flux: count x 3 floats, linear signal x pixel, r g b: the total a star adds to the frame, in the units of the
+ * linear frame.  The camera C is the context's current one and the scene the resident one, as for dsrt_render_gbuffer; W = desc->width, H = desc->height.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order written; fmaxf and fminf return the other operand
+ * when one is a NaN; the constants are float literals.  Per star i, with D = dir_i:
+ *   1. Projection: TEMPORAL ACCUMULATION's, verbatim, with D in place of X_p - C.origin -- a, b, cc, eu, ev, ew, hu, vv, k, s, t, fx, fy and its two "not
+ *      projected" rules, !(k > 0) and the window (-1, W) x (-1, H) with both borders excluded.  A zero, NaN or infinite D falls out as not projected by those same tests and needs
+ *      no rule of its own: D = 0 gives cc = 0 and k = ew / 0, which is -inf or NaN and fails k > 0, or +inf, and then a*k = 0 * inf is a NaN that reaches fx; a NaN
+ *      in D reaches k, fx or fy; an infinite D gives a k that is NaN or zero, or products inf * 0 and sums inf - inf that are NaN -- and a NaN fx or fy fails the
+ *      window.  A star behind the camera has cc >= 0 (ew is negative for every camera of dsrt_camera_look_at) and fails k > 0.
+ *   2. Occlusion, when occlusion != 0, for projected stars only: blocked = the boolean of scene_hit(ray(C.origin, D), 0.001f, 1e9f) in its any-hit form on the
+ *      REFERENCE tree -- exactly what dsrt_trace_rays answers in mode DSRT_TRACE_ANY for that ray, spheres and posed bodies included.
+ *      visible = projected && !blocked; with occlusion == 0, visible = projected.
+ *   3. Deposit, for visible stars: x0, y0, wx, wy, ox, oy, the four taps, their order and their weights bq are TEMPORAL ACCUMULATION's.  A tap outside the image is
+ *      skipped: flux falls off the edge.  For each tap inside the image and each channel k:
+ *        d = flux_k * bq;   q = fminf(fmaxf(d * 16777216.0f, 0.0f), 1099511627776.0f);   n = (uint64_t)q  (truncation);   A[pixel][k] += n
+ *      A is an integer sum of quanta of 2^-24, hence independent of every order; with count <= 2^22 and a star touching a pixel at most once, A < 2^62.  Negative,
+ *      NaN and sub-quantum deposits are 0; a deposit above 2^16 (q above 2^40) counts as 2^16.
+ *   4. Resolve, per pixel and channel: layer = (float)A * 0x1p-24f -- the conversion rounds to nearest, ties to even; the scaling is exact -- and
+ *      out = linear_in + layer.  A pixel no star touched has layer = +0.0f, so an input of -0.0f comes out as +0.0f.
+ *   Outputs; each optional, at least one, and any subset gives the same bytes in each:
+ *        layer        W*H*3 floats
+ *        linear_out   W*H*3 floats; needs linear_in (W*H*3 floats, read only)
+ *        xy           count x 2 floats: (fx, fy) when projected -- blocked or not -- else (+0, +0)
+ *        status       count bytes: bit 0 projected, bit 1 visible, bit 2 projected and all four taps inside the image (x0 >= 0, x0+1 < W, y0 >= 0, y0+1 < H)
+ *
+ * dsrt_render_stars: desc gives width and height and nothing else.  It behaves as dsrt_render_gbuffer does: asynchronous on `stream` unless `stats` is given (then it
+ *   waits, and kernel_ms is the pass's time); it waits for the context's previous launch and the next launch waits for it; camera, sun, scene and render buffers are
+ *   left as they were; DSRT_ERR_NO_SCENE before an upload.  Working memory belongs to the context (grown on demand, freed by dsrt_ctx_destroy): count words for the
+ *   list of projected stars, and -- only when layer or linear_out is asked for -- the accumulator A, W*H*3 uint64_t: 50 MB at 1920 x 1080, 200 MB at 3840 x 2160.
+ *   It is cleared when it is allocated, and every call's resolve pass hands it back all zeros.  count == 0 is legal: the layer is zero and out = in + 0.
+ *   DSRT_ERR_INVALID: a NULL ctx, desc, stars or out; W or H < 2, 2^31 pixels; count outside [0, 2^22]; a NULL dir or flux with count > 0; no output; linear_out
+ *   without linear_in; a float pointer not 4-byte aligned; an output range that overlaps an input or another output.  A refused call touches no buffer.
+ * dsrt_render_stars_to_host: the same from HOST buffers into HOST buffers, synchronously.
+ * dsrt_stars_from_catalog: a host helper.  dir = (cos dec cos ra, cos dec sin ra, sin dec) as doubles in the frame the catalogue is given in -- the caller brings
+ *   them into the model frame with dsrt_pose_dirs_to_model -- and flux = flux_mag0 * 10^(-0.4 mag) per channel, rounded to float.  Its bits are NOT part of the
+ *   contract (sin, cos and pow are the C library's).  DSRT_ERR_INVALID: n < 0, a NULL array.
+ * dsrt_stars_synthetic_catalog: n stars uniform on the sphere from a splitmix64 stream of `seed`, magnitudes in [mag_min, mag_max] with the sky's rough count law
+ *   N(< m) ~ 10^(0.5 m).  A stand-in for a real catalogue; its bits are not part of the contract either.  DSRT_ERR_INVALID: n < 0, mag_min > mag_max or not finite, a NULL array.
+ */
+typedef struct DsrtStars {
+    int count;                        /* 0 .. 2^22 */
+    int occlusion;                    /* 0: every projected star is visible */
+    const float* dir;                 /* count x 3, model frame, towards the star */
+    const float* flux;                /* count x 3, r g b */
+    const float* linear_in;           /* W*H*3, or NULL when linear_out is not asked for */
+} DsrtStars;
+typedef struct DsrtStarsOut { float* layer; float* linear_out; float* xy; uint8_t* status; } DsrtStarsOut;
+int  dsrt_render_stars(DsrtContext* ctx, const DsrtRenderDesc* desc /* width, height only */, const DsrtStars* stars, const DsrtStarsOut* out, void* stream, DsrtStats* stats);
+int  dsrt_render_stars_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtStars* h_stars, const DsrtStarsOut* h_out, DsrtStats* stats);
+int  dsrt_stars_from_catalog(int n, const double* ra_deg, const double* dec_deg, const double* mag, const float flux_mag0[3], double* world_dirs /* n x 3 */, float* flux /* n x 3 */);
+int  dsrt_stars_synthetic_catalog(uint64_t seed, int n, double mag_min, double mag_max, double* ra_deg, double* dec_deg, double* mag);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
