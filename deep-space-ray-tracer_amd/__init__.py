@@ -376,6 +376,28 @@ def synthetic_star_catalog(seed, count, mag_min=0.0, mag_max=6.5):
     return ra, dec, m
 
 
+def lens_defaults(**changes):
+    """dsrt_lens_defaults (include/dsrt.h, LENS MODEL): the DsrtLens the library fills -- filter 2 (Catmull-Rom), channels 3, clamp_zero 1, everything else 0 -- with
+    `changes` applied.  The caller sets the two frames: src_width, src_height, src_fx .. src_cy and fx .. cy (lens_intrinsics_from_camera gives the library's own)."""
+    return _defaults(capi.DsrtLens, lib.dsrt_lens_defaults, changes)
+
+
+def lens_distort_points(params, xy):
+    """dsrt_lens_distort_points: positions `xy` (N, 2) in the SOURCE frame, in pixels -- star centroids, prev_xy, keypoints -- through the forward model of `params`
+    (a DsrtLens) into the distorted frame.  Returns (xy_out float32 (N, 2), ok uint8 (N,)); a point that is not finite has ok 0 and comes out as (0, 0)."""
+    src = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out, ok = np.zeros_like(src), np.zeros(len(src), np.uint8)
+    _check(lib.dsrt_lens_distort_points(C.byref(params), len(src), src.ctypes.data, out.ctypes.data, ok.ctypes.data), "dsrt_lens_distort_points")
+    return out, ok
+
+
+def lens_intrinsics_from_camera(cam, width, height):
+    """dsrt_lens_intrinsics_from_camera: (fx, fy, cx, cy) of the library's own pinhole for the GPUCamera `cam` at width x height, as Python floats (float32 values)."""
+    out = np.zeros(4, np.float32)
+    _check(lib.dsrt_lens_intrinsics_from_camera(C.byref(cam), int(width), int(height), out.ctypes.data), "dsrt_lens_intrinsics_from_camera")
+    return tuple(float(v) for v in out)
+
+
 def aligned_zeros(count, dtype=np.float32, align=64):
     """A zeroed numpy array of `count` elements whose data starts on an `align`-byte boundary (a host history buffer must be 16-byte aligned)."""
     raw = np.zeros(count * np.dtype(dtype).itemsize + align, np.uint8)
@@ -1252,6 +1274,49 @@ class Context:
         else:
             _check(lib.dsrt_render_stars_to_host(*head, C.byref(st) if st is not None else None), "dsrt_render_stars_to_host")
         return (out, st) if want_stats else out
+
+    # ---- the lens model (include/dsrt.h, LENS MODEL): distortion and vignetting on the linear frame, and on its labels ----
+    def lens_apply(self, desc, src, params, want=("image", "src_xy", "status"), stream=None):
+        """dsrt_lens_apply (a torch device tensor) or dsrt_lens_apply_to_host (a numpy array, chosen by src's type): the pinhole frame `src` -- params.src_height *
+        params.src_width * params.channels 32-bit elements: float32 for filters 1 and 2; float32, int32 or uint32 for nearest, which copies words -- through the lens
+        `params` (a DsrtLens: lens_defaults(...)) into the frame of desc.width x desc.height.  want: names among image, src_xy, status.  Returns {name: array}: image
+        (height, width, channels) of src's dtype -- (height, width) for one channel -- src_xy (height, width, 2) float32, status (height, width) uint8."""
+        names = list(want)
+        unknown = set(names) - {"image", "src_xy", "status"}
+        if unknown:
+            raise ValueError(f"unknown lens output(s) {sorted(unknown)}; known: image, src_xy, status")
+        on_device = _torch is not None and isinstance(src, _torch.Tensor)
+        ch = int(params.channels)
+        n = params.src_width * params.src_height * ch
+        words = ("float32",) if params.filter != capi.LENS_NEAREST else ("float32", "int32", "uint32")
+        if on_device:
+            kinds = [getattr(_torch, w) for w in words if hasattr(_torch, w)]
+            if src.dtype not in kinds:
+                raise TypeError(f"src must be one of {words} for filter {params.filter}, not {src.dtype}")
+            s = self._device_tensor(src, src.dtype, (n, f"src_width*src_height*channels = {n}"), "src")
+        else:
+            s = np.ascontiguousarray(src)
+            if s.dtype.name not in words:
+                raise TypeError(f"src must be one of {words} for filter {params.filter}, not {s.dtype}")
+            if s.size != n:
+                raise ValueError(f"src has {s.size} elements, not src_width*src_height*channels = {n}")
+        H, W = desc.height, desc.width
+        shapes = {"image": ((H, W, ch) if ch > 1 else (H, W), None), "src_xy": ((H, W, 2), "float32"), "status": ((H, W), "uint8")}
+        out = {}
+        for k in names:
+            shape, dt = shapes[k]
+            if on_device:
+                out[k] = _torch.empty(shape, dtype=s.dtype if dt is None else getattr(_torch, dt), device=s.device)
+            else:
+                out[k] = np.zeros(shape, s.dtype if dt is None else dt)
+        ptr = _tensor_ptr if on_device else _array_ptr
+        lout = capi.DsrtLensOut(**{k: ptr(x) for k, x in out.items()})
+        head = (self._h, C.byref(desc), ptr(s), C.byref(params), C.byref(lout))
+        if on_device:
+            _check(lib.dsrt_lens_apply(*head, C.c_void_p(self._raw_stream(stream))), "dsrt_lens_apply")
+        else:
+            _check(lib.dsrt_lens_apply_to_host(*head), "dsrt_lens_apply_to_host")
+        return out
 
     def poke_node_word(self, word_index, value):
         """Test hook (dsrt_selftest_poke_node_word): overwrite one 32-bit word of the resident node records; returns the previous value."""

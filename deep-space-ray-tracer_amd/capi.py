@@ -178,6 +178,20 @@ STAR_PROJECTED, STAR_VISIBLE, STAR_INSIDE = 1, 2, 4                     # the bi
 MAX_STARS = 1 << 22
 
 
+class DsrtLens(C.Structure):
+    _fields_ = ([("src_width", C.c_int), ("src_height", C.c_int)] +
+                [(n, C.c_float) for n in ("src_fx", "src_fy", "src_cx", "src_cy", "fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2", "v1", "v2", "v3")] +
+                [("cos4", C.c_int), ("filter", C.c_int), ("channels", C.c_int), ("clamp_zero", C.c_int), ("fill_bits", C.c_uint32)])
+
+
+class DsrtLensOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("image", "src_xy", "status")]
+
+
+LENS_NEAREST, LENS_BILINEAR, LENS_CUBIC = 0, 1, 2                       # DSRT_LENS_* of include/dsrt.h: DsrtLens.filter ...
+LENS_INVERTED, LENS_ANY_TAP, LENS_ALL_TAPS = 1, 2, 4                    # ... and the bits of the status byte
+
+
 class DsrtCoverage(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("hits", "alpha", "mask", "sun_hits", "sun_alpha", "sun_mask", "class_hits")] + [("rep", DsrtGBuffer)]
 
@@ -230,6 +244,7 @@ EXPORTS = [
     "dsrt_upscale_coverage_alpha_min", "dsrt_upscale_guided_coverage", "dsrt_upscale_guided_coverage_to_host", "dsrt_render_upscaled_coverage_to_host",
     "dsrt_sensor_defaults", "dsrt_sensor_psf_gaussian", "dsrt_sensor_apply", "dsrt_sensor_apply_to_host", "dsrt_write_pnm16",
     "dsrt_render_stars", "dsrt_render_stars_to_host", "dsrt_stars_from_catalog", "dsrt_stars_synthetic_catalog",
+    "dsrt_lens_defaults", "dsrt_lens_apply", "dsrt_lens_apply_to_host", "dsrt_lens_distort_points", "dsrt_lens_intrinsics_from_camera",
     "dsrt_selftest_read_schedule", "dsrt_selftest_tile_order", "dsrt_selftest_tile_reorder", "dsrt_selftest_batch_table",
     "dsrt_selftest_math", "dsrt_selftest_devkat", "dsrt_selftest_philox", "dsrt_microbench_gather", "dsrt_microbench_valu", "dsrt_microbench_valu_kinds", "dsrt_microbench_valu_kind_name", "gpu_render_scene", "dsrt_build_gpu_scene", "dsrt_free_gpu_scene",
 ]
@@ -382,6 +397,11 @@ def load():
     sig("dsrt_render_stars_to_host", C.c_int, [vp, P(DsrtRenderDesc), P(DsrtStars), P(DsrtStarsOut), P(DsrtStats)])
     sig("dsrt_stars_from_catalog", C.c_int, [C.c_int, vp, vp, vp, vp, vp, vp])
     sig("dsrt_stars_synthetic_catalog", C.c_int, [C.c_uint64, C.c_int, C.c_double, C.c_double, vp, vp, vp])
+    sig("dsrt_lens_defaults", None, [P(DsrtLens)])
+    sig("dsrt_lens_apply", C.c_int, [vp, P(DsrtRenderDesc), vp, P(DsrtLens), P(DsrtLensOut), vp])
+    sig("dsrt_lens_apply_to_host", C.c_int, [vp, P(DsrtRenderDesc), vp, P(DsrtLens), P(DsrtLensOut)])
+    sig("dsrt_lens_distort_points", C.c_int, [P(DsrtLens), C.c_int, vp, vp, vp])
+    sig("dsrt_lens_intrinsics_from_camera", C.c_int, [P(GPUCamera), C.c_int, C.c_int, vp])
     sig("dsrt_host_scene_begin_body", C.c_int, [vp])
     sig("dsrt_host_scene_body_count", C.c_int, [vp])
     sig("dsrt_host_scene_body_range", C.c_int, [vp, C.c_int, P(C.c_int), P(C.c_int)])
@@ -411,7 +431,7 @@ def load():
         raise ImportError(f"ABI mismatch: {LIB_PATH} was built for {have}, include/dsrt.h says {want}, capi.py's structs are laid out for {ABI_VERSION}: "
                           "rebuild with `make lib` / update capi.py")
     for which, struct in enumerate((DsrtRenderDesc, DsrtStats, GPUScene, GPUCamera, DsrtPose, DsrtFrame, DsrtGBuffer, DsrtRays,
-                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses, None, DsrtSensor, None, DsrtStars, DsrtStarsOut)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
+                                          DsrtRayHits, DsrtAccum, DsrtAdaptive, DsrtAdaptiveStats, DsrtDenoiseGuides, DsrtDenoise, DsrtTemporal, DsrtUpscaleGuides, DsrtUpscale, None, DsrtBodyMotion, DsrtTemporalShading, DsrtCoverageDesc, DsrtCoverage, DsrtCoverageClasses, None, DsrtSensor, None, DsrtStars, DsrtStarsOut, None, DsrtLens, DsrtLensOut)):      # DSRT_SIZEOF_* of include/dsrt.h, in order (None: an index left unassigned)
         if struct is not None and lib.dsrt_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"capi.py lays {struct.__name__} out in {C.sizeof(struct)} bytes, the library in {lib.dsrt_sizeof(which)}: update capi.py")
     return lib

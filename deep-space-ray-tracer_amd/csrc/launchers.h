@@ -3,6 +3,7 @@
 #pragma once
 
 #include "device_layout.h"
+#include "lens_math.h"
 
 namespace dsrt {
 
@@ -154,7 +155,21 @@ struct StarsArgs {
 };
 hipError_t launch_stars(const StarsArgs& a, hipStream_t stream);             // project, deposit, resolve: three launches in stream order
 
-// bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES).  What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
+// lens_kernel.hip (include/dsrt.h, LENS MODEL).  src: the pinhole frame, src_w*src_h*channels 32-bit words (floats for filters 1 and 2); the outputs that are not
+// null are written (at least one is): out_image W*H*channels words, out_src_xy W*H*2 floats, out_status W*H bytes.  The rest is DsrtLens's.
+struct LensArgs {
+    const uint32_t* src;
+    uint32_t* out_image; float* out_src_xy; uint8_t* out_status;
+    int W, H, src_w, src_h;
+    float fx, fy, cx, cy, src_fx, src_fy, src_cx, src_cy;
+    LensCoeffs c;
+    float v1, v2, v3;
+    int cos4, clamp_zero;
+    uint32_t fill_bits;
+};
+hipError_t launch_lens(const LensArgs& a, int channels, int filter, hipStream_t stream);      // dsrt_lens_kernel<channels, filter>
+
+// bodies_kernel.hip (include/dsrt.h, MOVABLE RIGID BODIES). What a pose update reads and writes: the three arrays of the resident scene it rewrites in place, and what
 // dsrt_scene_upload_bodies made resident beside them.  A movable ENTRY is a pair record of tri_pairs that holds triangles of a body >= 1; entries are sorted by body.
 struct BodiesView {
     float4* pairs; float4* tri_pairs; float4* tri_shade;     // the resident scene's (device_layout.h)

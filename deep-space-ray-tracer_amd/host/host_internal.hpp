@@ -81,6 +81,10 @@ struct BodyMotionTable { int first[DSRT_MAX_BODIES], count[DSRT_MAX_BODIES]; uin
 int check_body_motion(const char* fn, const DsrtBodyMotion* m);
 void pack_body_motion(const DsrtBodyMotion& m, BodyMotionTable& t);
 
+// lens_host.cpp (include/dsrt.h, LENS MODEL): what dsrt_lens_apply and dsrt_lens_distort_points refuse alike of a DsrtLens -- focal lengths, principal points and
+// k1 .. p2 -- and, with `warp`, what only the warp reads: the source's size, the vignetting terms, filter, channels and the two switches.
+int check_lens_params(const char* fn, const DsrtLens* p, bool warp);
+
 bool texture_flip_latch();
 void texture_flip_latch_set(bool v);
 

@@ -171,6 +171,8 @@ size_t dsrt_sizeof(int which) {                              // what a binding's
         case DSRT_SIZEOF_SENSOR: return sizeof(DsrtSensor);
         case DSRT_SIZEOF_STARS: return sizeof(DsrtStars);
         case DSRT_SIZEOF_STARS_OUT: return sizeof(DsrtStarsOut);
+        case DSRT_SIZEOF_LENS: return sizeof(DsrtLens);
+        case DSRT_SIZEOF_LENS_OUT: return sizeof(DsrtLensOut);
         default: return 0;
     }
 }

@@ -70,6 +70,14 @@
 //     before --sensor, whose raw frame then contains the stars.  Writes <frame>_stars.pfm (the layer) and <frame>_stars.txt (per star: index, fx, fy, status);
 //     without --sensor nothing else changes.  A malformed spec or catalogue is a usage error before any device is touched.  In rng_mode 0 the flag is announced and
 //     ignored, like --sensor; it refuses the combinations --sensor refuses.
+//   * rng_mode 1 only: --lens SPEC warps each frame's LINEAR image through a lens (include/dsrt.h, LENS MODEL: dsrt_lens_apply_to_host).  SPEC is a comma list, every
+//     key optional:  k1=  k2=  k3=  p1=  p2=  (Brown-Conrady)   zoom=Z (the output's focal length is Z times the frame's; default 1)   vig=V1:V2:V3   cos4
+//     filter=nearest|linear|cubic (default cubic).  The source is the chain's linear image with the intrinsics of the frame's camera
+//     (dsrt_lens_intrinsics_from_camera); the output has the same size and principal point.  It runs after --stars and before --sensor, whose raw frame is then the
+//     distorted one.  Writes <frame>_lens.pfm (the warped linear image), <frame>_lens_map.pfm (three channels: the source position sx, sy and the status byte) and,
+//     with --stars, <frame>_stars_lens.txt (per star: index, its centroid in the distorted frame -- dsrt_lens_distort_points of <frame>_stars.txt's -- and the
+//     star's status; a star that was not projected keeps 0 0).  Without --lens every other file is byte for byte what it is without this flag.  A malformed SPEC is
+//     a usage error before any device is touched.  In rng_mode 0 the flag is announced and ignored, like --sensor; it refuses the combinations --sensor refuses.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -166,6 +174,57 @@ static bool parse_stars_spec(const std::string& spec, StarsSpec& out, std::strin
     return true;
 }
 
+// --lens SPEC (include/dsrt.h, LENS MODEL): the library's defaults with the SPEC's keys applied; the two frames are set per frame, from its camera.
+struct LensSpec { DsrtLens p; double zoom = 1.0; };
+
+static bool parse_lens_spec(const std::string& spec, LensSpec& out, std::string& why) {
+    static const char* known = "k1 k2 k3 p1 p2 zoom vig cos4 filter";
+    dsrt_lens_defaults(&out.p);
+    auto number = [&](const std::string& key, const std::string& v, double& x) {
+        char* end = nullptr;
+        x = std::strtod(v.c_str(), &end);
+        if (v.empty() || *end || !std::isfinite(x) || !std::isfinite((float)x)) { why = key + " needs a finite number, not '" + v + "'"; return false; }
+        return true;
+    };
+    if (spec.empty()) { why = "an empty SPEC"; return false; }
+    size_t at = 0;
+    while (at <= spec.size()) {
+        const size_t comma = std::min(spec.find(',', at), spec.size());
+        const std::string item = spec.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eq = item.find('=');
+        const std::string key = item.substr(0, eq), v = eq == std::string::npos ? "" : item.substr(eq + 1);
+        double x = 0.0;
+        if (key == "cos4" && eq == std::string::npos) out.p.cos4 = 1;
+        else if (eq == std::string::npos) { why = item.empty() ? "an empty item" : "'" + item + "' needs a value (key=value); known keys: " + known; return false; }
+        else if (key == "filter") {
+            if (v == "nearest") out.p.filter = DSRT_LENS_NEAREST;
+            else if (v == "linear") out.p.filter = DSRT_LENS_BILINEAR;
+            else if (v == "cubic") out.p.filter = DSRT_LENS_CUBIC;
+            else { why = "filter is nearest, linear or cubic, not '" + v + "'"; return false; }
+        }
+        else if (key == "vig") {
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            double a = 0.0, b = 0.0, c = 0.0;
+            if (c2 == std::string::npos || !number("vig=V1", v.substr(0, c1), a) || !number("vig=V1:V2", v.substr(c1 + 1, c2 - c1 - 1), b) || !number("vig=V1:V2:V3", v.substr(c2 + 1), c)) {
+                if (why.empty()) why = "vig takes V1:V2:V3";
+                return false;
+            }
+            out.p.v1 = (float)a; out.p.v2 = (float)b; out.p.v3 = (float)c;
+        }
+        else if (!number(key, v, x)) return false;
+        else if (key == "k1") out.p.k1 = (float)x;
+        else if (key == "k2") out.p.k2 = (float)x;
+        else if (key == "k3") out.p.k3 = (float)x;
+        else if (key == "p1") out.p.p1 = (float)x;
+        else if (key == "p2") out.p.p2 = (float)x;
+        else if (key == "zoom") { if (!(x > 0.0)) { why = "zoom must be > 0"; return false; } out.zoom = x; }
+        else if (key == "cos4") { if (x != 0.0 && x != 1.0) { why = "cos4 is 0 or 1"; return false; } out.p.cos4 = (int)x; }
+        else { why = "unknown key '" + key + "'; known keys: " + known; return false; }
+    }
+    return true;
+}
+
 static bool parse_sensor_spec(const std::string& spec, SensorSpec& out, std::string& why) {
     dsrt_sensor_defaults(&out.p);
     auto number = [&](const std::string& key, const std::string& v, double& x) {
@@ -257,6 +316,8 @@ int main(int argc, char** argv) {
     SensorSpec sensor_spec;                                         // --sensor SPEC (include/dsrt.h, SENSOR MODEL)
     bool stars = false;
     StarsSpec stars_spec;                                           // --stars FILE[,flux=F][,occlusion=0] (include/dsrt.h, POINT SOURCES)
+    bool lens = false;
+    LensSpec lens_spec;                                             // --lens SPEC (include/dsrt.h, LENS MODEL)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -330,7 +391,12 @@ int main(int argc, char** argv) {
             if (!parse_stars_spec(next("--stars"), stars_spec, why)) { std::fprintf(stderr, "dsrt_render: --stars: %s\n", why.c_str()); return 2; }
             stars = true;
         }
-        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]] [--rng-mode 1 --sensor SPEC] [--rng-mode 1 --stars FILE[,flux=F][,occlusion=0]]\n"); return 2; }
+        else if (a == "--lens") {                                   // rng_mode 1: distortion and vignetting on each frame's linear image (include/dsrt.h, LENS MODEL)
+            std::string why;
+            if (!parse_lens_spec(next("--lens"), lens_spec, why)) { std::fprintf(stderr, "dsrt_render: --lens: %s\n", why.c_str()); return 2; }
+            lens = true;
+        }
+        else { std::fprintf(stderr, "usage: dsrt_render --obj mesh.obj [--input_txt poses.txt] [--output_dir dir] [--width W --height H --spp N --depth D] [--frame i --frames n] [--bvh median|sah|lbvh] [--rng-mode 0|1] [--reference-math] [--certified-tree] [--fast] [--png] [--gbuffer] [--strict-textures] [--passes P] [--variance] [--adaptive TOL [--adaptive-passes P] [--adaptive-min-passes M] [--adaptive-floor F]] [--denoise [ITER]] [--temporal] [--flow] [--upscale [S]] [--body body.obj [--body-scale S]]... [--body-poses poses.txt] [--follow-bodies] [--follow-shading] [--coverage grid:S|diag:N] [--coverage-aware [ALPHA_MIN]] [--rng-mode 1 --upscale [S] --coverage-aware [ALPHA_MIN] [--coverage diag:N]] [--rng-mode 1 --sensor SPEC] [--rng-mode 1 --stars FILE[,flux=F][,occlusion=0]] [--rng-mode 1 --lens SPEC]\n"); return 2; }
     }
     if (obj.empty()) { std::fprintf(stderr, "dsrt_render: --obj is required\n"); return 2; }
     if (!bodies.empty() && (sah || lbvh || certified)) { std::fprintf(stderr, "dsrt_render: --body brings its own tree: it does not combine with --bvh sah|lbvh, --fast or --certified-tree\n"); return 2; }
@@ -350,6 +416,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "dsrt_render: --stars needs --rng-mode 1 (or --fast): ignored\n");
         stars = false;
     }
+    if (lens && rng_mode != 1) {                                    // announced and ignored, like --sensor
+        std::fprintf(stderr, "dsrt_render: --lens needs --rng-mode 1 (or --fast): ignored\n");
+        lens = false;
+    }
+    if (lens && (adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --lens does not combine with --adaptive / --passes / --gbuffer\n"); return 2; }
+    if (lens && spp < 2) { std::fprintf(stderr, "dsrt_render: --lens needs --spp 2 or more\n"); return 2; }
     if (stars && (adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --stars does not combine with --adaptive / --passes / --gbuffer\n"); return 2; }
     if (stars && spp < 2) { std::fprintf(stderr, "dsrt_render: --stars needs --spp 2 or more\n"); return 2; }
     if (sensor && (adaptive || passes != 0 || gbuffer)) { std::fprintf(stderr, "dsrt_render: --sensor does not combine with --adaptive / --passes / --gbuffer\n"); return 2; }
@@ -477,8 +549,8 @@ int main(int argc, char** argv) {
         return (png ? dsrt_write_png(path.c_str(), image, width, height) : dsrt_write_ppm(path.c_str(), image, width, height)) == DSRT_OK;
     };
 
-    // --sensor, --stars: every chain below also hands out its LINEAR image (at the upscaler's output size with --upscale), the star field's and the detector's input.
-    const bool wants_linear = sensor || stars;
+    // --sensor, --stars, --lens: every chain below also hands out its LINEAR image (at the upscaler's output size with --upscale), the star field's and the detector's input.
+    const bool wants_linear = sensor || stars || lens;
     const int sensor_w = upscale ? width * upscale_factor : width, sensor_h = upscale ? height * upscale_factor : height;
     std::vector<float> sensor_linear(wants_linear ? (size_t)sensor_w * sensor_h * 3 : 0);
     float* const lin = wants_linear ? sensor_linear.data() : nullptr;
@@ -680,7 +752,7 @@ int main(int argc, char** argv) {
         return 0;
     };
 
-    // --sensor or --stars without --denoise or --upscale: the plain mean of the frame's samples as its linear image (the denoiser with 0 iterations); with --variance its variance.
+    // --sensor, --stars or --lens without --denoise or --upscale: the plain mean of the frame's samples as its linear image (the denoiser with 0 iterations); with --variance its variance.
     DsrtDenoise dn_mean = dn;
     dn_mean.iterations = 0;
     if (wants_linear && !frame_step) frame_step = [&](size_t, const std::string& base) -> int {
@@ -717,6 +789,43 @@ int main(int argc, char** argv) {
         if (std::fclose(f) != 0) { std::fprintf(stderr, "dsrt_render: short write to %s_stars.txt\n", base.c_str()); return 1; }
         std::printf("stars: %zu of %zu visible at %d x %d%s\nSaved %s_stars.pfm, %s_stars.txt\n", visible, n_stars, sensor_w, sensor_h, stars_spec.occlusion ? "" : ", occlusion off",
                     base.c_str(), base.c_str());
+        return 0;
+    };
+    // --lens: the linear image the frame's step (and --stars) left, through the lens (include/dsrt.h, LENS MODEL); `q` indexes the frame's camera
+    const size_t lens_px = lens ? (size_t)sensor_w * sensor_h : 0;
+    std::vector<float> lens_image(lens_px * 3), lens_xy(lens_px * 2), lens_map(lens_px * 3), star_lens_xy(lens && stars ? star_xy.size() : 0);
+    std::vector<uint8_t> lens_status(lens_px), star_lens_ok(lens && stars ? n_stars : 0);
+    auto write_lens = [&](size_t q, const std::string& base) -> int {
+        DsrtRenderDesc sd = d;
+        sd.width = sensor_w; sd.height = sensor_h;
+        float k[4];
+        if (dsrt_lens_intrinsics_from_camera(&cams[q], sensor_w, sensor_h, k) != DSRT_OK) return fail("taking the camera's intrinsics");
+        DsrtLens& p = lens_spec.p;
+        p.src_width = sensor_w; p.src_height = sensor_h; p.channels = 3;
+        p.src_fx = k[0]; p.src_fy = k[1]; p.src_cx = k[2]; p.src_cy = k[3];
+        p.fx = (float)(k[0] * lens_spec.zoom); p.fy = (float)(k[1] * lens_spec.zoom); p.cx = k[2]; p.cy = k[3];
+        const DsrtLensOut out{lens_image.data(), lens_xy.data(), lens_status.data()};
+        if (dsrt_lens_apply_to_host(ctx, &sd, lin, &p, &out) != DSRT_OK) return fail("applying the lens model");
+        size_t inverted = 0;
+        for (size_t i = 0; i < lens_px; ++i) {
+            lens_map[3 * i] = lens_xy[2 * i]; lens_map[3 * i + 1] = lens_xy[2 * i + 1]; lens_map[3 * i + 2] = (float)lens_status[i];
+            inverted += lens_status[i] & DSRT_LENS_INVERTED;
+        }
+        if (dsrt_write_pfm((base + "_lens.pfm").c_str(), lens_image.data(), sensor_w, sensor_h, 3) != DSRT_OK ||
+            dsrt_write_pfm((base + "_lens_map.pfm").c_str(), lens_map.data(), sensor_w, sensor_h, 3) != DSRT_OK) return fail("writing the warped frame");
+        sensor_linear = lens_image;                                 // what --sensor sees
+        std::printf("lens: %d x %d, filter %d, %zu of %zu pixels have a source\nSaved %s_lens.pfm, %s_lens_map.pfm\n", sensor_w, sensor_h, p.filter, inverted, lens_px,
+                    base.c_str(), base.c_str());
+        if (!stars) return 0;
+        if (dsrt_lens_distort_points(&p, (int)n_stars, star_xy.data(), star_lens_xy.data(), star_lens_ok.data()) != DSRT_OK) return fail("distorting the star centroids");
+        FILE* f = std::fopen((base + "_stars_lens.txt").c_str(), "w");
+        if (!f) { std::fprintf(stderr, "dsrt_render: cannot write %s_stars_lens.txt\n", base.c_str()); return 1; }
+        for (size_t i = 0; i < n_stars; ++i) {
+            const bool has = (star_status[i] & 1u) && star_lens_ok[i];           // projected by the pinhole, and finite through the lens
+            std::fprintf(f, "%zu %.9g %.9g %u\n", i, has ? (double)star_lens_xy[2 * i] : 0.0, has ? (double)star_lens_xy[2 * i + 1] : 0.0, (unsigned)star_status[i]);
+        }
+        if (std::fclose(f) != 0) { std::fprintf(stderr, "dsrt_render: short write to %s_stars_lens.txt\n", base.c_str()); return 1; }
+        std::printf("Saved %s_stars_lens.txt\n", base.c_str());
         return 0;
     };
     // --sensor: the detector over the linear image the frame's step left (include/dsrt.h, SENSOR MODEL); `frame` is the frame's index in the pose file
@@ -756,6 +865,7 @@ int main(int argc, char** argv) {
         if (dsrt_scene_set_camera_sun(ctx, &cams[q], suns.data() + 3 * q) != DSRT_OK) return fail("setting the camera");
         if (const int rc = frame_step(q, frame_base(ids[q]))) return rc;
         if (stars) if (const int rc = write_stars(ids[q], frame_base(ids[q]))) return rc;
+        if (lens) if (const int rc = write_lens(q, frame_base(ids[q]))) return rc;
         if (sensor) if (const int rc = write_sensor(ids[q], frame_base(ids[q]))) return rc;
         if (coverage) if (const int rc = write_coverage(frame_base(ids[q]))) return rc;
     }

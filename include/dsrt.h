@@ -35,7 +35,7 @@ const char* dsrt_last_error(void);
 /* ABI version: THE one place it is written.  Bumped on any signature, struct or flag change (3 = round 2: DsrtStats grew,
  * dsrt_render_batch, dsrt_multi_*; 4 = round 3: DsrtRenderDesc.tune[3] pruned to the switches a host may need, reserved bits
  * refused; dsrt_selftest_devkat, dsrt_microbench_valu; 5 = DsrtRenderDesc.math_mode appended;
- * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host, DsrtSensor, dsrt_sensor_defaults, dsrt_sensor_psf_gaussian, dsrt_sensor_apply, dsrt_sensor_apply_to_host, dsrt_write_pnm16, DSRT_SIZEOF_SENSOR, DsrtStars, DsrtStarsOut, dsrt_render_stars, dsrt_render_stars_to_host, dsrt_stars_from_catalog, dsrt_stars_synthetic_catalog, DSRT_SIZEOF_STARS, DSRT_SIZEOF_STARS_OUT).  dsrt_abi_version() returns the value the library was compiled with;
+ * 6 = dsrt_host_scene_add_texture_file; 7 = round 4: dsrt_microbench_copy, dsrt_sizeof, dsrt_dev_set_experiment, dsrt_selftest_poke_node_word, dsrt_ctx_set_certified_tree, DsrtStats grew; 8 = DsrtGBuffer, dsrt_render_gbuffer, dsrt_render_gbuffer_to_host, dsrt_write_pfm; purely additive since, version kept: DsrtRays, DsrtRayHits, dsrt_trace_rays, dsrt_trace_rays_to_host, dsrt_pose_points_to_model, dsrt_pose_dirs_to_model, DsrtAccum, dsrt_render_accumulate, dsrt_render_accumulate_to_host, dsrt_resolve_accumulated, dsrt_resolve_accumulated_to_host, DSRT_SIZEOF_ACCUM, DsrtAdaptive, DsrtAdaptiveStats, dsrt_render_accumulate_masked, dsrt_render_accumulate_masked_to_host, dsrt_select_unconverged, dsrt_resolve_accumulated_counts, dsrt_render_adaptive, dsrt_render_adaptive_to_host, DSRT_SIZEOF_ADAPTIVE, DSRT_SIZEOF_ADAPTIVE_STATS, DsrtDenoiseGuides, DsrtDenoise, dsrt_denoise_defaults, dsrt_denoise_accumulated, dsrt_denoise_accumulated_to_host, dsrt_render_denoised_to_host, DSRT_SIZEOF_DENOISE_GUIDES, DSRT_SIZEOF_DENOISE, DsrtTemporal, dsrt_temporal_defaults, dsrt_denoise_temporal, dsrt_denoise_temporal_to_host, dsrt_render_denoised_temporal_to_host, DSRT_SIZEOF_TEMPORAL, DsrtUpscaleGuides, DsrtUpscale, dsrt_upscale_defaults, dsrt_upscale_guided, dsrt_upscale_guided_to_host, dsrt_render_upscaled_to_host, DSRT_SIZEOF_UPSCALE_GUIDES, DSRT_SIZEOF_UPSCALE, DSRT_MAX_BODIES, dsrt_host_scene_begin_body, dsrt_host_scene_body_count, dsrt_host_scene_body_range, dsrt_host_scene_build_bvh_bodies, dsrt_host_scene_set_body_poses, dsrt_scene_upload_bodies, dsrt_scene_set_body_poses, dsrt_ctx_body_count, dsrt_ctx_body_update_ms, dsrt_selftest_read_scene_words, DsrtBodyMotion, dsrt_body_motion_host, dsrt_denoise_temporal_bodies, dsrt_denoise_temporal_bodies_to_host, dsrt_ctx_set_temporal_bodies, dsrt_ctx_temporal_bodies, DSRT_SIZEOF_BODY_MOTION, DsrtCoverageDesc, DsrtCoverageClasses, DsrtCoverage, dsrt_coverage_defaults, dsrt_render_coverage, dsrt_render_coverage_to_host, dsrt_denoise_coverage_alpha_min, dsrt_denoise_accumulated_coverage, dsrt_denoise_accumulated_coverage_to_host, dsrt_render_denoised_coverage_to_host, DSRT_SIZEOF_COVERAGE_DESC, DSRT_SIZEOF_COVERAGE, DSRT_SIZEOF_COVERAGE_CLASSES, dsrt_selftest_read_schedule, dsrt_selftest_tile_order, dsrt_selftest_tile_reorder, dsrt_selftest_batch_table, dsrt_upscale_coverage_alpha_min, dsrt_upscale_guided_coverage, dsrt_upscale_guided_coverage_to_host, dsrt_render_upscaled_coverage_to_host, DsrtSensor, dsrt_sensor_defaults, dsrt_sensor_psf_gaussian, dsrt_sensor_apply, dsrt_sensor_apply_to_host, dsrt_write_pnm16, DSRT_SIZEOF_SENSOR, DsrtStars, DsrtStarsOut, dsrt_render_stars, dsrt_render_stars_to_host, dsrt_stars_from_catalog, dsrt_stars_synthetic_catalog, DSRT_SIZEOF_STARS, DSRT_SIZEOF_STARS_OUT, DsrtLens, DsrtLensOut, dsrt_lens_defaults, dsrt_lens_apply, dsrt_lens_apply_to_host, dsrt_lens_distort_points, dsrt_lens_intrinsics_from_camera, DSRT_SIZEOF_LENS, DSRT_SIZEOF_LENS_OUT).  dsrt_abi_version() returns the value the library was compiled with;
  * bindings parse this line (capi.header_abi_version) and compare. */
 #define DSRT_ABI_VERSION 8
 int dsrt_abi_version(void);
@@ -66,6 +66,8 @@ int dsrt_abi_version(void);
 #define DSRT_SIZEOF_SENSOR        24   /* (23 is left unassigned and answers 0, like 17: tests/test_coverage_host.py holds it to that as the first unknown index of its day) */
 #define DSRT_SIZEOF_STARS         26   /* (25 is left unassigned and answers 0, like 17 and 23: tests/test_sensor_host.py holds it to that) */
 #define DSRT_SIZEOF_STARS_OUT     27
+#define DSRT_SIZEOF_LENS          29   /* (28 is left unassigned and answers 0, like 17, 23 and 25: tests/test_stars_host.py holds it to that) */
+#define DSRT_SIZEOF_LENS_OUT      30
 size_t dsrt_sizeof(int which);
 
 /* ===================================================================================== */
@@ -1277,6 +1279,101 @@ int  dsrt_render_stars(DsrtContext* ctx, const DsrtRenderDesc* desc /* width, he
 int  dsrt_render_stars_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const DsrtStars* h_stars, const DsrtStarsOut* h_out, DsrtStats* stats);
 int  dsrt_stars_from_catalog(int n, const double* ra_deg, const double* dec_deg, const double* mag, const float flux_mag0[3], double* world_dirs /* n x 3 */, float* flux /* n x 3 */);
 int  dsrt_stars_synthetic_catalog(uint64_t seed, int n, double mag_min, double mag_max, double* ra_deg, double* dec_deg, double* mag);
+
+/*
+ * LENS MODEL (after POINT SOURCES, before the SENSOR MODEL): the pinhole frame as a real lens would have formed it -- Brown-Conrady distortion (fx, fy, cx, cy, k1, k2,
+ * p1, p2, k3: what every calibration tool emits, OpenCV's meaning and order of terms) and a flat field that falls off towards the corners.  The warp acts on the LINEAR
+ * frame, the same call warps every label with it (nearest: words are copied, so id planes, masks and range go through untouched), it returns the map it used, and like
+ * every output of this library the result is REPRODUCIBLE: tests/_lens_model.py reproduces every bit.
+ *
+ * THE FRAMES.  The source is a pinhole frame of src_width x src_height pixels with intrinsics src_fx, src_fy, src_cx, src_cy: a point at normalised coordinates
+ * (xu, yu) -- x to the right, y DOWN, depth 1 -- lies at pixel (xu*src_fx + src_cx, yu*src_fy + src_cy), pixel centres at integer coordinates, row 0 on top.  The output
+ * is the distorted camera's frame, W = desc->width by H = desc->height, intrinsics fx, fy, cx, cy.  dsrt_lens_intrinsics_from_camera gives the library's own pinhole.
+ *
+ * THE ARITHMETIC.  All fp32; every operation one correctly rounded IEEE operation, never contracted, in the order and with the parentheses written; / and floorf are the
+ * IEEE ones; fmaxf returns the other operand when one is a NaN; the constants are float literals.  Per output pixel (x, y):
+ *   1. Normalise.    xd = ((float)x - cx) / fx;   yd = ((float)y - cy) / fy
+ *   2. The forward model distort(xu, yu), stated once and used by steps 3 and 4 and by dsrt_lens_distort_points:
+ *        xx = xu*xu;  yy = yu*yu;  xy = xu*yu;  r2 = xx + yy
+ *        rad = 1.0f + r2*(k1 + r2*(k2 + r2*k3))
+ *        dx  = (2.0f*p1)*xy + p2*(r2 + 2.0f*xx)
+ *        dy  = p1*(r2 + 2.0f*yy) + (2.0f*p2)*xy
+ *        distort = (xu*rad + dx,  yu*rad + dy)
+ *   3. The inverse, by fixed-point steps: xu = xd, yu = yd; then EXACTLY 12 times, rad, dx, dy taken at the current (xu, yu) and both coordinates replaced together:
+ *        xu = (xd - dx) / rad;   yu = (yd - dy) / rad
+ *      There is no early exit: control flow is wave-uniform and the bits do not depend on a tolerance.
+ *   4. The certificate.  (xr, yr) = distort(xu, yu);
+ *        inverted = fabsf((xr - xd)*fx) <= 0x1p-6f && fabsf((yr - yd)*fy) <= 0x1p-6f        -- a NaN fails
+ *      Beyond the fold-over radius of a strong barrel an output pixel has no preimage; the iteration then ends somewhere, and this test says so: the library reports
+ *      it per pixel and does not guess.  A pixel that is not inverted has no source position and no taps.
+ *   5. The source position.  sx = xu*src_fx + src_cx;  sy = yu*src_fy + src_cy.  The window, in float, before any conversion to an integer:
+ *        in_window = sx > -3.0f && sx < (float)src_width + 2.0f && sy > -3.0f && sy < (float)src_height + 2.0f      -- a NaN fails
+ *      Outside the window the pixel has no taps (no tap of any filter could lie inside the source).
+ *   6. The taps, C = channels interleaved 32-bit words per pixel.  A tap (qx, qy) is INSIDE when 0 <= qx < src_width and 0 <= qy < src_height.
+ *        nearest (filter 0):     the one tap (floorf(sx + 0.5f), floorf(sy + 0.5f)); inside: its C words are copied untouched; not inside: fill_bits in each.
+ *        bilinear (filter 1):    x0 = floorf(sx), tx = sx - x0;  weights wx[0] = 1.0f - tx, wx[1] = tx for the columns x0, x0 + 1; wy[] likewise from sy.
+ *        Catmull-Rom (filter 2): x0 = floorf(sx), t = sx - x0;  for the columns x0 - 1, x0, x0 + 1, x0 + 2
+ *                                  wx[0] = (((-0.5f*t) + 1.0f)*t - 0.5f)*t        wx[1] = (((1.5f*t) - 2.5f)*t)*t + 1.0f
+ *                                  wx[2] = (((-1.5f*t) + 2.0f)*t + 0.5f)*t        wx[3] = (((0.5f*t) - 0.5f)*t)*t              wy[] likewise from sy.
+ *        Filters 1 and 2: acc_k = +0.0f per channel; rows outer (ascending), columns inner (ascending); for a tap inside,  acc_k = acc_k + (wy[j]*wx[i])*c_k.
+ *        A tap that is not inside is skipped (space is black); nothing is renormalised and nothing is reassociated.
+ *   7. Vignetting, filters 1 and 2 only (nearest copies words).  ru2 = xu*xu + yu*yu;
+ *        g = 1.0f + ru2*(v1 + ru2*(v2 + ru2*v3));   with cos4 != 0:  q = 1.0f + ru2;  g = g / (q*q)      -- the natural cos^4(theta), ru2 = tan^2(theta)
+ *        g = fmaxf(g, 0.0f);   out_k = acc_k * g;   with clamp_zero != 0:  out_k = fmaxf(out_k, 0.0f)       -- Catmull-Rom has negative lobes
+ *   8. Outputs; each optional, at least one, and any subset gives the same bytes in each:
+ *        image    W*H*C 32-bit words (floats for filters 1 and 2).  A pixel that is not inverted: +0.0f (filters 1, 2) or fill_bits (nearest) in every word.
+ *                 An inverted pixel outside the window: acc = +0.0f through step 7 (filters 1, 2), fill_bits (nearest).
+ *        src_xy   W*H*2 floats: (sx, sy) when inverted -- in the window or not -- else (+0, +0).  The ground-truth map with which a caller warps anything else.
+ *        status   W*H bytes: bit 0 inverted, bit 1 at least one tap of the chosen filter inside the source, bit 2 all of them inside.
+ *   With every coefficient zero and the source's own intrinsics, sx and sy are the pixel grid wherever (((float)x - cx)/fx)*fx + cx == x (always so for a power-of-two
+ *   focal length), and the three filters return the source's words -- filters 1 and 2 with -0.0f as +0.0f, since the sum starts at +0.0f, and for finite sources.
+ *
+ * WHAT IT DOES NOT DO.  Stars deposited before the warp (dsrt_render_stars) are resampled with the frame: their centroid labels are exact -- dsrt_lens_distort_points
+ * of the xy the star pass returned -- but their flux is not conserved, to the order of the local magnification and the filter's response.  A deposit at given
+ * centroids AFTER the warp is not here yet.  Nor are a rolling shutter, chromatic aberration or fisheye (equidistant, Kannala-Brandt) models.
+ *
+ * dsrt_lens_apply: desc gives width and height (the OUTPUT's) and nothing else; d_src is src_width*src_height*channels words, read only.  Asynchronous on `stream`; like
+ *   dsrt_sensor_apply it waits for the context's previous launch, the next launch waits for it, it needs no scene, and the context's camera, sun and render buffers
+ *   are left as they were.  It has no working memory.
+ *   DSRT_ERR_INVALID: a NULL ctx, desc, source, params or out; W, H, src_width or src_height < 2, 2^31 pixels in either frame; a focal length (fx, fy, src_fx,
+ *   src_fy) not > 0 or not finite; a principal point or a coefficient (k1, k2, k3, p1, p2, v1, v2, v3) not finite; filter outside [0, 2], channels outside [1, 4],
+ *   cos4 or clamp_zero not 0 or 1; no output; a word or float pointer not 4-byte aligned; an output range that overlaps the source or another output.  A refused
+ *   call touches no buffer.  The context is the last thing looked at ("null context"), so every other refusal can be seen without a device.
+ * dsrt_lens_apply_to_host: the same from a HOST buffer into HOST buffers, synchronously.
+ * dsrt_lens_defaults: every size, intrinsic and coefficient 0 (the caller sets the two frames), cos4 0, filter 2, channels 3, clamp_zero 1, fill_bits 0.
+ * dsrt_lens_distort_points: a HOST function, the exact forward direction in closed form, for labels.  xy_src: n x 2 floats, positions in the SOURCE frame in pixels
+ *   (star centroids from dsrt_render_stars, the temporal stage's prev_xy, keypoints).  Per point, with the arithmetic pinned as above:
+ *        xu = (px - src_cx) / src_fx;  yu = (py - src_cy) / src_fy;  (xr, yr) = distort(xu, yu);  out = (xr*fx + cx,  yr*fy + cy)
+ *   ok (optional, n bytes) is 1 when the input and the result are finite; otherwise it is 0 and out is (+0, +0).  Sizes, filter and channels are not looked at.
+ *   DSRT_ERR_INVALID: NULL params, xy_src or xy_out; n < 0; the focal lengths, principal points and k1 .. p2 as for dsrt_lens_apply.
+ * dsrt_lens_intrinsics_from_camera: out = {fx, fy, cx, cy} of the library's own pinhole at W x H, derived from TEMPORAL ACCUMULATION's projection, with normalised
+ *   coordinates xu = -a/cc, yu = b/cc of that projection's a, b, cc:  fx = -ew (W-1)/hu,  cx = -eu (W-1)/hu - 0.5,  fy = -ew (H-1)/vv,  cy = (H-1) + 0.5 + ev (H-1)/vv.
+ *   (The renderer's u = (x + 0.5)/(W - 1) and its row flip put the principal point off (W-1)/2.)  Computed in double and rounded once; a convenience whose bits are
+ *   NOT part of the contract.  DSRT_ERR_INVALID: a NULL argument, W or H < 2, a camera whose hu, vv or ew is zero or not finite.
+ */
+typedef struct DsrtLens {
+    int   src_width, src_height;          /* the pinhole frame that is read */
+    float src_fx, src_fy, src_cx, src_cy; /* its intrinsics, in pixels (pixel centres at integer coordinates, row 0 on top) */
+    float fx, fy, cx, cy;                 /* the output (distorted) camera's intrinsics; output size = desc->width x desc->height */
+    float k1, k2, k3, p1, p2;             /* Brown-Conrady, OpenCV's meaning and order of terms */
+    float v1, v2, v3; int cos4;           /* vignetting: polynomial in tan^2(theta), optional natural cos^4 */
+    int   filter;                         /* 0 nearest (labels: words are copied), 1 bilinear, 2 Catmull-Rom */
+    int   channels;                       /* 1..4 interleaved 32-bit words per pixel */
+    int   clamp_zero;                     /* filters 1, 2: fmaxf(result, 0) -- Catmull-Rom has negative lobes */
+    uint32_t fill_bits;                   /* nearest: the word written where there is no source */
+} DsrtLens;
+typedef struct DsrtLensOut { void* image; float* src_xy; uint8_t* status; } DsrtLensOut;
+#define DSRT_LENS_NEAREST  0
+#define DSRT_LENS_BILINEAR 1
+#define DSRT_LENS_CUBIC    2
+#define DSRT_LENS_INVERTED 1u            /* the bits of DsrtLensOut.status */
+#define DSRT_LENS_ANY_TAP  2u
+#define DSRT_LENS_ALL_TAPS 4u
+void dsrt_lens_defaults(DsrtLens* out);
+int  dsrt_lens_apply(DsrtContext* ctx, const DsrtRenderDesc* desc /* width, height only */, const void* d_src, const DsrtLens* params, const DsrtLensOut* out, void* stream);
+int  dsrt_lens_apply_to_host(DsrtContext* ctx, const DsrtRenderDesc* desc, const void* h_src, const DsrtLens* params, const DsrtLensOut* h_out);
+int  dsrt_lens_distort_points(const DsrtLens* params, int n, const float* xy_src, float* xy_out, uint8_t* ok /* optional */);
+int  dsrt_lens_intrinsics_from_camera(const GPUCamera* cam, int width, int height, float out[4]);
 
 /* Root rank, after a gather: tile-major shards [shard][tile][tile*tile*3] -> image-order rgb8. */
 int dsrt_deinterleave_tiles(DsrtContext* ctx, const DsrtRenderDesc* desc, const uint8_t* d_gathered, uint8_t* d_rgb8_image,
