@@ -15,7 +15,7 @@ ARCH     ?= gfx950
 BUILD    := build
 
 HOST_SRC := $(PKG)/host/obj_mesh.cpp $(PKG)/host/image_io.cpp $(PKG)/host/jpeg_decode.cpp $(PKG)/host/bmp_tga_decode.cpp $(PKG)/host/scene_flatten.cpp $(PKG)/host/bvh_median.cpp $(PKG)/host/bvh_sah.cpp $(PKG)/host/bvh_bodies.cpp $(PKG)/host/body_motion.cpp $(PKG)/host/pose_camera.cpp $(PKG)/host/sensor_host.cpp $(PKG)/host/stars_host.cpp $(PKG)/host/lens_host.cpp
-HIP_SRC  := $(PKG)/csrc/render_kernel.hip $(PKG)/csrc/scene_pack.hip $(PKG)/csrc/api_context.hip $(PKG)/csrc/api_bodies.hip $(PKG)/csrc/api_render.hip $(PKG)/csrc/api_sample_sets.hip $(PKG)/csrc/api_reconstruct.hip $(PKG)/csrc/api_queries.hip $(PKG)/csrc/api_selftest.hip $(PKG)/csrc/api_dropin.hip $(PKG)/csrc/microbench.hip $(PKG)/csrc/multi_gpu.hip $(PKG)/csrc/bvh_lbvh.hip $(PKG)/csrc/gbuffer_kernel.hip $(PKG)/csrc/coverage_kernel.hip $(PKG)/csrc/raycast_kernel.hip $(PKG)/csrc/denoise_kernel.hip $(PKG)/csrc/temporal_kernel.hip $(PKG)/csrc/upscale_kernel.hip $(PKG)/csrc/bodies_kernel.hip $(PKG)/csrc/sensor_kernel.hip $(PKG)/csrc/api_sensor.hip $(PKG)/csrc/stars_kernel.hip $(PKG)/csrc/api_stars.hip $(PKG)/csrc/lens_kernel.hip $(PKG)/csrc/api_lens.hip
+HIP_SRC  := $(PKG)/csrc/render_kernel.hip $(PKG)/csrc/schedule_kernel.hip $(PKG)/csrc/sample_set_kernel.hip $(PKG)/csrc/selftest_kernel.hip $(PKG)/csrc/scene_pack.hip $(PKG)/csrc/api_context.hip $(PKG)/csrc/api_bodies.hip $(PKG)/csrc/api_render.hip $(PKG)/csrc/api_sample_sets.hip $(PKG)/csrc/api_reconstruct.hip $(PKG)/csrc/api_queries.hip $(PKG)/csrc/api_selftest.hip $(PKG)/csrc/api_dropin.hip $(PKG)/csrc/microbench.hip $(PKG)/csrc/multi_gpu.hip $(PKG)/csrc/bvh_lbvh.hip $(PKG)/csrc/gbuffer_kernel.hip $(PKG)/csrc/coverage_kernel.hip $(PKG)/csrc/raycast_kernel.hip $(PKG)/csrc/denoise_kernel.hip $(PKG)/csrc/temporal_kernel.hip $(PKG)/csrc/upscale_kernel.hip $(PKG)/csrc/bodies_kernel.hip $(PKG)/csrc/sensor_kernel.hip $(PKG)/csrc/api_sensor.hip $(PKG)/csrc/stars_kernel.hip $(PKG)/csrc/api_stars.hip $(PKG)/csrc/lens_kernel.hip $(PKG)/csrc/api_lens.hip
 HOST_OBJ := $(patsubst $(PKG)/host/%.cpp,$(BUILD)/host_%.o,$(HOST_SRC))
 HIP_OBJ  := $(patsubst $(PKG)/csrc/%.hip,$(BUILD)/hip_%.o,$(HIP_SRC))
 HEADERS  := $(wildcard include/*.h) $(wildcard $(PKG)/host/*.hpp) $(wildcard $(PKG)/csrc/*.h)

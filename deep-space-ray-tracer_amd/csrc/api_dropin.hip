@@ -1,5 +1,5 @@
 // api_dropin.hip -- the drop-in layer: the reference's own entry points (build_gpu_scene, gpu_render_scene, free_gpu_scene) on one process-wide context with its
-// cache of the converted scene.  Calls the public entry points of api_context.hip and api_render.hip and the content-hash launcher of render_kernel.hip.
+// cache of the converted scene.  Calls the public entry points of api_context.hip and api_render.hip and the content-hash launcher of selftest_kernel.hip.
 #include <cassert>
 #include <cstdlib>
 #include <mutex>

@@ -105,6 +105,11 @@ inline void pack_camera(const GPUCamera& c, float (&cam)[12]) {
                              c.horizontal.x, c.horizontal.y, c.horizontal.z, c.vertical.x, c.vertical.y, c.vertical.z};
     std::memcpy(cam, cam12, sizeof cam12);
 }
+// The 21-float camera block of TemporalArgs / StarsArgs (launchers.h): those twelve and the basis u, v, w.
+inline void pack_camera21(const GPUCamera& c, float (&cam)[21]) {
+    static_assert(offsetof(GPUCamera, w) == 18 * sizeof(float), "origin, lower_left_corner, horizontal, vertical, u, v, w: the first 21 floats of GPUCamera");
+    std::memcpy(cam, &c, sizeof cam);
+}
 
 inline float bits(int i) { float f; std::memcpy(&f, &i, 4); return f; }
 

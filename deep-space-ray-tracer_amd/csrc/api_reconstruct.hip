@@ -124,11 +124,7 @@ int denoise_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, c
         a.cl = b.cl[0]; a.vl = b.vl[0]; a.nr = b.nr; a.xf = b.xf;
         a.prev = (const float4*)t->prev; a.next = (float4*)t->next; a.prev_xy = t->prev_xy; a.weight = t->weight;
         a.counts = d_n; a.samples_done = samples_done; a.width = desc->width; a.height = desc->height;
-        if (t->prev_camera) {
-            const GPUCamera& c = *t->prev_camera;
-            const DsrtF3 v[7] = {c.origin, c.lower_left_corner, c.horizontal, c.vertical, c.u, c.v, c.w};
-            for (int k = 0; k < 7; ++k) { a.cam[3 * k] = v[k].x; a.cam[3 * k + 1] = v[k].y; a.cam[3 * k + 2] = v[k].z; }
-        }
+        if (t->prev_camera) pack_camera21(*t->prev_camera, a.cam);
         a.alpha_min = t->tp->alpha_min; a.normal_cos_min = t->tp->normal_cos_min; a.plane_tol = t->tp->plane_tol; a.min_support = t->tp->min_support;
         BodyMotionArgs mo;                                                            // (all zero without a motion: no prim_id, no body moved)
         std::memset(&mo, 0, sizeof mo);

@@ -1,6 +1,6 @@
 // api_render.hip -- a render launch in stages (plan, working buffers, one of three pre-passes, launch and resolve, stats) as render_impl, and the entry points
 // that are nothing but such a launch: dsrt_render, dsrt_render_batch, their _to_host forms, the shard layout and the tile de-interleave.
-// Calls the launchers of render_kernel.hip and api_context.hip (experiment_word); api_sample_sets.hip calls render_impl.
+// Calls the launchers of render_kernel.hip, schedule_kernel.hip and sample_set_kernel.hip, and api_context.hip (experiment_word); api_sample_sets.hip calls render_impl.
 #include <algorithm>
 #include <cmath>
 
@@ -44,6 +44,7 @@ struct RenderPlan {
     Tiling t;
     RenderArgs a;                     // complete but for what grow_render_buffers (accum_fixed of the context's own sums, spill, sched) and the pre-pass (tile order, batch table) add
     RenderVariant variant;
+    bool device_libm;                 // DsrtRenderDesc.math_mode 1: which compilation of render_kernel.hip `rl` is, and the resolve's powf
     const RenderLaunchers* rl;
     PrePass pre;
     bool cull, probe;                 // the pre-pass removes provably empty tiles / re-sorts the heavy tiles by measured cost ...
@@ -61,7 +62,8 @@ int plan_render(const DsrtContext* ctx, const DsrtRenderDesc* desc, uint8_t* d_r
     const PackedScene& sc = *scp;
     if (desc->rng_mode != 0 && desc->rng_mode != 1) { set_error("dsrt_render: rng_mode must be 0 (reference LCG stream per pixel) or 1 (Philox4x32-10 stream per sample)"); return DSRT_ERR_INVALID; }
     if (desc->math_mode != 0 && desc->math_mode != 1) { set_error("dsrt_render: math_mode must be 0 (deterministic sin / cos / pow shared with the CPU oracle) or 1 (the device math library's)"); return DSRT_ERR_INVALID; }
-    p.rl = &render_launchers(desc->math_mode == 1);
+    p.device_libm = desc->math_mode == 1;
+    p.rl = &render_launchers(p.device_libm);
     if (desc->tune[3] & ~DSRT_TUNE_FLAG_MASK) { set_error("dsrt_render: tune[3] has bits set that this ABI version does not define (DSRT_TUNE_* in include/dsrt.h)"); return DSRT_ERR_INVALID; }
     const uint32_t flags = (uint32_t)desc->tune[3];
     const uint32_t xp = experiment_word();
@@ -327,7 +329,7 @@ int launch_and_resolve(const RenderPlan& p, hipStream_t stream) {
     const RenderArgs& a = p.a;
     if (p.pre == PrePass::Batch) HIP_TRY(p.rl->launch_render_batch(a, p.variant.rng_mode, p.blocks, p.variant.lean, stream));
     else HIP_TRY(p.rl->launch_render(a, p.variant, p.blocks, stream));
-    if (p.own_sums) HIP_TRY(p.rl->launch_resolve(a.accum_fixed, a.frame.spp, a.frame.inv_gamma, p.out_pixels, a.out_rgb8, a.out_f32, nullptr, nullptr, stream));
+    if (p.own_sums) HIP_TRY(launch_resolve(a.accum_fixed, a.frame.spp, a.frame.inv_gamma, p.device_libm, p.out_pixels, a.out_rgb8, a.out_f32, nullptr, nullptr, stream));
     return DSRT_OK;
 }
 

@@ -1,5 +1,5 @@
 // api_sample_sets.hip -- sample sets and adaptive sampling: the accumulate, resolve, masked, select and adaptive entry points and what they refuse.
-// Calls api_render.hip (render_impl) and the launchers of render_kernel.hip; api_reconstruct.hip shares the checks of a frame's description declared in api_internal.h.
+// Calls api_render.hip (render_impl) and the launchers of sample_set_kernel.hip; api_reconstruct.hip shares the checks of a frame's description declared in api_internal.h.
 #include "api_internal.h"
 
 using namespace dsrt;
@@ -95,12 +95,12 @@ int resolve_sums(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, c
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = launch_begin(ctx, stream, {}))) return rc;                             // the context's last launch (an accumulate into these sums, maybe) comes first
-    const RenderLaunchers& rl = render_launchers(desc->math_mode == 1);
+    const bool device_libm = desc->math_mode == 1;
     const size_t px = (size_t)desc->width * desc->height;
     const unsigned long long* sum = (const unsigned long long*)acc->sum;
     const unsigned long long* sq = d_var_of_mean ? (const unsigned long long*)acc->sum_sq : nullptr;       // (the second moment serves the variance only)
-    HIP_TRY(per_pixel ? rl.launch_resolve_counts(sum, d_n, inv_gamma_of(*desc), px, d_rgb8, d_f32, sq, d_var_of_mean, stream)
-                      : rl.launch_resolve(sum, samples_done, inv_gamma_of(*desc), px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
+    HIP_TRY(per_pixel ? launch_resolve_counts(sum, d_n, inv_gamma_of(*desc), device_libm, px, d_rgb8, d_f32, sq, d_var_of_mean, stream)
+                      : launch_resolve(sum, samples_done, inv_gamma_of(*desc), device_libm, px, d_rgb8, d_f32, sq, d_var_of_mean, stream));
     return DSRT_OK;
 }
 

@@ -1,6 +1,6 @@
 // api_selftest.hip -- the self-test hooks of include/dsrt.h: poke and read the resident scene's words, and run the device math, the kernel helpers and the
 // Philox stream on plain arrays; read what the scheduling pre-pass of the context's last launch left, and run its three array kernels on plain arrays.
-// Calls the self-test launchers of render_kernel.hip; nothing calls into this file.
+// Calls the self-test launchers of selftest_kernel.hip and schedule_kernel.hip; nothing calls into this file.
 #include "api_internal.h"
 
 using namespace dsrt;

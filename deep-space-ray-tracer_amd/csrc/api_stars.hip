@@ -52,8 +52,7 @@ int stars_impl(const char* fn, DsrtContext* ctx, const DsrtRenderDesc* desc, con
     a.dir = in->dir; a.flux = in->flux; a.linear_in = out->linear_out ? in->linear_in : nullptr;
     a.count = in->count; a.width = desc->width; a.height = desc->height; a.occlusion = in->occlusion != 0;
     a.stack_entries = std::max(1, std::min(64, sc->view.stack_need));       // upload refuses trees that need more than 64
-    static_assert(offsetof(GPUCamera, w) == 18 * sizeof(float), "origin, lower_left_corner, horizontal, vertical, u, v, w: the first 21 floats of GPUCamera");
-    std::memcpy(a.cam, &ctx->frame.camera, sizeof a.cam);
+    pack_camera21(ctx->frame.camera, a.cam);
     a.list = ctx->st_list.p; a.list_len = ctx->st_ctrl.p; a.status = ctx->st_ctrl.p + 1;
     a.acc = image ? ctx->st_acc.p : nullptr;
     a.layer = out->layer; a.linear_out = out->linear_out; a.xy = out->xy; a.star_status = out->status;

@@ -1,12 +1,12 @@
 // denoise_kernel.hip -- the variance-guided a-trous filter of include/dsrt.h (DENOISER): three kernels, one thread per pixel each.
 //
-//   prepare   mean and variance of the mean from the integer sums (the resolve's double arithmetic, restated: render_kernel.hip keeps its own), and everything a tap
+//   prepare   mean and variance of the mean from the integer sums (pixel_arith.h: the resolve's own functions), and everything a tap
 //             reads packed into 16-byte records, so that a tap is five dwordx4 loads:
 //                 cl = {c.rgb, L(c)}   vl = {v.rgb, L(v)}   nr = {N, range}   xf = {X, F ? 1 : 0}   al = {A, 0}
 //             L(c) and L(v) are cached beside the values they are the luminance of: computed once, by the operations the header writes, wherever c and v are written.
 //   a-trous   one launch per iteration, cl / vl ping-ponging; 16 x 16 pixels per workgroup.  The sums run in the header's order (dy outer, dx inner, one
 //             accumulator each): nothing is reassociated, a skipped tap is a branch.
-//   output    d_linear, d_var and the resolve's tone map + 8-bit store of the filtered mean; templated over where powf comes from (DsrtRenderDesc.math_mode).
+//   output    d_linear, d_var and the tone map + 8-bit store (pixel_arith.h) of the filtered mean; templated over where powf comes from (DsrtRenderDesc.math_mode).
 // prepare and output are bodies templated over "has alpha" (include/dsrt.h, COVERAGE DEMODULATION: dsrt_denoise_accumulated_coverage) behind two kernels each:
 // the plain denoiser's, unchanged instruction for instruction, and the _coverage ones, which divide the filterable pixels' c and v by alpha and alpha^2 at the
 // start and multiply them back at the end.
@@ -15,13 +15,10 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off, no fast-math -- IEEE division and square root and the absence of contraction are the contract.
 #include <cfloat>
 
-#include "../../include/dsrt_detmath.h"
 #include "launchers.h"
+#include "pixel_arith.h"
 
 namespace dsrt {
-
-__device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
 // prepare's body, over "has alpha" (include/dsrt.h, COVERAGE DEMODULATION): HAS_ALPHA = false is the plain denoiser's kernel, instruction for instruction.
 template <bool HAS_ALPHA>
@@ -35,16 +32,13 @@ __device__ __forceinline__ void denoise_prepare(const unsigned long long* __rest
     const uint32_t cnt = counts ? counts[i] : (uint32_t)samples_done;
     float c[3] = {0.0f, 0.0f, 0.0f}, v[3] = {0.0f, 0.0f, 0.0f};
     if (cnt) {
-        const double unit = 1.0 / 1048576.0 / (double)cnt;
-        for (int ch = 0; ch < 3; ++ch) c[ch] = (float)((double)sums[i * 3 + ch] * unit);
+        for (int ch = 0; ch < 3; ++ch) c[ch] = sum_mean(sums[i * 3 + ch], (double)cnt);
     }
     if (cnt >= 2u) {
         const double n = (double)cnt;
         for (int ch = 0; ch < 3; ++ch) {
-            const double s = (double)sums[i * 3 + ch] * (1.0 / 1048576.0), s2 = (double)sums_sq[i * 3 + ch] * (1.0 / 1048576.0);
-            double var = (s2 - s * s / n) / (n - 1.0);
-            var = var > 0.0 ? var : 0.0;
-            v[ch] = (float)(var / n);
+            double s;
+            v[ch] = (float)(sum_variance(sums[i * 3 + ch], sums_sq[i * 3 + ch], n, s) / n);
         }
     }
     const float r = range[i];
@@ -144,13 +138,6 @@ __global__ __launch_bounds__(256) void dsrt_denoise_atrous_kernel(const float4* 
     }
 }
 
-template <bool DEVICE_LIBM>
-__device__ __forceinline__ float tone(float c, float inv_gamma) {       // the resolve's tone map (render_kernel.hip, dsrt_resolve_kernel), operation for operation
-    c = fminf(fmaxf(c, 0.0f), 10.0f);
-    c = DEVICE_LIBM ? ::powf(c, inv_gamma) : dsrt_powf(c, inv_gamma);
-    return fminf(1.0f, fmaxf(0.0f, c));
-}
-
 // output's body, over "has alpha": the filterable pixels' c and v multiplied back by a and a*a (xf.w is prepare's F_p, alpha_min included) before anything is written.
 template <bool DEVICE_LIBM, bool HAS_ALPHA>
 __device__ __forceinline__ void denoise_output(const float4* __restrict__ cl, const float4* __restrict__ vl, const float4* __restrict__ xf, const float* __restrict__ alpha,
@@ -172,13 +159,9 @@ __device__ __forceinline__ void denoise_output(const float4* __restrict__ cl, co
         out_var[i * 3 + 0] = v.x; out_var[i * 3 + 1] = v.y; out_var[i * 3 + 2] = v.z;
     }
     if (!out_rgb8 && !out_f32) return;
-    const float r = tone<DEVICE_LIBM>(c.x, inv_gamma), g = tone<DEVICE_LIBM>(c.y, inv_gamma), b = tone<DEVICE_LIBM>(c.z, inv_gamma);
-    if (out_rgb8) {
-        out_rgb8[i * 3 + 0] = (unsigned char)(255.99f * r);
-        out_rgb8[i * 3 + 1] = (unsigned char)(255.99f * g);
-        out_rgb8[i * 3 + 2] = (unsigned char)(255.99f * b);
-    }
-    if (out_f32) { out_f32[i * 3 + 0] = r; out_f32[i * 3 + 1] = g; out_f32[i * 3 + 2] = b; }
+    const F3 col = mk(tone_map<DEVICE_LIBM>(c.x, inv_gamma), tone_map<DEVICE_LIBM>(c.y, inv_gamma), tone_map<DEVICE_LIBM>(c.z, inv_gamma));
+    if (out_rgb8) store_rgb8(out_rgb8, i * 3, col);
+    if (out_f32) { out_f32[i * 3 + 0] = col.x; out_f32[i * 3 + 1] = col.y; out_f32[i * 3 + 2] = col.z; }
 }
 
 template <bool DEVICE_LIBM>

@@ -13,6 +13,9 @@
 #define dsrt_sinf(x) sinf(x)
 #define dsrt_cosf(x) cosf(x)
 #define dsrt_powf(x, y) powf(x, y)
+namespace dsrt { constexpr bool kDeviceLibm = true; }                 // the same choice as a template argument (pixel_arith.h: tone_map)
+#else
+namespace dsrt { constexpr bool kDeviceLibm = false; }
 #endif
 
 namespace dsrt {

@@ -19,16 +19,12 @@ struct RenderLaunchers {
     hipError_t (*launch_render)(const RenderArgs& a, const RenderVariant& v, int blocks, hipStream_t stream);
     hipError_t (*launch_render_batch)(const RenderArgs& a, int rng_mode, int blocks, bool lean, hipStream_t stream);
     hipError_t (*launch_probe)(const RenderArgs& a, int blocks, bool lean, hipStream_t stream);
-    hipError_t (*launch_resolve)(const unsigned long long* sums, int samples_done, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
-                                 const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
-    hipError_t (*launch_resolve_counts)(const unsigned long long* sums, const uint32_t* counts, float inv_gamma, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
-                                        const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
 };
 const RenderLaunchers& compiled_render_launchers();
 namespace devlibm { const RenderLaunchers& compiled_render_launchers(); }
-const RenderLaunchers& render_launchers(bool device_libm);          // device_api.hip: the table of one of the two
+const RenderLaunchers& render_launchers(bool device_libm);          // api_render.hip: the table of one of the two
 
-// render_kernel.hip, first compilation only: the scheduling pre-pass ...
+// schedule_kernel.hip: the scheduling pre-pass
 hipError_t launch_tile_order(const DeviceScene& S, const FrameParams& P, uint32_t* cost, uint32_t* order, uint32_t* sched, uint32_t items_per_pixel,
                              uint32_t resident_lanes, bool cull, hipStream_t stream, const BatchFrame* batch = nullptr, uint32_t frames = 1, uint32_t stride = 0);
 // (dsrt_selftest_tile_order: the order kernel alone, one frame, on cost words the caller supplies -- no cost kernel in front)
@@ -38,14 +34,19 @@ hipError_t launch_tile_reorder(const uint32_t* work, uint32_t* order, uint32_t* 
 hipError_t launch_batch_table(BatchFrame* table, const uint32_t* sched, uint32_t sched_stride, uint32_t frames, uint32_t tt, int rng_mode, int spp, int light_chunk_len,
                               uint32_t* total_items, hipStream_t stream);
 
-// ... adaptive sampling: the lists of a masked accumulate launch (with its update of the sample counts), the counts of an unmasked pass, the convergence test
+// sample_set_kernel.hip: the lists of a masked accumulate launch (with its update of the sample counts), the counts of an unmasked pass, the convergence test ...
 hipError_t launch_pixel_list(const FrameParams& P, const uint32_t* order, const uint32_t* sched, const uint8_t* mask, uint32_t* list, uint32_t* list_len,
                              uint32_t* n, uint32_t count, hipStream_t stream);
 hipError_t launch_add_count(uint32_t* n, uint32_t count, size_t n_pixels, hipStream_t stream);
 hipError_t launch_select_unconverged(const unsigned long long* sums, const unsigned long long* sums_sq, const uint32_t* counts, size_t n_pixels, float rel_tol, float floor_,
                                      uint32_t n_min, uint32_t n_max, uint8_t* mask, uint32_t* n_active, hipStream_t stream);
+// ... and the resolve of the sums to an image, with n = samples_done for every pixel or each pixel's own counts[i]; the outputs that are not null are written
+hipError_t launch_resolve(const unsigned long long* sums, int samples_done, float inv_gamma, bool device_libm, size_t n_pixels, uint8_t* out_rgb8, float* out_f32,
+                          const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
+hipError_t launch_resolve_counts(const unsigned long long* sums, const uint32_t* counts, float inv_gamma, bool device_libm, size_t n_pixels, uint8_t* out_rgb8,
+                                 float* out_f32, const unsigned long long* sums_sq, float* out_var, hipStream_t stream);
 
-// ... tile de-interleave, the drop-in layer's content hash and the self-test hooks
+// selftest_kernel.hip: tile de-interleave, the drop-in layer's content hash and the self-test hooks
 hipError_t launch_deinterleave(const uint8_t* gathered, uint8_t* image, int W, int H, int tile, int tiles_x, int shard_count,
                                size_t shard_stride_bytes, hipStream_t stream);
 hipError_t launch_content_hash(const uint32_t* words, size_t n_words, uint64_t salt, uint64_t* d_hash2, hipStream_t stream);

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "device_math.h"
+#include "pixel_arith.h"
 
 namespace dsrt {
 
@@ -498,15 +499,10 @@ __device__ __forceinline__ void advance_step(LaneOf<MOMENTS>& ln, const RenderAr
             // tone map + store :1003-1030
             float inv_spp = 1.0f / (float)spp;
             F3 col = accum * inv_spp;
-            col = mk(fmaxf(col.x, 0.0f), fmaxf(col.y, 0.0f), fmaxf(col.z, 0.0f));
-            col = mk(fminf(col.x, 10.0f), fminf(col.y, 10.0f), fminf(col.z, 10.0f));
-            col = mk(dsrt_powf(col.x, P.inv_gamma), dsrt_powf(col.y, P.inv_gamma), dsrt_powf(col.z, P.inv_gamma));
-            col = clamp01(col);
+            col = tone_map<kDeviceLibm>(col, P.inv_gamma);
             const size_t o = (size_t)out_index * 3;
             if constexpr (!PROBE) {                             // (the probe launch measures, it has no image: in a batch its frame is not even the buffer's)
-                args.out_rgb8[o + 0] = (unsigned char)(255.99f * col.x);
-                args.out_rgb8[o + 1] = (unsigned char)(255.99f * col.y);
-                args.out_rgb8[o + 2] = (unsigned char)(255.99f * col.z);
+                store_rgb8(args.out_rgb8, o, col);
                 if (args.out_f32) { args.out_f32[o + 0] = col.x; args.out_f32[o + 1] = col.y; args.out_f32[o + 2] = col.z; }
             }
             if (COUNT && (args.steal & 8) && args.out_f32) {

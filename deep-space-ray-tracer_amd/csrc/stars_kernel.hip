@@ -20,19 +20,18 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off, no fast-math, as raycast_kernel.hip.
 #include "hit_record.h"
 #include "launchers.h"
+#include "pixel_arith.h"
 
 namespace dsrt {
 
 namespace {
 
-__device__ __forceinline__ float s_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
 // include/dsrt.h, POINT SOURCES step 1: TEMPORAL ACCUMULATION's projection of D, operation by operation.  C: origin, lower_left_corner, horizontal, vertical, u, v, w.
 __device__ __forceinline__ bool project_star(const float* C, int W, int H, float Dx, float Dy, float Dz, float& fx, float& fy) {
     const float ex = C[3] - C[0], ey = C[4] - C[1], ez = C[5] - C[2];
-    const float da = s_dot3(Dx, Dy, Dz, C[12], C[13], C[14]), db = s_dot3(Dx, Dy, Dz, C[15], C[16], C[17]), dc = s_dot3(Dx, Dy, Dz, C[18], C[19], C[20]);
-    const float eu = s_dot3(ex, ey, ez, C[12], C[13], C[14]), ev = s_dot3(ex, ey, ez, C[15], C[16], C[17]), ew = s_dot3(ex, ey, ez, C[18], C[19], C[20]);
-    const float hu = s_dot3(C[6], C[7], C[8], C[12], C[13], C[14]), vv = s_dot3(C[9], C[10], C[11], C[15], C[16], C[17]);
+    const float da = dot3(Dx, Dy, Dz, C[12], C[13], C[14]), db = dot3(Dx, Dy, Dz, C[15], C[16], C[17]), dc = dot3(Dx, Dy, Dz, C[18], C[19], C[20]);
+    const float eu = dot3(ex, ey, ez, C[12], C[13], C[14]), ev = dot3(ex, ey, ez, C[15], C[16], C[17]), ew = dot3(ex, ey, ez, C[18], C[19], C[20]);
+    const float hu = dot3(C[6], C[7], C[8], C[12], C[13], C[14]), vv = dot3(C[9], C[10], C[11], C[15], C[16], C[17]);
     const float k = ew / dc;
     if (!(k > 0.0f)) return false;
     const float s = (da * k - eu) / hu, t = (db * k - ev) / vv;

@@ -30,13 +30,11 @@
 #include <cfloat>
 
 #include "launchers.h"
+#include "pixel_arith.h"
 
 namespace dsrt {
 
 namespace {
-__device__ __forceinline__ float t_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-__device__ __forceinline__ float t_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
 template <bool kMotion, bool kShaded>
 __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const BodyMotionArgs* mo, const ShadingArgs* sh, const float4* pose_lds) {
     static_assert(kMotion || !kShaded, "the sun state comes with the motion stage");
@@ -93,9 +91,9 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Body
         const float* C = a.cam;                                              // origin, lower_left_corner, horizontal, vertical, u, v, w
         const float Dx = hxx - C[0], Dy = hxy - C[1], Dz = hxz - C[2];
         const float ex = C[3] - C[0], ey = C[4] - C[1], ez = C[5] - C[2];
-        const float da = t_dot3(Dx, Dy, Dz, C[12], C[13], C[14]), db = t_dot3(Dx, Dy, Dz, C[15], C[16], C[17]), dc = t_dot3(Dx, Dy, Dz, C[18], C[19], C[20]);
-        const float eu = t_dot3(ex, ey, ez, C[12], C[13], C[14]), ev = t_dot3(ex, ey, ez, C[15], C[16], C[17]), ew = t_dot3(ex, ey, ez, C[18], C[19], C[20]);
-        const float hu = t_dot3(C[6], C[7], C[8], C[12], C[13], C[14]), vv = t_dot3(C[9], C[10], C[11], C[15], C[16], C[17]);
+        const float da = dot3(Dx, Dy, Dz, C[12], C[13], C[14]), db = dot3(Dx, Dy, Dz, C[15], C[16], C[17]), dc = dot3(Dx, Dy, Dz, C[18], C[19], C[20]);
+        const float eu = dot3(ex, ey, ez, C[12], C[13], C[14]), ev = dot3(ex, ey, ez, C[15], C[16], C[17]), ew = dot3(ex, ey, ez, C[18], C[19], C[20]);
+        const float hu = dot3(C[6], C[7], C[8], C[12], C[13], C[14]), vv = dot3(C[9], C[10], C[11], C[15], C[16], C[17]);
         const float k = ew / dc;
         if (k > 0.0f) {
             const float s = (da * k - eu) / hu, t = (db * k - ev) / vv;
@@ -123,7 +121,7 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Body
                 if (gx < 0 || gx >= W) continue;
                 const float4* rec = a.prev + ((size_t)gy * (size_t)W + (size_t)gx) * 4;
                 const float4 cq = rec[0], xq = rec[3];
-                guarded |= cq.w > 0.0f && t_dot3(hnx, hny, hnz, xq.x - hxx, xq.y - hxy, xq.z - hxz) > tol;
+                guarded |= cq.w > 0.0f && dot3(hnx, hny, hnz, xq.x - hxx, xq.y - hxy, xq.z - hxz) > tol;
                 if constexpr (kShaded) edge_prev |= cq.w > 0.0f && !(xq.w == 0.0f || xq.w == sp);
             }
         }
@@ -136,8 +134,8 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Body
             const float4* rec = a.prev + ((size_t)qy * (size_t)W + (size_t)qx) * 4;
             const float4 cq = rec[0], vq = rec[1], nq = rec[2], xq = rec[3];
             if (!(cq.w > 0.0f)) continue;
-            if (!(t_dot3(hnx, hny, hnz, nq.x, nq.y, nq.z) >= a.normal_cos_min)) continue;
-            if (!(fabsf(t_dot3(hnx, hny, hnz, xq.x - hxx, xq.y - hxy, xq.z - hxz)) <= tol)) continue;
+            if (!(dot3(hnx, hny, hnz, nq.x, nq.y, nq.z) >= a.normal_cos_min)) continue;
+            if (!(fabsf(dot3(hnx, hny, hnz, xq.x - hxx, xq.y - hxy, xq.z - hxz)) <= tol)) continue;
             const float b = bw[k];
             if constexpr (kShaded) {
                 seen_g |= b >= 0.99f;                                        // what the stage without the sun state would have accumulated
@@ -163,8 +161,8 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Body
             c0 = beta * (sc0 / sw) + alpha * cp.x; c1 = beta * (sc1 / sw) + alpha * cp.y; c2 = beta * (sc2 / sw) + alpha * cp.z;
             v0 = b2 * (sv0 / sw) + a2 * vp.x; v1 = b2 * (sv1 / sw) + a2 * vp.y; v2 = b2 * (sv2 / sw) + a2 * vp.z;
             m = nf / alpha;
-            a.cl[p] = make_float4(c0, c1, c2, t_lum(c0, c1, c2));
-            a.vl[p] = make_float4(v0, v1, v2, t_lum(v0, v1, v2));
+            a.cl[p] = make_float4(c0, c1, c2, lum(c0, c1, c2));
+            a.vl[p] = make_float4(v0, v1, v2, lum(v0, v1, v2));
         }
     }
 

@@ -7,7 +7,7 @@
 //   upscale   one lane per OUTPUT pixel, 16 x 16 pixels per workgroup: the pixel's own full-resolution guides, the 4 x 4 low-resolution taps gathered straight
 //             through L1 / L2 (the s^2 output pixels over one low-resolution pixel share its sixteen taps, and a workgroup's footprint is (16/s + 3)^2 records
 //             per array), both levels of the header in its order (qy outer, qx inner, one accumulator per sum: nothing is reassociated, a skipped tap is a
-//             branch), then the resolve's tone map and 8-bit store; templated over where powf comes from (DsrtRenderDesc.math_mode).
+//             branch), then the tone map and 8-bit store (pixel_arith.h); templated over where powf comes from (DsrtRenderDesc.math_mode).
 //
 // With coverage (include/dsrt.h, COVERAGE-AWARE UPSCALER) both kernels have a second instantiation behind a symbol of its own, HAS_ALPHA = true of the same bodies;
 // HAS_ALPHA = false is the kernel above, instruction for instruction.  pack then stores the low-resolution alpha in nn.w, and the gather divides every usable tap's
@@ -20,21 +20,10 @@
 #include <cfloat>
 
 #include "../../include/dsrt.h"
-#include "../../include/dsrt_detmath.h"
 #include "launchers.h"
+#include "pixel_arith.h"
 
 namespace dsrt {
-
-namespace {
-__device__ __forceinline__ float up_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
-template <bool DEVICE_LIBM>
-__device__ __forceinline__ float up_tone(float c, float inv_gamma) {    // the resolve's tone map (render_kernel.hip, dsrt_resolve_kernel), operation for operation
-    c = fminf(fmaxf(c, 0.0f), 10.0f);
-    c = DEVICE_LIBM ? ::powf(c, inv_gamma) : dsrt_powf(c, inv_gamma);
-    return fminf(1.0f, fmaxf(0.0f, c));
-}
-}  // namespace
 
 // pack's body, over "has alpha": HAS_ALPHA = false is the plain upscaler's kernel, instruction for instruction.
 template <bool HAS_ALPHA>

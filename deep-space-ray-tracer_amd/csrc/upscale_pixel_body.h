@@ -47,11 +47,11 @@
                 const float4 nq = a.nn[q], xq = a.xx[q], aq = a.aa[q];
                 const float bx = fmaxf(1.0f - 0.5f * fabsf((float)qx - fx), 0.0f);
                 const float b = bx * by;
-                float wn = fmaxf(up_dot3(npx, npy, npz, nq.x, nq.y, nq.z), 0.0f);
+                float wn = fmaxf(dot3(npx, npy, npz, nq.x, nq.y, nq.z), 0.0f);
                 for (int k = 0; k < a.normal_power_log2; ++k) wn = wn * wn;
-                const float ez = fabsf(up_dot3(npx, npy, npz, xq.x - xpx, xq.y - xpy, xq.z - xpz)) / den_z;
+                const float ez = fabsf(dot3(npx, npy, npz, xq.x - xpx, xq.y - xpy, xq.z - xpz)) / den_z;
                 const float dax = aq.x - apx, day = aq.y - apy, daz = aq.z - apz;
-                const float ea2 = up_dot3(dax, day, daz, dax, day, daz) / sa2;
+                const float ea2 = dot3(dax, day, daz, dax, day, daz) / sa2;
                 if constexpr (HAS_ALPHA) {                               // the covered part's colour and variance, weighed by the share of the samples that made them
                     const float wt = ((b * wn) * al) / ((1.0f + ez * ez) * (1.0f + ea2));
                     const float wt2 = wt * wt, al2 = al * al;
@@ -135,10 +135,6 @@
     if (a.out_support) a.out_support[P] = support;
     if constexpr (HAS_ALPHA) { if (out_level) out_level[P] = (uint8_t)level; }
     if (!a.out_rgb8 && !a.out_f32) return;
-    const float r = up_tone<DEVICE_LIBM>(c0, a.inv_gamma), g = up_tone<DEVICE_LIBM>(c1, a.inv_gamma), b = up_tone<DEVICE_LIBM>(c2, a.inv_gamma);
-    if (a.out_rgb8) {
-        a.out_rgb8[P * 3 + 0] = (unsigned char)(255.99f * r);
-        a.out_rgb8[P * 3 + 1] = (unsigned char)(255.99f * g);
-        a.out_rgb8[P * 3 + 2] = (unsigned char)(255.99f * b);
-    }
-    if (a.out_f32) { a.out_f32[P * 3 + 0] = r; a.out_f32[P * 3 + 1] = g; a.out_f32[P * 3 + 2] = b; }
+    const F3 col = mk(tone_map<DEVICE_LIBM>(c0, a.inv_gamma), tone_map<DEVICE_LIBM>(c1, a.inv_gamma), tone_map<DEVICE_LIBM>(c2, a.inv_gamma));
+    if (a.out_rgb8) store_rgb8(a.out_rgb8, P * 3, col);
+    if (a.out_f32) { a.out_f32[P * 3 + 0] = col.x; a.out_f32[P * 3 + 1] = col.y; a.out_f32[P * 3 + 2] = col.z; }

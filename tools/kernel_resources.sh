@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development aid: register / spill / scratch figures of every kernel in csrc/render_kernel.hip, as the compiler reports them
+# Development aid: register / spill / scratch figures of every kernel in csrc/render_kernel.hip (the render, listed, batch and probe kernels), as the compiler reports them
 # (-Rpass-analysis=kernel-resource-usage), for both compilations (default and -DDSRT_DEVICE_LIBM).  Usage: tools/kernel_resources.sh [extra hipcc flags]
 set -e
 cd "$(dirname "$0")/.."
